@@ -4,19 +4,28 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...         (no launcher: bench.py starts the N ranks itself, self_launch())
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full     (everything below: roofline, parity, CPU baseline, ...)
 
 A "step" is one policy forward (DecentralPlannerNet.addGSO + forward) over one batch of synthetic
 input resident in HBM: BASELINE.json configs[1] = 10 agents, K=3, B=512 GSO+observation batch
 (seed 1337).  With N GPUs every rank runs its own replica on its own batch
 (independent rollout shards, no data-path collective): weak scaling, value = total agent-steps/s.
 
-Timing: W warm-up steps, then `--repeats` timed regions of EXACTLY K steps each, every region
-bracketed by barrier + torch.cuda.synchronize() on both sides, max over ranks per region; the
-reported region is the MEDIAN one (all of them are listed under `regions_ms`).  HIP events recorded
+A plain run (no --full) does only what the headline needs: set-up, pre-warm, W warm-up steps, ONE timed region of
+exactly K steps, then prints the line with the contract keys (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...).  `--dump-outputs DIR` writes what the last timed step returned (the logits, see dump_outputs())
+to DIR/*.npy; the inputs are seeded, so two builds given the same arguments can be compared output for output.
+Everything else this file measures or checks -- the roofline and its rocprofv3 passes, the pipelined and secondary
+records, other configurations, the parity gate against the CPU oracle, the CPU baseline and the side file -- runs
+only with `--full`, as described below.
+
+Timing: W warm-up steps (in a discarded region of their own), then `--repeats` timed regions of EXACTLY K steps
+each (default: 1, or 7 with --full), every region bracketed by barrier + torch.cuda.synchronize() on both sides, max
+over ranks per region; the reported region is the MEDIAN one (all of them are listed under `regions_ms`).  HIP events recorded
 on the launch stream around the same regions give the device-side time the roofline uses, so the
 kernel time can never exceed the step time it is part of.
 
-Rank 0 prints ONE JSON line of at most 6 KB (driver_line(): the contract keys, `roofline`, `cpu_baseline`, `parity`,
+With --full, rank 0 prints ONE JSON line of at most 6 KB (driver_line(): the contract keys, `roofline`, `cpu_baseline`, `parity`,
 `summary`, and `details_file` = the side file holding everything else: `secondary`, sweeps, shard records, notes).  `value`, `ms_per_step`, `dtype`, `roofline` and `parity` all describe the DEFAULT
 precision ("fp32": every fp32 operand exactly as three bf16 planes, six plane products on the bf16 MFMA, fp32
 accumulate -- no input domain, nothing narrower than the reference's fp32).  Besides the contract fields:
@@ -78,6 +87,42 @@ PRECISION_INFO = {
     2: {'name': 'split_f16', 'instr': 'v_mfma_f32_16x16x32_f16', 'peak': F16_MFMA_PEAK_TFLOPS, 'products': 3,
         'dtype': 'f32 operands as f16 hi+lo pairs (22 significand bits, |x| < 65504): NARROWER than f32'},
 }
+HEADLINE_DTYPE = 'f32 (bf16x3 exact operand split, f32 accumulate)'     # `dtype` of the line: PRECISION_INFO[0]
+
+
+def headline_precision(net, _native, result):
+    """The headline is measured in the model's default arithmetic 'fp32' = bf16x3 operand split (fp32-equivalent;
+    include/gnnpp.h GNNPP_PREC_FP32): states it in `result` and returns its code."""
+    prec = net._prec()
+    assert prec == _native.PREC_FP32, 'the headline is measured in the default (fp32-equivalent) arithmetic'
+    result['precision'] = PRECISION_INFO[prec]['name']
+    result['dtype'] = HEADLINE_DTYPE
+    result['dtype_detail'] = PRECISION_INFO[prec]['dtype']
+    return prec
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs: what the last timed step returned to its caller -- DecentralPlannerNet.forward's list of N
+    [B, 5] logit tensors -- stacked to [N, B, 5] float32 as DIR/logits.npy (C2: 100 KB, C5: 256 KB)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    logits = torch.stack([o.detach() for o in out]).float().cpu().numpy()
+    np.save(os.path.join(directory, 'logits.npy'), logits)
+    return logits.shape
+
+
+def check_rank_layout(result, args, rank_ordinals, rank_devices):
+    """One process per GPU, really: as many ranks in the group as the line claims, each on its own device (unless
+    GNNPP_BENCH_DEVICE pinned them to one on purpose: the gloo code-path check)."""
+    assert result['ranks_in_group'] == result['n_gpus'] == args.gpus, (result['ranks_in_group'], args.gpus)
+    if 'GNNPP_BENCH_DEVICE' not in os.environ:
+        # every rank on its OWN device ordinal of this node (what the launch controls); the physical identities
+        # (uuid / PCI bus id, as torch reports them) are stated beside it, not asserted: a runtime that reports
+        # one uuid for every GPU must not cost the line
+        assert len(set(rank_ordinals)) == args.gpus, rank_ordinals
+        result['rank_devices_distinct'] = len(set(map(str, rank_devices))) == args.gpus
+    else:
+        result['device_override'] = os.environ['GNNPP_BENCH_DEVICE']
 
 
 def roofline_block(kernel, info, flops, t_launch, exe_flops, lanes='', column_fill=1.0):
@@ -721,8 +766,17 @@ def main():
                     help='weak (default): every rank runs its own batch of the config\'s size; strong: the '
                          'config\'s batch is the GLOBAL batch, sharded over the ranks with sharding.shard_batch '
                          '(SURVEY.md section 8e: C5 = 128 graphs -> 16 per GPU at N = 8)')
-    ap.add_argument('--repeats', type=int, default=7,
-                    help='timed regions of exactly --steps steps each; the median one is reported')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed regions of exactly --steps steps each; the median one is reported (default: 1, '
+                         'or 7 with --full)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure / check everything beyond the headline: roofline (with its rocprofv3 passes), '
+                         'pipelined and secondary records, parity gate against the CPU oracle, CPU baseline, side '
+                         'file.  --no-cpu-baseline, --no-secondary, --pipeline-streams, --cpu-seconds and --pmc shape '
+                         'those extras and only act with --full')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (logits, [N, B, 5] float32) '
+                         'as DIR/logits.npy (rank 0)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-secondary', action='store_true', help='skip sweeps / rollout / exact-fp32 extras')
     ap.add_argument('--pipeline-streams', type=int, default=3,
@@ -745,6 +799,8 @@ def main():
                          'gpurun_out/bench/bench_<config>_full.json.  The printed line stays <= %d bytes and names it'
                          % DRIVER_LINE_MAX_BYTES)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:   # no launcher around us: run the N ranks ourselves
         sys.exit(self_launch(args, sys.argv[1:]))
@@ -794,9 +850,10 @@ def main():
     def timed_regions(fn, steps, repeats, collective=True):
         """`repeats` regions of exactly `steps` calls; per region (wall seconds max over ranks,
         device seconds from HIP events on the launch stream).  collective=False: rank-local (the
-        secondary measurements run on rank 0 only)."""
+        secondary measurements run on rank 0 only).  last_return[0]: what the last call returned."""
         dist = dist_all if collective else None
         out = []
+        ret = None
         for _ in range(repeats):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
@@ -806,7 +863,7 @@ def main():
             t0 = time.perf_counter()
             e0.record()
             for _ in range(steps):
-                fn()
+                ret = fn()
             e1.record()
             torch.cuda.synchronize()
             if dist is not None:
@@ -816,8 +873,10 @@ def main():
             if dist is not None:
                 _, _, wall = aggregate_throughput(1, wall, device=dev)    # max over ranks
             out.append((wall, e0.elapsed_time(e1) * 1e-3))
+        last_return[0] = ret
         return out
 
+    last_return = [None]
     dist_all = dist
     with torch.no_grad():
         t_pre = time.perf_counter()
@@ -825,8 +884,10 @@ def main():
             for _ in range(50):
                 step()
             torch.cuda.synchronize()
-        for _ in range(args.warmup):
-            out = step()
+        # the W warm-up steps run inside a region of their own (discarded): the region's one-time costs (first event
+        # records, first synchronisations) must not land in the first timed region, which a plain run reports
+        timed_regions(step, args.warmup, 1)
+        out = last_return[0]
         regions = timed_regions(step, args.steps, max(1, args.repeats))
     dist_all = None                              # everything below is rank-local
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
@@ -835,12 +896,14 @@ def main():
     # global batch, whose shards differ by at most one graph)
     value = (B_global if strong else world * B) * N * args.steps / elapsed
     value_rank = B * N * args.steps / elapsed             # this rank's own rate (what one GPU does)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_return[0], args.dump_outputs)
 
     # Secondary: the same K steps with `pipeline_streams` independent rollout batches in flight
     # (batch i on stream i % S).  Sequentially dependent steps of ONE batch cannot overlap, so this
     # is reported separately; it is what a rollout driver holding S episode batches per GPU gets.
     pipelined = None
-    if args.pipeline_streams > 1 and not args.no_secondary:
+    if args.full and args.pipeline_streams > 1 and not args.no_secondary:
         S_n = args.pipeline_streams
         nets, ins, streams = [net], [(obs, S)], [torch.cuda.Stream() for _ in range(S_n)]
         for i in range(1, S_n):
@@ -887,8 +950,9 @@ def main():
         'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': args.scaling,
         'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'prewarm_s': args.prewarm_seconds,
         'regions_ms': [round(1e3 * r[0], 4) for r in regions],
-        'timing': 'median of %d timed regions of exactly %d steps each (barrier + synchronize on both '
-                  'sides of every region, max over ranks)' % (len(regions), args.steps),
+        'timing': ('median of %d timed regions of exactly %d steps each' % (len(regions), args.steps)
+                   if len(regions) > 1 else 'one timed region of exactly %d steps' % args.steps) +
+                  ' (barrier + synchronize on both sides of every region, max over ranks)',
         'config': {'workload': 'policy forward (addGSO+forward), %d agents, %dx%d map GSO, K=%d, '
                                'batch=%d per GPU, eval mode, fp32 GSO resident in HBM; the SAME resident '
                                'batch every step (inputs are L2 / Infinity-Cache warm by construction)'
@@ -901,6 +965,17 @@ def main():
     }
     if pipelined is not None:
         result['pipelined'] = pipelined
+
+    if not args.full:                            # a plain run: the headline line and nothing else
+        if rank == 0:
+            headline_precision(net, _native, result)
+            check_rank_layout(result, args, rank_ordinals, rank_devices)
+            print(driver_line(result, write_details(result, args.details_file) if args.details_file else None),
+                  flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     if rank == 0:
       with rank_local_block(active=dist is not None):
@@ -924,8 +999,7 @@ def main():
 
           # ---- roofline of the dominant kernel, in the arithmetic the HEADLINE runs: the model's default precision
           # 'fp32' = bf16x3 operand split (fp32-equivalent; include/gnnpp.h GNNPP_PREC_FP32)
-          prec = net._prec()
-          assert prec == _native.PREC_FP32, 'the headline is measured in the default (fp32-equivalent) arithmetic'
+          prec = headline_precision(net, _native, result)
           info = PRECISION_INFO[prec]
           tiles = (M + 15) // 16
           fused = fused_rule(L, B, N, K, prec)
@@ -1001,9 +1075,6 @@ def main():
                                            'kernel, median over its workgroups)')
               rl['frac_at_effective_clock'] = rl['frac'] * NOMINAL_CLOCK_GHZ / clk
               rl['pipe_busy_frac_at_effective_clock'] = rl['pipe_busy_frac'] * NOMINAL_CLOCK_GHZ / clk
-          result['precision'] = info['name']
-          result['dtype'] = 'f32 (bf16x3 exact operand split, f32 accumulate)'
-          result['dtype_detail'] = info['dtype']
           gf_bytes = M * (1024 + 4 * N) + 196608.0 * K / 3
           result['step_breakdown_us'] = {
               'whole_step_wall': 1e6 * elapsed / args.steps, 'whole_step_device': 1e6 * dev_elapsed / args.steps,
@@ -1291,17 +1362,7 @@ def main():
                                   'c1_b1_agent_steps_per_s': N / medt1}
               result['cpu_baseline'] = cb
           result['summary'] = compact_summary(result)
-          # one process per GPU, really: as many ranks in the group as the line claims, each on its own device (unless
-          # GNNPP_BENCH_DEVICE pinned them to one on purpose: the gloo code-path check)
-          assert result['ranks_in_group'] == result['n_gpus'] == args.gpus, (result['ranks_in_group'], args.gpus)
-          if 'GNNPP_BENCH_DEVICE' not in os.environ:
-              # every rank on its OWN device ordinal of this node (what the launch controls); the physical identities
-              # (uuid / PCI bus id, as torch reports them) are stated beside it, not asserted: a runtime that reports
-              # one uuid for every GPU must not cost the line
-              assert len(set(rank_ordinals)) == args.gpus, rank_ordinals
-              result['rank_devices_distinct'] = len(set(map(str, rank_devices))) == args.gpus
-          else:
-              result['device_override'] = os.environ['GNNPP_BENCH_DEVICE']
+          check_rank_layout(result, args, rank_ordinals, rank_devices)
           # the line the driver parses: <= 6 KB (contract keys, roofline, cpu_baseline, parity, summary); the rest
           # (secondary records, sweeps, notes) in the side file it names
           print(driver_line(result, write_details(result, args.details_file)), flush=True)

@@ -1265,7 +1265,8 @@ def test_bench_prints_one_parseable_line_of_at_most_6_kb(dev, tmp_path):
     details = str(tmp_path / 'bench_full.json')
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '10', '--warmup', '3',
-                        '--repeats', '3', '--no-secondary', '--no-cpu-baseline', '--pmc', 'off', '--details-file', details],
+                        '--full', '--repeats', '3', '--no-secondary', '--no-cpu-baseline', '--pmc', 'off',
+                        '--details-file', details],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
@@ -1283,3 +1284,39 @@ def test_bench_prints_one_parseable_line_of_at_most_6_kb(dev, tmp_path):
     sys.path.insert(0, root)
     import bench
     assert bench.driver_line(full, d['details_file']) == lines[0]
+
+
+def test_plain_bench_prints_the_headline_and_dumps_the_last_steps_logits(dev, tmp_path):
+    """`python bench.py` without --full: one timed region of exactly --steps steps, the contract keys only (no roofline,
+    parity, CPU baseline or side file), and --dump-outputs writes the logits of the last timed step, which agree with
+    the CPU oracle on the bench's seeded C2 batch."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / 'outputs'
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2',
+                        '--dump-outputs', str(dump)],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'n_gpus', 'steps', 'warmup'):
+        assert key in d, key
+    assert d['steps'] == 7 and d['warmup'] == 2 and len(d['regions_ms']) == 1 and d['details_file'] is None
+    assert d['dtype'] == 'f32 (bf16x3 exact operand split, f32 accumulate)' and d['unit'] == 'agent-steps/s'
+    assert abs(d['value'] - 5120 / (d['ms_per_step'] * 1e-3)) <= 1e-3 * d['value']
+    assert abs(d['ms_per_step'] * 7 - d['regions_ms'][0]) <= 1e-3 * d['regions_ms'][0]
+    for key in ('roofline', 'parity', 'cpu_baseline', 'summary', 'pipelined'):
+        assert key not in d, key
+    got = np.load(str(dump / 'logits.npy'))
+    assert got.dtype == np.float32 and got.shape == (10, 512, 5)
+    sd = orc.init_state_dict(3, seed=1337)
+    obs = orc.synth_obs(512, 10, seed=1337)
+    S = torch.from_numpy(orc.synth_gso_geometric(512, 10, 20, seed=1337)).float()
+    with torch.no_grad():
+        want = torch.stack(orc.policy_forward(sd, S, obs)).numpy()
+    assert np.abs(got - want).max() <= TOL

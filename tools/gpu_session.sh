@@ -19,9 +19,9 @@ if has test; then stamp "pytest -m gpu"
 if has smoke; then stamp smoke
   timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee $OUT/smoke.log; fi
 if has bench; then stamp "bench c2"
-  timeout 400 python bench.py --steps 200 --warmup 20 --details-file $OUT/bench_c2_full.json 2>&1 | tail -1 | tee $OUT/bench_c2.json; fi
+  timeout 400 python bench.py --full --steps 200 --warmup 20 --details-file $OUT/bench_c2_full.json 2>&1 | tail -1 | tee $OUT/bench_c2.json; fi
 if has benchdrv; then stamp "bench c2 with the driver's flags"
-  timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --details-file $OUT/bench_c2_driverflags_full.json 2>&1 | tail -1 | tee $OUT/bench_c2_driverflags.json; fi
+  timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --details-file $OUT/bench_c2_driverflags_full.json 2>&1 | tail -1 | tee $OUT/bench_c2_driverflags.json; fi
 if has train; then stamp "train bench"
   timeout 300 python tools/train_bench.py --steps 50 2>&1 | tail -1 | tee $OUT/train_bench.json
   timeout 300 python tools/train_bench.py --steps 50 --graph 2>&1 | tail -3 | tee $OUT/train_bench_graph.json
@@ -55,20 +55,20 @@ if has trainops; then stamp "which op launches the stray fill / copy kernels of 
 if has trainprof; then stamp "host profile of the eager training step"
   timeout 300 python tools/train_host_profile.py 2>&1 | grep -v amdgpu.ids | head -60 | tee $OUT/train_host_profile.txt; fi
 if has distcheck; then stamp "launcher-less bench.py --gpus 2 (bench.py starts its two ranks itself; gloo, both ranks on GPU 0)"
-  GNNPP_BENCH_DEVICE=0 timeout 300 python bench.py --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --pmc off --dist-backend gloo --details-file $OUT/bench_selflaunch_full.json 2>&1 | tail -1 | cut -c1-700 | tee $OUT/distcheck.log
+  GNNPP_BENCH_DEVICE=0 timeout 300 python bench.py --full --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --pmc off --dist-backend gloo --details-file $OUT/bench_selflaunch_full.json 2>&1 | tail -1 | cut -c1-700 | tee $OUT/distcheck.log
   stamp "... and without the device override: refused (one GPU here)"
   timeout 120 python bench.py --gpus 2 --steps 5 --warmup 1 --no-cpu-baseline --no-secondary --pmc off 2>&1 | tail -1 | cut -c1-300 | tee -a $OUT/distcheck.log
   stamp "2-rank gloo run of bench.py on one GPU under torch.distributed.run (code-path check only)"
-  GNNPP_BENCH_DEVICE=0 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --dist-backend gloo 2>&1 | tail -2 | cut -c1-600 | tee -a $OUT/distcheck.log
+  GNNPP_BENCH_DEVICE=0 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --dist-backend gloo 2>&1 | tail -2 | cut -c1-600 | tee -a $OUT/distcheck.log
   stamp "2 ranks over RCCL on ONE GPU: GraphedTrainStep(dp=FlatBucketDP) -- the captured all-reduce must execute"
   GNNPP_BENCH_DEVICE=0 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 tools/train_bench.py --steps 20 --graph > $OUT/rccl_one_gpu.log 2>&1; echo "exit $?" >> $OUT/rccl_one_gpu.log
   grep -i "error\|duplicate\|invalid\|agent-steps\|^exit" $OUT/rccl_one_gpu.log | grep -v amdgpu.ids | head -12 | cut -c1-400 | tee -a $OUT/distcheck.log
   stamp "1-rank torchrun nccl"
-  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-300 | tee -a $OUT/distcheck.log; fi
+  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-300 | tee -a $OUT/distcheck.log; fi
 if has distbench; then stamp "2-rank gloo run of bench.py on one GPU, full secondary block (rank-0-only records must not start collectives)"
-  GNNPP_BENCH_DEVICE=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29536 bench.py --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --dist-backend gloo 2>&1 | tail -2 | cut -c1-700 | tee $OUT/distbench.log
+  GNNPP_BENCH_DEVICE=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29536 bench.py --full --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --dist-backend gloo 2>&1 | tail -2 | cut -c1-700 | tee $OUT/distbench.log
   stamp "the same with --scaling strong --config c5"
-  GNNPP_BENCH_DEVICE=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29537 bench.py --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --dist-backend gloo --scaling strong --config c5 2>&1 | tail -1 | cut -c1-700 | tee -a $OUT/distbench.log; fi
+  GNNPP_BENCH_DEVICE=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29537 bench.py --full --gpus 2 --steps 20 --warmup 3 --no-cpu-baseline --dist-backend gloo --scaling strong --config c5 2>&1 | tail -1 | cut -c1-700 | tee -a $OUT/distbench.log; fi
 if has cpab; then stamp "column-packed policy kernel A/B (+ phase stamps)"
   timeout 400 python tools/cp_ab.py stamps 2>&1 | grep -v "amdgpu.ids\|warning\|note:" | tee $OUT/cp_ab.jsonl; fi
 if has cptiles; then stamp "column-packed encoder tiles (latency regime) A/B + stamps"
@@ -82,15 +82,15 @@ if has filtersweep; then stamp "filter-only throughput sweep"
 if has stamps; then stamp "phase stamps of the rollout kernels"
   timeout 300 python tools/phase_stamps.py 2>&1 | grep -v "amdgpu.ids\|warning\|note:" | tail -14 | tee $OUT/phase_stamps.jsonl; fi
 if has bench35; then for c in c3 c5; do stamp "bench $c"
-  timeout 400 python bench.py --config $c --steps 100 --warmup 10 --cpu-seconds 4 --details-file $OUT/bench_${c}_full.json 2>&1 | tail -1 | tee $OUT/bench_$c.json; done; fi
+  timeout 400 python bench.py --full --config $c --steps 100 --warmup 10 --cpu-seconds 4 --details-file $OUT/bench_${c}_full.json 2>&1 | tail -1 | tee $OUT/bench_$c.json; done; fi
 cd /tmp && export TMPDIR=/tmp
 if has prof; then stamp "rocprofv3 kernel trace"
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-secondary --pipeline-streams 0 --pmc off > $OUT/prof_run.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python $R/bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-secondary --pipeline-streams 0 --pmc off > $OUT/prof_run.log 2>&1
   f=$(find $OUT/prof -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && head -12 "$f" | tee $OUT/kernel_stats_head.csv
   find $OUT/prof -name "*kernel_trace.csv" -size +6M -delete; fi
 if has prof35; then for c in c3 c5; do stamp "rocprofv3 kernel trace $c"
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$c -o trace -- python $R/bench.py --config $c --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --pipeline-streams 0 --pmc off > $OUT/prof_run_$c.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$c -o trace -- python $R/bench.py --full --config $c --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --pipeline-streams 0 --pmc off > $OUT/prof_run_$c.log 2>&1
   f=$(find $OUT/prof_$c -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && head -8 "$f" | tee $OUT/kernel_stats_head_$c.csv
   find $OUT/prof_$c -name "*kernel_trace.csv" -size +6M -delete; done; fi
