@@ -19,8 +19,8 @@
 //                             columns = (image, position), contraction = (tap, input channel); images
 //                             zero-bordered in LDS, A fragments from the pack; the 2x2 layers run as DENSE
 //                             maps of the flattened image (no multiplications spent on the border); per-workgroup
-//                             partial (sum, sum of squares) per channel for the BatchNorm statistics
-//     bn_relu_pool_kernel     partials -> mean, 1/sqrt(var + eps) per (agent, channel) (+ unbiased variance for
+//                             (mean, sum of squared deviations) per channel for the BatchNorm statistics
+//     bn_relu_pool_kernel     partials -> (Chan's merge) mean, 1/sqrt(var + eps) per (agent, channel) (+ unbiased variance for
 //                             the running statistics) in the workgroup's prologue, then
 //                             x_{l+1} = maxpool2x2?( relu( (y - mean) * invstd * gamma + beta ) )
 //   then bn_running_kernel    the N sequential momentum updates of every layer's running statistics
@@ -180,9 +180,9 @@ inline TrainPackLayout train_pack_layout() {
 // so the operand of any (tap, c) is the lane's column offset plus a compile-time constant: the inner loop is
 // ds_read (immediate offsets) + MFMA and nothing else.  Lane (i = lane & 15, q = lane >> 4): A value (row i,
 // k = 4s + q), B value (k = 4s + q, column i);  D register r: (row 4q + r, column i).
-// Epilogue: + bias, store, and (part != nullptr) the BatchNorm partial sums of the workgroup's channels over
-// its valid columns -> part[((n*chunks + chunk)*C + c)*2 + {sum, sum of squares}] (16-lane butterflies, then
-// the four waves in order: deterministic).
+// Epilogue: + bias, store, and (part != nullptr) the BatchNorm moments of the workgroup's channels over its
+// nimg * P * RPC valid values -> part[((n*chunks + chunk)*C + c)*2 + {mean, sum of squared deviations from it}]
+// (16-lane butterflies, then the four waves in order: deterministic).
 template <int H, int W>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(const float* __restrict__ x, const float* __restrict__ wp,
                                                         const float* __restrict__ bias, float* __restrict__ y,
@@ -316,50 +316,67 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const float* __restrict_
 
     // ---- epilogue
     const int C = M / RPC;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    float bv[4], s1[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int m = m0 + 4 * q + r;
-        const float bv = bias ? bias[m / RPC] : 0.f;
+        bv[r] = bias ? bias[m / RPC] : 0.f;
 #pragma unroll
         for (int t = 0; t < TN; ++t) {
-            const float v = acc[t][r] + bv;
+            const float v = acc[t][r] + bv[r];
             if (cv[t]) {
                 y[(((long)n * B + b0 + cimg[t]) * M + m) * P + cp[t]] = v;
-                s1[RPC == 1 ? r : 0] += v;
-                s2[RPC == 1 ? r : 0] += v * v;
+                s1[RPC == 1 ? r : 0] += acc[t][r];
             }
         }
     }
     if (part) {
+        // Two passes over the registers: the workgroup's mean per channel, then the sum of squared deviations from it
+        // (not the sum of squares: s2 / m - mean^2 cancels catastrophically when a channel's mean is large against
+        // its spread).  bn_relu_pool_kernel merges the (mean, M2) pairs of the chunks with Chan's formula.  Both
+        // passes run on the accumulators, i.e. shifted by the channel's bias (exact for a constant channel: zero
+        // weights give mean = bias and M2 = 0); the data's own offset is left to the second pass.
         constexpr int NS = RPC == 1 ? 4 : 1;                     // channel slots per lane
         __syncthreads();                                         // the A fragments are dead: reuse their LDS
-        float* red = wsm;                                        // [4 waves][16 / RPC channels][2]
+        float* red = wsm;                                        // wave sums [4][16] at 0 and 64, means [16] at 128
+        auto wg_sum = [&](const float (&s)[4], int base) {       // -> red[base + w * 16 + slot] of every wave
 #pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            float a1 = s1[k], a2 = s2[k];
+            for (int k = 0; k < NS; ++k) {
+                float a = s[k];
 #pragma unroll
-            for (int msk = 1; msk < 16; msk <<= 1) {
-                a1 += __shfl_xor(a1, msk);
-                a2 += __shfl_xor(a2, msk);
+                for (int msk = 1; msk < 16; msk <<= 1) a += __shfl_xor(a, msk);
+                if (i16 == 0) red[base + wave * 16 + (RPC == 1 ? 4 * q + k : q)] = a;
             }
-            if (i16 == 0) {
-                const int slot = RPC == 1 ? 4 * q + k : q;
-                red[(wave * 16 + slot) * 2] = a1;
-                red[(wave * 16 + slot) * 2 + 1] = a2;
+        };
+        auto waves = [&](int base) { return red[base + tid] + red[base + 16 + tid] + red[base + 32 + tid] + red[base + 48 + tid]; };
+        const float cnt = (float)(nimg * P * RPC);               // values of one channel in this workgroup
+        wg_sum(s1, 0);
+        __syncthreads();
+        if (tid < 16 / RPC) red[128 + tid] = waves(0) / cnt;
+        __syncthreads();
+        // second pass: sum of d and of d^2, d = acc - mu (the corrected two-pass form: the sum of d, ~0, removes the
+        // roundoff of mu from both moments)
+        float s2[4] = {0.f, 0.f, 0.f, 0.f}, sd[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float mu = red[128 + (RPC == 1 ? 4 * q + r : q)];       // (of the accumulators)
+#pragma unroll
+            for (int t = 0; t < TN; ++t) {
+                const float d = acc[t][r] - mu;
+                if (cv[t]) {
+                    sd[RPC == 1 ? r : 0] += d;
+                    s2[RPC == 1 ? r : 0] = fmaf(d, d, s2[RPC == 1 ? r : 0]);
+                }
             }
         }
+        wg_sum(sd, 0);
+        wg_sum(s2, 64);
         __syncthreads();
         if (tid < 16 / RPC) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                t1 += red[(w * 16 + tid) * 2];
-                t2 += red[(w * 16 + tid) * 2 + 1];
-            }
+            const float dsum = waves(0), dmean = dsum / cnt;
             float* o = part + (((long)n * chunks + chunk) * C + m0 / RPC + tid) * 2;
-            o[0] = t1;
-            o[1] = t2;
+            o[0] = (bias ? bias[m0 / RPC + tid] : 0.f) + (red[128 + tid] + dmean);
+            o[1] = fmaxf(waves(64) - dsum * dmean, 0.f);
         }
     }
 }
@@ -393,10 +410,46 @@ __device__ __forceinline__ void reduce_partials(const float* __restrict__ part, 
     }
 }
 
+// The same for the forward's (mean, M2) pairs of conv_mfma_kernel (chunk k holds the cnt_k = min(IB, B - k IB) * P
+// values of images [k IB, k IB + IB)), merged in double with Chan's formula:
+//   n = na + nb,  d = mb - ma,  mean = ma + d nb / n,  M2 = M2a + M2b + d^2 na nb / n
+// in the same fixed association as reduce_partials (deterministic).  red: LDS, 768 doubles.  Result of channel cc:
+// red[(cc * (256 / CG)) * 3 + {0: count, 1: mean, 2: M2}].
+__device__ __forceinline__ void chan_merge(double& na, double& ma, double& qa, double nb, double mb, double qb) {
+    const double n = na + nb, d = mb - ma;
+    ma += d * (nb / n);
+    qa += qb + d * d * (na * nb / n);
+    na = n;
+}
+__device__ __forceinline__ void reduce_moments(const float* __restrict__ part, int n, int chunks, int C, int c0,
+                                               int CG, int B, int IB, int P, double* red) {
+    const int tpc = 256 / CG;
+    const int cc = threadIdx.x / tpc, r = threadIdx.x - cc * tpc;
+    double cn = 0.0, mu = 0.0, m2 = 0.0;
+    for (int k = r; k < chunks; k += tpc) {
+        const float* p = part + (((long)n * chunks + k) * C + c0 + cc) * 2;
+        chan_merge(cn, mu, m2, (double)(min(IB, B - k * IB) * P), (double)p[0], (double)p[1]);
+    }
+    double* o = red + threadIdx.x * 3;
+    o[0] = cn; o[1] = mu; o[2] = m2;
+    __syncthreads();
+    for (int off = tpc >> 1; off > 0; off >>= 1) {
+        if (r < off) {
+            const double* b = red + (threadIdx.x + off) * 3;
+            if (b[0] > 0.0) {                               // (threads past the last chunk hold nothing)
+                chan_merge(cn, mu, m2, b[0], b[1], b[2]);
+                o[0] = cn; o[1] = mu; o[2] = m2;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // Workgroup shape of the two BatchNorm element-wise kernels: (channels per workgroup, images per workgroup)
 // chosen so that a workgroup's slice of one image is a contiguous run of >= 64 floats and a layer has a
 // few hundred workgroups.
-constexpr size_t kBnSmem = 512 * sizeof(double) + 32 * 5 * sizeof(float);
+constexpr int kBnRed = 768;                                 // doubles of reduce_moments / reduce_partials
+constexpr size_t kBnSmem = kBnRed * sizeof(double) + 32 * 5 * sizeof(float);
 struct BnTile { int CG, BR; };
 __host__ __device__ inline BnTile bn_tile(int l) {
     const BnTile t[kTrainLayers] = {{2, 8}, {8, 8}, {8, 8}, {32, 16}, {32, 16}};
@@ -446,11 +499,11 @@ __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restri
                                                            const float* __restrict__ gamma,
                                                            const float* __restrict__ beta,
                                                            float* __restrict__ xn, int B, int C, int H, int W,
-                                                           int pool, int chunks, int CG, int BR, float eps,
+                                                           int pool, int chunks, int IB, int CG, int BR, float eps,
                                                            int out_bn, const BnRunningFuse rf) {
     extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
-    double* red = reinterpret_cast<double*>(gnnpp_smem);                               // [512]
-    float (*sm)[5] = reinterpret_cast<float (*)[5]>(gnnpp_smem + 512 * sizeof(double));  // mean, invstd, gamma, beta
+    double* red = reinterpret_cast<double*>(gnnpp_smem);                                  // [kBnRed]
+    float (*sm)[5] = reinterpret_cast<float (*)[5]>(gnnpp_smem + kBnRed * sizeof(double));  // mean, invstd, gamma, beta
     const int N = rf.mode == 2 ? rf.N : (int)gridDim.z;
     if (rf.mode == 1 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 8)
         rf.tick[threadIdx.x] = 0u;                               // (a later launch of this stream takes the tickets)
@@ -466,14 +519,11 @@ __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restri
     }
     const int n = blockIdx.z, c0 = blockIdx.x * CG, b0 = blockIdx.y * BR;
     const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W, Po = Ho * Wo, P = H * W;
-    reduce_partials(part, n, chunks, C, c0, CG, red);
+    reduce_moments(part, n, chunks, C, c0, CG, B, IB, P, red);
     if ((int)threadIdx.x < CG) {
         const int cc = threadIdx.x, c = c0 + cc;
         const int m = B * P;
-        const double s1 = red[cc * (256 / CG) * 2], s2 = red[cc * (256 / CG) * 2 + 1];
-        const double mean = s1 / m;
-        double var = s2 / m - mean * mean;
-        if (var < 0.0) var = 0.0;
+        const double mean = red[cc * (256 / CG) * 3 + 1], var = red[cc * (256 / CG) * 3 + 2] / m;   // (M2 >= 0)
         const float invstd = (float)(1.0 / sqrt(var + (double)eps));
         sm[cc][0] = (float)mean;
         sm[cc][1] = invstd;
@@ -627,8 +677,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            float* __restrict__ dz, float* __restrict__ pn, int B,
                                                            int C, int P, int chunks, int CG, int BR) {
     extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
-    double* red = reinterpret_cast<double*>(gnnpp_smem);                               // [512]
-    float (*sm)[5] = reinterpret_cast<float (*)[5]>(gnnpp_smem + 512 * sizeof(double));  // mean, invstd, k1, k2, k3
+    double* red = reinterpret_cast<double*>(gnnpp_smem);                                  // [512]
+    float (*sm)[5] = reinterpret_cast<float (*)[5]>(gnnpp_smem + kBnRed * sizeof(double));  // mean, invstd, k1, k2, k3
     const int n = blockIdx.z, c0 = blockIdx.x * CG, b0 = blockIdx.y * BR;
     reduce_partials(part, n, chunks, C, c0, CG, red);
     if ((int)threadIdx.x < CG) {
@@ -1123,7 +1173,7 @@ int train_encoder_fwd(const EncRawParams& rp, float* const* rmean, float* const*
         hipLaunchKernelGGL(bn_relu_pool_kernel, dim3(d.Cout / t.CG, (B + t.BR - 1) / t.BR, N + (f.mode == 2 ? 1 : 0)),
                            dim3(256), kBnSmem, st, ws + L.y[l], ws + L.part, ws + L.stat[l], rp.bn_w[l], rp.bn_b[l],
                            last ? feat : ws + L.xn[l], B, d.Cout, d.H, d.W, d.pool,
-                           conv_chunks(l, B), t.CG, t.BR, rp.bn_eps, (last && feat_bn) ? 1 : 0, f);
+                           conv_chunks(l, B), conv_geom(l, false, B).IB, t.CG, t.BR, rp.bn_eps, (last && feat_bn) ? 1 : 0, f);
     }
     if (have_running && !fuse_running) {
         TrainCounters nb = {};

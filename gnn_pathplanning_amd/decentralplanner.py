@@ -385,6 +385,9 @@ class DecentralPlannerNet(nn.Module):
                 for nm in ('running_mean', 'running_var'):
                     t.append(bn._buffers[nm])
                     slots.append((bn._buffers, nm, t[-1]))
+            if any(x is None for x in t):
+                raise _native.GnnppError('eval mode without BatchNorm running statistics (track_running_stats=False) '
+                                         'is not implemented')
             fc = self.compressMLP[0]
             slots.append((self.compressMLP._modules, '0', fc))
             for nm in ('weight', 'bias'):
@@ -444,7 +447,36 @@ class DecentralPlannerNet(nn.Module):
                 self._range_flag.zero_()
             raise _native.GnnppError(_native.lib().gnnpp_error_string(-4).decode())
 
+    def _bn_settings(self, training):
+        """(eps, momentum, track) of the five BatchNorm2d layers, which the kernels take as ONE value each: a setting
+        they do not compute raises GnnppError instead of silently differing from torch -- per-layer eps or momentum,
+        momentum=None (torch's cumulative moving average), track_running_stats off in some layers only, and eval mode
+        without running statistics (torch normalises with the batch's own statistics there)."""
+        mods = self.ConvLayers._modules
+        bns = [mods[str(bi)] for bi in _BN_IDX]
+        eps = bns[0].eps
+        if any(bn.eps != eps for bn in bns):
+            raise _native.GnnppError('the BatchNorm2d layers have different eps (%s): the encoder kernels take one'
+                                     % ', '.join(str(bn.eps) for bn in bns))
+        tracks = {bool(bn.track_running_stats and bn.running_mean is not None and bn.running_var is not None)
+                  for bn in bns}
+        if len(tracks) > 1:
+            raise _native.GnnppError('running statistics are tracked by some BatchNorm2d layers only')
+        track = tracks.pop()
+        if not training:
+            if not track:
+                raise _native.GnnppError('eval mode without BatchNorm running statistics is not implemented')
+            return eps, None, track
+        momentum = bns[0].momentum
+        if track and momentum is None:
+            raise _native.GnnppError('BatchNorm2d(momentum=None) (cumulative moving average) is not implemented')
+        if track and any(bn.momentum != momentum for bn in bns):
+            raise _native.GnnppError('the BatchNorm2d layers have different momentum (%s): the encoder kernels take one'
+                                     % ', '.join(str(bn.momentum) for bn in bns))
+        return eps, momentum, track
+
     def _pack_encoder(self):
+        eps = self._bn_settings(False)[0]
         L = _native.lib()
         ts = [x.detach().contiguous().float() for x in self._encoder_tensors()]
         dev = _native.require_gpu(*ts)
@@ -455,7 +487,7 @@ class DecentralPlannerNet(nn.Module):
             p.bn_w[i], p.bn_b[i] = bw.data_ptr(), bb.data_ptr()
             p.bn_mean[i], p.bn_var[i] = bm.data_ptr(), bv.data_ptr()
         p.fc_w, p.fc_b = ts[30].data_ptr(), ts[31].data_ptr()
-        p.bn_eps = float(self.ConvLayers[_BN_IDX[0]].eps)
+        p.bn_eps = float(eps)
         packed = torch.empty(L.gnnpp_encoder_packed_floats(), dtype=torch.float32, device=dev)
         with _native.device_guard(dev):
             _native.check(L.gnnpp_encoder_pack(ctypes.byref(p), _ptr(packed),
@@ -654,17 +686,15 @@ class DecentralPlannerNet(nn.Module):
             obs = obs[:, :N]
         obs = obs.contiguous().float()
         tensors, buffers = [], []
-        bn0 = self.ConvLayers[_BN_IDX[0]]
-        track = all(self.ConvLayers[bi].track_running_stats and self.ConvLayers[bi].momentum is not None
-                    for bi in _BN_IDX)
+        eps, momentum, track = self._bn_settings(True)
         for ci, bi in zip(_CONV_IDX, _BN_IDX):
             conv, bn = self.ConvLayers[ci], self.ConvLayers[bi]
             tensors += [conv.weight, conv.bias, bn.weight, bn.bias]
             buffers += [bn.running_mean, bn.running_var]
         counters = [self.ConvLayers[bi].num_batches_tracked for bi in _BN_IDX] if track else None   # += N each
         packs = self._train_packs(tensors)                                              # one launch per weight version
-        feat = _EncoderTrainFunction.apply(obs, buffers if track else None, counters, float(bn0.momentum or 0.0),
-                                           float(bn0.eps), packs[0] if packs else None, *tensors)   # [B,N,128]
+        feat = _EncoderTrainFunction.apply(obs, buffers if track else None, counters, float(momentum or 0.0),
+                                           float(eps), packs[0] if packs else None, *tensors)   # [B,N,128]
         fc = self.compressMLP[0]
         if self.S.shape[0] != B:
             raise _native.GnnppError('addGSO() was given %d graphs, the input has %d samples' % (self.S.shape[0], B))

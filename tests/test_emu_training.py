@@ -122,10 +122,13 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
     if fbn:                                                  # feat_sample_major: the same rows as [B,N,128]
         feat = np.ascontiguousarray(feat.reshape(B, N, 128).transpose(1, 0, 2))
     assert np.abs(feat - want_feat.numpy()).max() <= 2e-5 * max(1.0, want_feat.abs().max().item())
+    _, _, run64 = reference_at(sd, obs, cot, torch.float64)
     for i in range(5):                                       # N sequential running-statistics updates
         for nm in ('running_mean', 'running_var'):
             key = 'ConvLayers.%d.%s' % (BN[i], nm)
             assert np.abs(arrs[key] - run_ref[key].numpy()).max() <= 1e-5, key
+            ok, rep = f64_gap(arrs[key], run64[key], run_ref[key])    # and at fp32 level against float64
+            assert ok, (key, rep)
 
     G = Grads()
     outs = {}
@@ -353,3 +356,139 @@ def test_emu_train_pack_filter_taps_and_masked_input_gradient():
                                         el.ptr(dx), B, N, G, F, K, E, 0, 1, 1, None)
         assert rc == 0
         np.testing.assert_array_equal(dx, ref if m is None else np.where(m > 0, ref, 0))
+
+
+# ---- float64 yardstick ---------------------------------------------------------------------------------------------
+# The train-mode kernels are exact fp32 (fp32 MFMA, fmaf, fixed reduction order), so against a float64 statement of the
+# same step their error must be of the size of any other fp32 implementation's.  The yardstick is torch's own fp32 CPU
+# result of the same statement: per tensor, the RMS error may be at most F64_RMS x the fp32 RMS error and the largest
+# error F64_MAX x the fp32 largest error, each + ULPS units in the last place of the tensor's scale.  Two fp32
+# implementations with different summation orders make independent roundoff of the same size: their RMS errors
+# differ by well under 2x and their maxima (the tail of a few hundred samples) by under 4x; the factors allow 2x on
+# top.  A kernel error of one part in 1e4 of a tensor's scale (a biased/unbiased variance factor at m = 64 * 121, a
+# lost weight-gradient split) is 100x beyond that.
+F64_RMS, F64_MAX, ULPS = 4.0, 8.0, 8.0
+ULP = 2.0 ** -24
+
+
+def f64_gap(got, want64, ref32, scale=None):
+    """(ok, report): got (kernel) and ref32 (torch fp32 CPU) against the float64 value want64."""
+    want = np.asarray(want64, np.float64)
+    e = np.asarray(got, np.float64) - want
+    e32 = np.asarray(ref32, np.float64) - want
+    scale = float(np.abs(want).max()) if scale is None else scale
+    floor = ULPS * ULP * scale
+    rms, rms32 = float(np.sqrt(np.mean(e * e))), float(np.sqrt(np.mean(e32 * e32)))
+    mx, mx32 = float(np.abs(e).max()), float(np.abs(e32).max())
+    ok = bool(np.isfinite(e).all()) and rms <= F64_RMS * rms32 + floor and mx <= F64_MAX * mx32 + floor
+    return ok, dict(rms=rms, rms32=rms32, max=mx, max32=mx32, scale=scale)
+
+
+def reference_at(sd, obs, cot, dtype):
+    """reference() with every tensor in `dtype`: float64 is the exact statement, float32 the yardstick."""
+    sd = {k: (v.to(dtype) if v.dtype.is_floating_point else v.clone()) for k, v in sd.items()}
+    return reference(sd, obs.to(dtype), cot.to(dtype))
+
+
+def run_emu_encoder(lib, sd, obs, cot):
+    """gnnpp_encoder_train_fwd + _bwd (one call each, default knobs) -> feat [N,B,128], running statistics,
+    num_batches_tracked increments, parameter gradients."""
+    import emu_lib as el
+    lib.gnnpp_encoder_train_workspace_floats.restype = ctypes.c_size_t
+    B, N = obs.shape[0], obs.shape[1]
+    P, arrs = el.EncParams(), {}
+    for i in range(5):
+        for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
+                           ('bn_w', 'ConvLayers.%d.weight' % BN[i]), ('bn_b', 'ConvLayers.%d.bias' % BN[i]),
+                           ('bn_mean', 'ConvLayers.%d.running_mean' % BN[i]),
+                           ('bn_var', 'ConvLayers.%d.running_var' % BN[i])):
+            arrs[key] = el.f32(sd[key].numpy().copy())
+            getattr(P, field)[i] = arrs[key].ctypes.data
+    P.bn_eps = 1e-5
+    ws = np.zeros(lib.gnnpp_encoder_train_workspace_floats(N, B), np.float32)
+    feat = np.full((N, B, 128), np.nan, np.float32)
+    obs_np = el.f32(obs.numpy())
+    nbt = [np.zeros(1, np.int64) for _ in range(5)]
+    assert lib.gnnpp_encoder_train_fwd(ctypes.byref(P), el.ptr(obs_np), el.ptr(ws), el.ptr(feat), B, N,
+                                       ctypes.c_float(0.1), 1, (ctypes.c_void_p * 5)(*[a.ctypes.data for a in nbt]),
+                                       0, None, None) == 0
+    G, grads = Grads(), {}
+    for i in range(5):
+        for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
+                           ('bn_w', 'ConvLayers.%d.weight' % BN[i]), ('bn_b', 'ConvLayers.%d.bias' % BN[i])):
+            grads[key] = np.full(tuple(sd[key].shape), np.nan, np.float32)
+            getattr(G, field)[i] = grads[key].ctypes.data
+    cot_np = el.f32(cot.numpy())
+    assert lib.gnnpp_encoder_train_bwd(ctypes.byref(P), el.ptr(obs_np), el.ptr(ws), el.ptr(cot_np), ctypes.byref(G),
+                                       B, N, 0, None, None) == 0
+    running = {k: a for k, a in arrs.items() if 'running' in k}
+    return feat, running, [int(a[0]) for a in nbt], grads
+
+
+def _edge_state(kind, seed):
+    """Parameters (seed-`seed` init) with one value edge applied."""
+    from oracle import policy_oracle as orc
+    sd = orc.init_state_dict(3, seed=seed)
+    if kind.startswith('bias0+'):                   # a pre-BN offset of layer 0: cancels exactly in train-mode BN
+        sd['ConvLayers.0.bias'] += float(kind[6:])
+    elif kind.startswith('bias2+'):                 # ... of the third convolution (5x5, 32 -> 64)
+        sd['ConvLayers.7.bias'] += float(kind[6:])
+    elif kind.startswith('bias3+'):                 # ... of the first dense 2x2 layer (64 -> 64)
+        sd['ConvLayers.11.bias'] += float(kind[6:])
+    elif kind == 'zero_var':                        # one output channel of zero variance: output = beta, d gamma = 0
+        for li, c in ((0, 5), (1, 3), (3, 7)):
+            sd['ConvLayers.%d.weight' % CONV[li]][c] = 0.0
+            sd['ConvLayers.%d.bias' % BN[li]][c] = 0.25
+    elif kind == 'gamma':                           # gamma = 0 and negative gamma, a channel dead after ReLU
+        for li in range(5):
+            w = sd['ConvLayers.%d.weight' % BN[li]]
+            w[0] = 0.0
+            w[1::3] *= -1.0
+            sd['ConvLayers.%d.bias' % BN[li]][2] = -10.0
+    elif kind.startswith('beta+'):                  # BN shifts of layers 1 .. 3: offsets of the next layer's input
+        for li in (1, 2, 3):
+            sd['ConvLayers.%d.bias' % BN[li]] += float(kind[5:])
+    return sd
+
+
+@pytest.mark.parametrize('kind,B,N', [('plain', 8, 2), ('bias0+10', 8, 2), ('bias0+100', 5, 2), ('bias0+1000', 8, 2),
+                                      ('bias2+100', 3, 3), ('bias3+100', 8, 1), ('zero_var', 4, 2), ('gamma', 3, 2),
+                                      ('beta+30', 8, 2)])
+def test_emu_train_encoder_against_float64(kind, B, N):
+    """The train-mode encoder (forward + backward, running statistics) against a float64 statement of the same step,
+    held to the fp32 yardstick (f64_gap) at the value edges where one-pass BatchNorm statistics go wrong: a conv bias
+    shift in front of train-mode BatchNorm cancels exactly, so the features may not move by more than fp32 roundoff;
+    a channel of zero variance must come out as beta with a zero gamma gradient."""
+    import emu_lib as el
+    lib = el.load()
+    sd = _edge_state(kind, 5)
+    g = torch.Generator().manual_seed(B * 10 + N)
+    obs = (torch.rand(B, N, 3, 11, 11, generator=g) < 0.25).float() + 0.1 * torch.randn(B, N, 3, 11, 11, generator=g)
+    cot = torch.randn(N, B, 128, generator=g)
+    f64, p64, r64 = reference_at(sd, obs, cot, torch.float64)
+    f32, p32, r32 = reference_at(sd, obs, cot, torch.float32)
+    feat, running, nbt, grads = run_emu_encoder(lib, sd, obs, cot)
+    assert nbt == [N] * 5
+    bad = []
+    ok, rep = f64_gap(feat, f64, f32)
+    if not ok:
+        bad.append(('feat', rep))
+    for k in running:                                     # the N sequential momentum updates, unbiased variance
+        ok, rep = f64_gap(running[k], r64[k], r32[k])
+        if not ok:
+            bad.append((k, rep))
+    for k, o in grads.items():
+        want, ref = p64[k].grad.numpy(), p32[k].grad.numpy()
+        li = CONV.index(int(k.split('.')[1])) if int(k.split('.')[1]) in CONV else None
+        if li is not None and k.endswith('bias'):
+            # exactly zero in exact arithmetic: roundoff of a sum over B * P terms of the weight gradient's size
+            wscale = np.abs(p64['ConvLayers.%d.weight' % CONV[li]].grad.numpy()).max()
+            ok, rep = f64_gap(o, want, ref, scale=wscale * np.sqrt(B * 121))
+        else:
+            ok, rep = f64_gap(o, want, ref)
+        if not ok:
+            bad.append((k, rep))
+    if kind == 'zero_var':
+        for li, c in ((0, 5), (1, 3), (3, 7)):
+            assert grads['ConvLayers.%d.weight' % BN[li]][c] == 0.0
+    assert not bad, bad
