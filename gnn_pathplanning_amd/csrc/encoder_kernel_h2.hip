@@ -847,23 +847,37 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
             float* row = z0 + (rb + half) * kZs;
             const v4f v = *reinterpret_cast<const v4f*>(row + 4 * hl);
             __builtin_amdgcn_wave_barrier();             // all reads of a row precede its writes
-            range_note(max4abs(0.f, v), bad);
+            float mx = max4abs(0.f, v);
+            range_note(mx, bad);
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));     // the row's largest |z|
+            const float up = row_scale_up(mx);           // power-of-two row scale (gnnpp_common.h)
             v4h h, l;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                h[c] = (_Float16)v[c];
-                l[c] = (_Float16)(v[c] - (float)h[c]);
+                const float u = v[c] * up;
+                h[c] = (_Float16)u;
+                l[c] = (_Float16)(u - (float)h[c]);
             }
             *reinterpret_cast<v2f*>(row + 2 * hl) = __builtin_bit_cast(v2f, h);
             *reinterpret_cast<v2f*>(row + 64 + 2 * hl) = __builtin_bit_cast(v2f, l);
+            if (hl == 0) { row[kRowScaleCol] = up; row[kRowScaleCol + 1] = 1.f / up; }
         }
     }
     __syncthreads();
     // contraction on the f16 pipe: channel tiles 2w, 2w+1; same term order as lsigf_kernel
     v4f fa[2] = {vzero(), vzero()}, fc[2] = {vzero(), vzero()};
+    float rinv = 1.f;                                    // 2^-s of the row scale fa / fc are in
 #pragma unroll
     for (int tap = 0; tap < KT; ++tap) {
         const float* zr = z0 + (tap * 16 + a) * kZs + 4 * q;
+        {                                                // into this tap's row scale: exact
+            const float* sc = z0 + (tap * 16 + a) * kZs + kRowScaleCol;
+            const float r = sc[0] * rinv;
+#pragma unroll
+            for (int m = 0; m < 2; ++m) { fa[m] *= r; fc[m] *= r; }
+            rinv = sc[1];
+        }
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) {
             __builtin_amdgcn_sched_barrier(kSchedItemMask);
@@ -895,7 +909,7 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
     // way: identical logits).  Every constant comes from LDS (parked there before the ring started).
     float* const yb = z0 + KT * (16 * kZs);              // [4 waves][16 nodes][8]: partial logits
     {
-        const float finv = hconst[773];
+        const float finv = hconst[773] * rinv;
         v4f d = vzero();
 #pragma unroll
         for (int m = 0; m < 2; ++m) {

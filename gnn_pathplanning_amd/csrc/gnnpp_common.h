@@ -90,6 +90,26 @@ __device__ __forceinline__ v4f mfma16h(v8h a, v8h b, v4f c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
+// Split-f16 filter operand rows (lsigf_kernel's split_rows, policy_filter_kernel, the fused policy tail) carry a
+// power-of-two scale.  Unscaled, the lo half of a value far below 1 is an f16 subnormal (spacing 2^-24): every
+// product then has an absolute error of ~2^-25 |w| whatever the size of z -- a relative error of 1e-2 at |z| ~ 1e-6.
+// So each row is multiplied by 2^s (exact) with its largest |z| in [2^13, 2^14) before the split, s in
+// [0, kRowScaleMax]: the lo halves of the values within 2^16 of the row's largest stay normal and the split keeps
+// 22 bits of them.  Rows that are already large keep s = 0 (the range guard still flags |z| >= 65504).  The scale
+// pair {2^s, 2^-s} is parked in the row's pad columns (kRowScaleCol, + 1; the row stride is 128 + 8 floats); the
+// contraction rescales its accumulators by 2^(s_k - s_(k-1)) when tap k brings a new scale, and the epilogue
+// multiplies by 2^-s of the last tap.  All of these are powers of two: exact.
+// Bound: a scaled |z| < 65504 and taps scaled below 1024 make products below 2^26, so an accumulator (128 E K of
+// them, rescaled by at most 2^kRowScaleMax) stays below 2^(33 + kRowScaleMax) E K: far from the fp32 range.
+constexpr int kRowScaleMax = 64;
+constexpr int kRowScaleCol = 128;
+
+__device__ __forceinline__ float row_scale_up(float m) {        // 2^s for a row of largest |z| = m
+    int e = 14;
+    if (m > 0.f && m < 8192.f) (void)frexpf(m, &e);             // m in [2^(e-1), 2^e)
+    return ldexpf(1.f, min(max(14 - e, 0), kRowScaleMax));
+}
+
 // v_mfma_f32_16x16x32_bf16: same lane map and rate as the f16 form; bf16 has fp32's exponent range, so three
 // bf16 planes represent ANY finite fp32 value exactly (bf16x3, below).
 __device__ __forceinline__ v4f mfma16b(v8b a, v8b b, v4f c) {

@@ -193,8 +193,8 @@ __global__ void pack_filter_kernel(const float* __restrict__ h, float* __restric
 }
 
 // In-place fp32 -> split-f16 conversion of the valid rows of a z buffer (G = 128): a half-wave
-// owns a row, reads all of it (16 bytes per lane), then writes the hi halves to the first 256 bytes
-// of the row and the lo halves to the second 256 bytes.
+// owns a row, reads all of it (16 bytes per lane), scales it (row_scale_up), then writes the hi halves to the first
+// 256 bytes of the row, the lo halves to the second 256 bytes and {2^s, 2^-s} to the pad columns.
 __device__ __forceinline__ void split_rows(float* __restrict__ z, int row_lo, int row_hi, int zs,
                                            int wave, int nwaves, int lane, unsigned long long& bad) {
     typedef _Float16 v4h __attribute__((ext_vector_type(4)));
@@ -206,16 +206,22 @@ __device__ __forceinline__ void split_rows(float* __restrict__ z, int row_lo, in
         const v4f v = *reinterpret_cast<const v4f*>(row + 4 * hl);
         __builtin_amdgcn_wave_barrier();                 // all reads of a row precede its writes
         // range guard: |z| >= 65504 does not fit the hi half (rows >= row_hi are copies of valid rows)
-        bad |= __ballot(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) >= 65504.f);
+        float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+        bad |= __ballot(m >= 65504.f);
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));     // the row's largest |z| (half-wave)
+        const float up = row_scale_up(m);
         v4h h, l;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            h[c] = (_Float16)v[c];
-            l[c] = (_Float16)(v[c] - (float)h[c]);
+            const float u = v[c] * up;
+            h[c] = (_Float16)u;
+            l[c] = (_Float16)(u - (float)h[c]);
         }
         if (ok) {
             *reinterpret_cast<v2f*>(row + 2 * hl) = __builtin_bit_cast(v2f, h);
             *reinterpret_cast<v2f*>(row + 64 + 2 * hl) = __builtin_bit_cast(v2f, l);
+            if (hl == 0) { row[kRowScaleCol] = up; row[kRowScaleCol + 1] = 1.f / up; }
         }
     }
 }
@@ -503,10 +509,11 @@ __global__ __launch_bounds__(NW * 64) void lsigf_kernel(const LsigfArgs p) {
 
     unsigned long long bad = 0;                          // H2: lanes that handed |z| >= 65504 to the f16 pipe
     v4f acc[RTW], acc2[H2 ? RTW : 1];                    // H2: cross terms accumulate separately
+    float rinv[H2 ? RTW : 1];                            // H2: 2^-s of the row scale the accumulators are in
 #pragma unroll
     for (int t = 0; t < RTW; ++t) acc[t] = vzero();
 #pragma unroll
-    for (int t = 0; t < (H2 ? RTW : 1); ++t) acc2[t] = vzero();
+    for (int t = 0; t < (H2 ? RTW : 1); ++t) { acc2[t] = vzero(); rinv[t] = 1.f; }
 
     // B-fragment row of this lane for the wave's t-th row tile, clamped into the allocated rows
     auto brow = [&](int t) { return min((rt0 + t) * 16 + a, R - 1); };
@@ -553,6 +560,14 @@ __global__ __launch_bounds__(NW * 64) void lsigf_kernel(const LsigfArgs p) {
                 __syncthreads();
                 GNNPP_STAMP(blockIdx.x, 4 + 3 * k, tid == 0 && k < 3);      // z_k split
                 if (has_mfma && !GNNPP_ABLATE(p, 2)) {
+#pragma unroll
+                    for (int t = 0; t < RTW; ++t) {       // into tap k's row scale (split_rows): exact
+                        const float* sc = zcur + brow(t) * zs + kRowScaleCol;
+                        const float r = sc[0] * rinv[t];
+                        acc[t] *= r;
+                        acc2[t] *= r;
+                        rinv[t] = sc[1];
+                    }
 #pragma unroll
                     for (int kb = 0; kb < 4; ++kb) {
                         const v8h Ah = __builtin_bit_cast(v8h, Acur[2 * kb]);
@@ -657,7 +672,7 @@ __global__ __launch_bounds__(NW * 64) void lsigf_kernel(const LsigfArgs p) {
                     for (int r = 0; r < 4; ++r)
                         bv[r] = (f0 + r < p.F) ? p.bias[(size_t)(p.f0 + f0 + r) * N + n] : 0.f;
                 }
-                v4f v = H2 ? (acc[t] + acc2[t]) * h2_inv + bv : acc[t] + bv;
+                v4f v = H2 ? (acc[t] + acc2[t]) * (h2_inv * rinv[t]) + bv : acc[t] + bv;
                 if (p.relu) v = vrelu(v);
                 *reinterpret_cast<v4f*>(ybuf + row * zs + f0) = v;
             }

@@ -138,17 +138,22 @@ __device__ __forceinline__ void pf_gather(const float* __restrict__ Sl, const un
 #pragma unroll
             for (int c = 0; c < 4; ++c) mx = fmaxf(mx, fmaxf(fabsf(acc0[c]), fabsf(acc1[c])));
             bad |= __ballot(rv && mx >= 65504.f);
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));   // the row's largest |z| (quarter wave)
+            const float up = row_scale_up(mx);                                       // as split_rows
             v4h h0, l0, h1, l1;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                h0[c] = (_Float16)acc0[c]; l0[c] = (_Float16)(acc0[c] - (float)h0[c]);
-                h1[c] = (_Float16)acc1[c]; l1[c] = (_Float16)(acc1[c] - (float)h1[c]);
+                const float u0 = acc0[c] * up, u1 = acc1[c] * up;
+                h0[c] = (_Float16)u0; l0[c] = (_Float16)(u0 - (float)h0[c]);
+                h1[c] = (_Float16)u1; l1[c] = (_Float16)(u1 - (float)h1[c]);
             }
             if (rv) {
                 *reinterpret_cast<v2f*>(row + 2 * ql) = __builtin_bit_cast(v2f, h0);          // features 4 ql ..
                 *reinterpret_cast<v2f*>(row + 32 + 2 * ql) = __builtin_bit_cast(v2f, h1);     // features 64 + 4 ql ..
                 *reinterpret_cast<v2f*>(row + 64 + 2 * ql) = __builtin_bit_cast(v2f, l0);
                 *reinterpret_cast<v2f*>(row + 96 + 2 * ql) = __builtin_bit_cast(v2f, l1);
+                if (ql == 0) { row[kRowScaleCol] = up; row[kRowScaleCol + 1] = 1.f / up; }
             }
         }
     }
@@ -285,16 +290,22 @@ __global__ __launch_bounds__(1024) void policy_filter_kernel(const LsigfArgs p) 
         const v4f v = ok ? xv[u] : vzero();
         const int r = i >> 5, c4 = i & 31;
         if (MODE == 0) {
-            bad |= __ballot(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))) >= 65504.f);
+            float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+            bad |= __ballot(mx >= 65504.f);
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));  // row r = 32 consecutive threads
+            const float up = row_scale_up(mx);                                      // as split_rows
             v4h hh, ll;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                hh[c] = (_Float16)v[c];
-                ll[c] = (_Float16)(v[c] - (float)hh[c]);
+                const float uu = v[c] * up;
+                hh[c] = (_Float16)uu;
+                ll[c] = (_Float16)(uu - (float)hh[c]);
             }
             if (ok) {
                 *reinterpret_cast<v2f*>(zbuf1 + r * kPfZs + 2 * c4) = __builtin_bit_cast(v2f, hh);
                 *reinterpret_cast<v2f*>(zbuf1 + r * kPfZs + 64 + 2 * c4) = __builtin_bit_cast(v2f, ll);
+                if (c4 == 0) { zbuf1[r * kPfZs + kRowScaleCol] = up; zbuf1[r * kPfZs + kRowScaleCol + 1] = 1.f / up; }
             }
         }
         if (B3) {
@@ -354,14 +365,23 @@ __global__ __launch_bounds__(1024) void policy_filter_kernel(const LsigfArgs p) 
     GNNPP_STAMP(blockIdx.x, 1, tid == 0);
 
     v4f acc[RTW], acc2[RTW];                           // hi.hi products | cross terms (MODE 1: acc only)
+    float rinv[RTW];                                   // MODE 0: 2^-s of the row scale the accumulators are in
 #pragma unroll
-    for (int t = 0; t < RTW; ++t) { acc[t] = vzero(); acc2[t] = vzero(); }
+    for (int t = 0; t < RTW; ++t) { acc[t] = vzero(); acc2[t] = vzero(); rinv[t] = 1.f; }
     auto brow = [&](int t) { return min((rt0 + t) * 16 + a, N - 1); };     // (rows >= N: copies, never stored)
     // contraction of one tap: D[f, row] += W_k[f, g] z_k[row, g]; `zsrc`: MODE 0 z_k as hi | lo halves, MODE 1 the
     // fp32 rows, MODE 2 ignored (the planes are in PB)
     auto contract = [&](const float* zsrc, const v4f (&A)[NA]) {
         if (!has_mfma) return;
         if (MODE == 0) {
+#pragma unroll
+            for (int t = 0; t < RTW; ++t) {               // into this tap's row scale (split_rows): exact
+                const float* sc = zsrc + brow(t) * kPfZs + kRowScaleCol;
+                const float r = sc[0] * rinv[t];
+                acc[t] *= r;
+                acc2[t] *= r;
+                rinv[t] = sc[1];
+            }
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb) {
                 const v8h Ah = __builtin_bit_cast(v8h, A[2 * kb]);
@@ -509,7 +529,7 @@ __global__ __launch_bounds__(1024) void policy_filter_kernel(const LsigfArgs p) 
 #pragma unroll
         for (int t = 0; t < RTW; ++t) {
             const int row = (rt0 + t) * 16 + a;
-            v4f v = MODE == 0 ? (acc[t] + acc2[t]) * h2_inv + bv : MODE == 1 ? acc[t] + bv : (acc[t] + acc2[t]) + bv;
+            v4f v = MODE == 0 ? (acc[t] + acc2[t]) * (h2_inv * rinv[t]) + bv : MODE == 1 ? acc[t] + bv : (acc[t] + acc2[t]) + bv;
             if (p.relu) v = vrelu(v);
             const v4f d = mfma16x4(A5, v, vzero());    // d[r] = logit part a5 = 4 q + r of this lane's row
             if (rt0 + t < tile_hi && row < N) {

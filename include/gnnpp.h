@@ -45,7 +45,11 @@ extern "C" {
  *       configuration) -- the contraction runs on the exact fp32 MFMA instead: exact as well, only slower.
  *   GNNPP_PREC_FP32_MFMA       v_mfma_f32_16x16x4_f32 everywhere: bitwise an fmaf chain, 2.7x more pipe time.
  *   GNNPP_PREC_SPLIT_F16       fast, NARROWER than fp32: operands as f16 hi + lo halves (22 significand bits)
- *       on v_mfma_f32_16x16x32_f16, valid for |activation| < 65504 only -- see "Range guard"; opt-in. */
+ *       on v_mfma_f32_16x16x32_f16, valid for |activation| < 65504 only -- see "Range guard"; opt-in.  The graph
+ *       filter's operand rows are scaled by a power of two before the split (largest |z| of a row in [2^13, 2^14),
+ *       undone exactly on the accumulators), so its error is fp32-level at any scale from 65504 down to ~2^-50.
+ *       The encoder's activations are split unscaled: there the lo half of a value far below 1 is an f16
+ *       subnormal, an absolute error of ~2^-25 |w| per product that does not shrink with the activations. */
 #define GNNPP_PREC_FP32        0
 #define GNNPP_PREC_FP32_MFMA   1
 #define GNNPP_PREC_SPLIT_F16   2
@@ -173,7 +177,8 @@ int gnnpp_lsigf_fwd(const float* x, const void* S, const float* packed, const fl
 
 /* Range guard (GNNPP_PREC_SPLIT_F16 only; the other modes have no input domain and never touch the flag).
  * The split-f16 schedules feed the f16 matrix pipe with fp32 operands split in hi + lo halves (22 significand
- * bits), which is exact to ~2^-22 as long as every activation satisfies |x| < 65504.  A call
+ * bits), which is exact to ~2^-22 as long as every activation satisfies |x| < 65504 (the filter's rows
+ * are power-of-two scaled first, so small values keep their 22 bits; the encoder's are not, see above).  A call
  * that hands a larger value to that pipe stores 1 to *range_flag (never cleared by the library; plain store, no
  * synchronisation added): the results of that call are then NOT trustworthy -- re-run it with
  * GNNPP_PREC_FP32.  gnnpp_error_string(GNNPP_ERR_RANGE) is the message the Python layer raises. */

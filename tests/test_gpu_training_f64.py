@@ -21,12 +21,11 @@ import pytest
 import torch
 import torch.nn.functional as tF
 
+from f64_yardstick import ULP, ULPS, gap
 from oracle import policy_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-RMS_K, MAX_K, ULPS = 4.0, 8.0, 8.0
-ULP = 2.0 ** -24
 CONV = (0, 4, 7, 11, 14)
 BN = (1, 5, 8, 12, 15)
 POS = (121, 25, 25, 4, 4)                 # positions per image at each convolution's output
@@ -40,19 +39,6 @@ def dev():
     from gnn_pathplanning_amd import _native
     _native.lib()
     return torch.device('cuda:0')
-
-
-def gap(got, want64, ref32, scale=None):
-    """(ok, report) of a kernel result and the fp32 CPU result against the float64 value."""
-    want = np.asarray(want64, np.float64)
-    e = np.asarray(got, np.float64) - want
-    e32 = np.asarray(ref32, np.float64) - want
-    scale = float(np.abs(want).max()) if scale is None else float(scale)
-    floor = ULPS * ULP * scale
-    rms, rms32 = float(np.sqrt(np.mean(e * e))), float(np.sqrt(np.mean(e32 * e32)))
-    mx, mx32 = float(np.abs(e).max()), float(np.abs(e32).max())
-    ok = bool(np.isfinite(e).all()) and rms <= RMS_K * rms32 + floor and mx <= MAX_K * mx32 + floor
-    return ok, dict(rms=rms, rms32=rms32, max=mx, max32=mx32, scale=scale)
 
 
 # ---- the float64 statement -----------------------------------------------------------------------------------------
