@@ -1,0 +1,125 @@
+"""CPU: the inference encoder and the fused policy kernels against float64 on the host emulation (tests/emu/) -- a
+reduced version of tests/test_gpu_policy_f64.py's matrix (same statements, runner and yardstick; small M).  The
+split-f16 encoder is held to the yardstick at activation scale 1; at 1e-3 its documented absolute floor applies (the
+activations' lo halves are f16 subnormals: ~2^-25 |w| per product), pinned as "no larger than at scale 1"."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu'))
+
+import filter_f64_cases as fc  # noqa: E402
+import policy_f64_cases as pc  # noqa: E402
+
+pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
+                                reason='host clang++ from ROCm not present')
+
+B3, B3CP, F32, H2 = 'encoder_kernel_b3<false,3>', 'encoder_kernel_b3<false,3,true>', 'encoder_kernel_f32', \
+    'encoder_kernel_h2<false,3>'
+
+
+@pytest.fixture(scope='module')
+def bk():
+    import emu_lib
+    return fc.EmuBackend(emu_lib.load())
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(seed, M, kind, scale, variant, resid=None):
+    obs1 = pc.make_obs(seed, M, kind)
+    if resid is not None:
+        obs1 = pc.with_residual(obs1, *resid)
+    sd = pc.make_net(seed, obs1, scale=scale, **dict(variant))
+    obs = (obs1.double() * scale).float()
+    pc.check_scales(sd, obs, scale)
+    with torch.no_grad():
+        return sd, obs, pc.encoder_statement(sd, obs.double(), torch.float64).numpy(), \
+            pc.encoder_statement(sd, obs, torch.float32).numpy()
+
+
+ENC = [
+    # auto CP tile: ceil(M / 256) = 1 agent per tile
+    dict(name='%s[tile1]/M1' % B3CP, M=1, seed=1, obs='real', knobs={pc.ENC_CP: 0}, expect={0: B3CP + '[tile1]'}),
+    dict(name='%s[tile1]/M17' % B3CP, M=17, seed=2, obs='binary', knobs={pc.ENC_CP: 0}, expect={0: B3CP + '[tile1]'}),
+    # 16-agent tiles: a full tile and a ragged one (M = 17), three tiles (M = 40)
+    dict(name='%s/M17' % B3, M=17, seed=3, obs='real', knobs={pc.ENC_CP: 16}, expect={0: B3, 1: F32, 2: H2}),
+    dict(name='%s/M40/bf16obs' % B3, M=40, seed=4, obs='bf16', knobs={pc.ENC_CP: 16}, expect={0: B3, 1: F32, 2: H2}),
+    dict(name='%s/M17/weak_channel' % B3, M=17, seed=5, obs='real', knobs={pc.ENC_CP: 16}, net=dict(weak=True),
+         expect={0: B3}),
+    dict(name='%s[tile1]/M17/weak_channel' % B3CP, M=17, seed=5, obs='binary', knobs={pc.ENC_CP: 0},
+         net=dict(weak=True), expect={0: B3CP + '[tile1]'}),
+]
+# one residual pixel in a binary tile: 16-agent tiles of M = 17 (a full tile, then a ragged one of 1 agent) and CP
+# tiles of 7 (two full, a ragged one of 3); agent 2's centre pixel is staged by the fourth wave
+for _tile, _kern in ((16, B3), (7, B3CP + '[tile7]')):
+    for _kind in ('m', 'l'):
+        for _where, _a, _last in (('first', 0, False), ('agent2_wave3', 2, False),
+                                  ('full_tile_last', _tile - 1, False), ('ragged_tile_last', 16, False),
+                                  ('last_pixel', _tile - 1, True)):
+            ENC.append(dict(name='%s/M17/resid_%s/%s' % (_kern, _kind, _where), M=17, seed=6, obs='binary',
+                            knobs={pc.ENC_CP: _tile}, resid=(_a, _kind, _last), expect={0: _kern}))
+
+
+def _case_inputs(case, scale):
+    return _inputs(case['seed'], case['M'], case['obs'], scale, tuple(sorted(case.get('net', {}).items())),
+                   case.get('resid'))
+
+
+# scales 1e-3 and 1; a residual pixel is a one-plane-plus-residual value at scale 1 only
+ENC_SCALED = [(c, s) for c in ENC for s in ((1.0,) if 'resid' in c else (1e-3, 1.0))]
+
+
+@pytest.mark.parametrize('prec', pc.PRECS, ids=pc.PREC_NAMES.get)
+@pytest.mark.parametrize('case,scale', ENC_SCALED, ids=lambda v: v['name'] if isinstance(v, dict) else 'scale=%g' % v)
+def test_emu_encoder_f64(bk, case, scale, prec):
+    sd, obs, w64, w32 = _case_inputs(case, scale)
+    got, kern, flag = pc.run_encoder(bk, sd, obs, prec, case['knobs'], case['expect'], name=case['name'])
+    assert flag == 0, (case['name'], kern)
+    if prec == 2 and scale < 1:
+        # split-f16 below scale 1: the absolute floor, no larger than the error at scale 1
+        sd1, obs1, w64_1, _ = _case_inputs(case, 1.0)
+        got1, _, _ = pc.run_encoder(bk, sd1, obs1, prec, case['knobs'], name=case['name'])
+        assert np.abs(got - w64).max() <= 4 * np.abs(got1 - w64_1).max()
+        return
+    pc.check('%s/%s/%s/scale=%g' % (case['name'], kern, pc.PREC_NAMES[prec], scale), got, w64, w32)
+
+
+POLICY = [
+    # fused, K = 3: N = 5 takes the column-packed front half, N = 13 the agents-on-columns one (fp32 MFMA: unfused)
+    dict(name='encoder_kernel_b3<true,3,true>/B2N5K3', B=2, N=5, K=3, seed=11, obs='real',
+         expect={0: 'encoder_kernel_b3<true,3,true>', 1: F32 + '+filter', 2: 'encoder_kernel_h2<true,3>'}),
+    dict(name='encoder_kernel_b3<true,3,false>/B1N13K3/f64S', B=1, N=13, K=3, seed=12, obs='binary', f64=True,
+         expect={0: 'encoder_kernel_b3<true,3,false>', 1: F32 + '+filter', 2: 'encoder_kernel_h2<true,3>'}),
+    # a residual pixel in the last agent of a binary team (last pixel)
+    dict(name='encoder_kernel_b3<true,3,true>/B2N5K3/resid_l', B=2, N=5, K=3, seed=13, obs='binary',
+         resid=(9, 'l', True), expect={0: 'encoder_kernel_b3<true,3,true>'}),
+    dict(name='encoder_kernel_b3<true,3,true>/B2N5K3/weak_channel', B=2, N=5, K=3, seed=14, obs='real',
+         net=dict(weak=True), expect={0: 'encoder_kernel_b3<true,3,true>'}),
+]
+
+
+@pytest.mark.parametrize('prec', pc.PRECS, ids=pc.PREC_NAMES.get)
+@pytest.mark.parametrize('case', POLICY, ids=lambda c: c['name'])
+def test_emu_policy_f64(bk, case, prec):
+    B, N, K = case['B'], case['N'], case['K']
+    obs1 = pc.make_obs(case['seed'], B * N, case['obs'])
+    if 'resid' in case:
+        obs1 = pc.with_residual(obs1, *case['resid'])
+    sd = pc.make_net(case['seed'], obs1, K=K, **case.get('net', {}))
+    obs = obs1.reshape(B, N, 3, 11, 11)
+    S = pc.make_gso(case['seed'], B, 1, N, f64=case.get('f64', False))
+    with torch.no_grad():
+        f64, l64 = (t.numpy() for t in pc.policy_statement(sd, S, obs, torch.float64))
+        f32, l32 = (t.numpy() for t in pc.policy_statement(sd, S, obs, torch.float32))
+    logits, acts, feat, kern, flag = pc.run_policy(bk, sd, obs, S, K, prec, {pc.FUSED: 1, pc.POLICY_CP: 1},
+                                                   case['expect'], name=case['name'])
+    assert flag == 0
+    tag = '%s/%s/%s' % (case['name'], kern, pc.PREC_NAMES[prec])
+    rep = pc.check(tag + '/logits', logits, l64, l32)
+    if feat is not None:
+        pc.check(tag + '/features', feat, f64, f32)
+    pc.check_actions(tag, acts, l64, rep)

@@ -23,6 +23,7 @@ import torch.nn.functional as tF
 
 from f64_yardstick import ULP, ULPS, gap
 from oracle import policy_oracle as orc
+from policy_f64_cases import filter_stack
 
 pytestmark = pytest.mark.gpu
 
@@ -70,22 +71,7 @@ def statement(sd, S, obs, tgt, N, dtype):
         comp.append(tF.relu(tF.linear(enc[-1], p['compressMLP.0.weight'], p['compressMLP.0.bias'])))
     h = torch.stack(comp, 2)                                             # [B,F,N]
     S4 = (S.unsqueeze(1) if S.dim() == 3 else S).to(dtype)               # [B,E,Ns,Ns]
-    Ns = S4.shape[-1]
-    l = 0
-    while 'GFL.%d.weight' % (2 * l) in p:
-        w, b = p['GFL.%d.weight' % (2 * l)], p.get('GFL.%d.bias' % (2 * l))   # [F,E,K,G], [F,1]
-        z0 = torch.cat([h, h.new_zeros(B, h.shape[1], Ns - N)], 2) if Ns > N else h
-        y = 0
-        for e in range(w.shape[1]):
-            z = z0
-            for k in range(w.shape[2]):
-                if k:
-                    z = z @ S4[:, e]
-                y = y + torch.einsum('fg,bgn->bfn', w[:, e, k], z)
-        if b is not None:
-            y = y + b
-        h = tF.relu(y[:, :, :N])
-        l += 1
+    h = filter_stack(h, S4, p, N)
     logits = torch.stack([tF.linear(h[:, :, n], p['actionsMLP.0.weight'], p['actionsMLP.0.bias'])
                           for n in range(N)], 1)                          # [B,N,5]
     labels = tgt.argmax(-1)                                              # first maximum
