@@ -9,6 +9,7 @@
 #include "encoder_ring_f32.hip"
 #include "encoder_kernel_f32.hip"
 #include "rollout_kernels.hip"       // before the fused policy kernel, which can run the simulator step too
+#include "rollout_team_kernels.hip"  // teams of more than GNNPP_ROLLOUT_MAX_AGENTS agents
 #include "encoder_kernel_h2.hip"
 #include "encoder_kernel_b3.hip"
 #include "lsigf_kernel.hip"
@@ -490,24 +491,30 @@ int gnnpp_decode_actions(const float* logits, int* actions, int B, int N, void* 
     return decode_actions_launch(logits, actions, B, N, static_cast<hipStream_t>(stream));
 }
 
-static int rollout_common_ok(const gnnpp_rollout* r) {
-    return r && r->pos && r->B > 0 && r->N > 0 && r->N <= GNNPP_ROLLOUT_MAX_AGENTS;
+// pointers first, then the sizes: a struct with NULL pointers is GNNPP_ERR_ARG whatever its N
+static int rollout_common_ok(const gnnpp_rollout* r, int max_agents = GNNPP_ROLLOUT_MAX_TEAM) {
+    return r && r->pos && r->B > 0 && r->N > 0 && r->N <= max_agents;
 }
+
+static bool rollout_team(const gnnpp_rollout* r) { return r->N > GNNPP_ROLLOUT_MAX_AGENTS; }
 
 int gnnpp_rollout_observe(const gnnpp_rollout* r, void* stream) {
     if (!rollout_common_ok(r) || !r->grid || !r->goal || !r->obs || r->H <= 0 || r->W <= 0)
         return GNNPP_ERR_ARG;
+    if (rollout_team(r)) return rollout_team_observe_launch(*r, static_cast<hipStream_t>(stream));
     return rollout_observe_launch(*r, static_cast<hipStream_t>(stream));
 }
 
 int gnnpp_rollout_gso(const gnnpp_rollout* r, void* stream) {
     if (!rollout_common_ok(r) || !r->radius || !r->S) return GNNPP_ERR_ARG;
+    if (rollout_team(r)) return rollout_team_gso_launch(*r, r->grow != 0, static_cast<hipStream_t>(stream));
     return rollout_gso_launch(*r, static_cast<hipStream_t>(stream));
 }
 
 int gnnpp_rollout_gso_observe(const gnnpp_rollout* r, void* stream) {
     if (!rollout_common_ok(r) || !r->radius || !r->S || !r->grid || !r->goal || !r->obs || r->H <= 0 || r->W <= 0)
         return GNNPP_ERR_ARG;
+    if (rollout_team(r)) return rollout_team_gso_observe_launch(*r, static_cast<hipStream_t>(stream));
     return rollout_gso_observe_launch(*r, static_cast<hipStream_t>(stream));
 }
 
@@ -519,6 +526,7 @@ int gnnpp_rollout_move(const gnnpp_rollout* r, void* stream) {
     if (r->tie_mode == GNNPP_TIE_REPLAY && (!r->choices || r->max_choices <= 0)) return GNNPP_ERR_ARG;
     if (r->tie_mode < 0 || r->tie_mode > 3) return GNNPP_ERR_ARG;
     if (r->tie_mode == GNNPP_TIE_MT19937 && (!r->rng_words || !r->rng_cursor || r->rng_max <= 0)) return GNNPP_ERR_ARG;
+    if (rollout_team(r)) return rollout_team_move_launch(*r, static_cast<hipStream_t>(stream));
     return rollout_move_launch(*r, static_cast<hipStream_t>(stream));
 }
 
@@ -530,13 +538,15 @@ int gnnpp_rollout_step(const gnnpp_rollout* r, void* stream) {
     if (r->tie_mode == GNNPP_TIE_REPLAY && (!r->choices || r->max_choices <= 0)) return GNNPP_ERR_ARG;
     if (r->tie_mode < 0 || r->tie_mode > 3) return GNNPP_ERR_ARG;
     if (r->tie_mode == GNNPP_TIE_MT19937 && (!r->rng_words || !r->rng_cursor || r->rng_max <= 0)) return GNNPP_ERR_ARG;
+    if (rollout_team(r)) return rollout_team_step_launch(*r, static_cast<hipStream_t>(stream));
     return rollout_step_launch(*r, static_cast<hipStream_t>(stream));
 }
 
 int gnnpp_rollout_policy_step(const gnnpp_rollout* r, const float* enc_packed, const float* filt_packed,
                               const float* gf_bias, const float* act_w, const float* act_b, int K,
                               int precision, void* stream) {
-    if (!rollout_common_ok(r) || !r->grid || !r->goal || !r->obs || !r->radius || !r->S || !r->logits ||
+    if (!rollout_common_ok(r, GNNPP_ROLLOUT_MAX_AGENTS) || !r->grid || !r->goal || !r->obs || !r->radius || !r->S ||
+        !r->logits ||
         !r->reached || !r->start_step || !r->end_step || !r->maxstep || !r->flags || !r->stats ||
         r->H <= 0 || r->W <= 0 || !enc_packed || !filt_packed || !act_w || !act_b)
         return GNNPP_ERR_ARG;

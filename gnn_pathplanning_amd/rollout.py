@@ -24,6 +24,9 @@ import torch
 from . import _native
 
 _TIE = {'lowest': 0, 'hashed': 1, 'replay': 2, 'mt19937': 3}
+MAX_AGENTS = 128            # GNNPP_ROLLOUT_MAX_AGENTS: the one-wave simulator kernels
+MAX_TEAM = 1024             # GNNPP_ROLLOUT_MAX_TEAM
+MAX_TEAM_CELLS = 65536      # GNNPP_ROLLOUT_TEAM_MAX_CELLS: map limit of the large-team kernels
 
 
 def _p(t):
@@ -32,8 +35,11 @@ def _p(t):
 
 class BatchedRollout:
     def __init__(self, grid, starts, goals, maxstep, device, commR=6.0, tie_mode='lowest', seed=0,
-                 rng_words=2048):
-        """grid [B,H,W] or [H,W] (1 = obstacle); starts, goals [B,N,2]; maxstep int or [B]."""
+                 rng_words=None):
+        """grid [B,H,W] or [H,W] (1 = obstacle); starts, goals [B,N,2]; maxstep int or [B].  Teams of up to
+        MAX_TEAM agents; beyond MAX_AGENTS the simulator runs the large-team kernels, which need H * W <=
+        MAX_TEAM_CELLS.  rng_words (tie_mode 'mt19937'): words of each episode's random stream, by default 2048,
+        and 64 per agent for teams of more than MAX_AGENTS agents."""
         dev = torch.device(device)
         if dev.type != 'cuda':
             raise _native.GnnppError('BatchedRollout needs a HIP device (no CPU fallback)')
@@ -48,8 +54,13 @@ class BatchedRollout:
         self.B, self.N = int(self.pos.shape[0]), int(self.pos.shape[1])
         assert self.goal.shape == self.pos.shape and self.pos.shape[2] == 2
         assert not self.grid_batched or self.grid.shape[0] == self.B
-        if self.N > 128:
-            raise _native.GnnppError('at most 128 agents per episode')
+        if self.N > MAX_TEAM:
+            raise _native.GnnppError('at most %d agents per episode' % MAX_TEAM)
+        if self.N > MAX_AGENTS and self.H * self.W > MAX_TEAM_CELLS:
+            raise _native.GnnppError('teams of more than %d agents need a map of at most %d cells (got %d x %d)'
+                                     % (MAX_AGENTS, MAX_TEAM_CELLS, self.H, self.W))
+        if rng_words is None:
+            rng_words = 2048 if self.N <= MAX_AGENTS else 64 * self.N
         ms = torch.as_tensor(maxstep, dtype=torch.int32)
         self.maxstep = (ms if ms.dim() else ms.repeat(self.B)).contiguous().to(dev)
         B, N = self.B, self.N

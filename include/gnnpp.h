@@ -416,7 +416,17 @@ int gnnpp_decode_actions(const float* logits, int* actions, int B, int N, void* 
  * One struct (HOST struct of DEVICE pointers) carries the episode state; each call reads the
  * fields of its section.  Integer / boolean / fp64 work: bit-exact against the simulator.
  * ------------------------------------------------------------------------------------------ */
+/* Team sizes.  Teams of up to GNNPP_ROLLOUT_MAX_AGENTS agents run the one-wave kernels (one wavefront per episode
+ * moves; gnnpp_rollout_step is one launch); gnnpp_rollout_policy_step(s) needs N <= 16 and refuses
+ * N > GNNPP_ROLLOUT_MAX_AGENTS with GNNPP_ERR_ARG.  observe / gso / move / gso_observe / step accept up to
+ * GNNPP_ROLLOUT_MAX_TEAM agents: beyond GNNPP_ROLLOUT_MAX_AGENTS they run the large-team kernels (one workgroup of
+ * one thread per agent per episode for move and gso; step and gso_observe enqueue the separate launches), with the
+ * same results.  Those need H * W <= GNNPP_ROLLOUT_TEAM_MAX_CELLS (the occupancy maps live in LDS); a larger map
+ * returns GNNPP_ERR_UNSUPPORTED with nothing enqueued.  N > GNNPP_ROLLOUT_MAX_TEAM: GNNPP_ERR_ARG.  (v330: the
+ * large-team range widens what the existing entry points accept and adds no symbol.) */
 #define GNNPP_ROLLOUT_MAX_AGENTS 128
+#define GNNPP_ROLLOUT_MAX_TEAM 1024
+#define GNNPP_ROLLOUT_TEAM_MAX_CELLS 65536
 #define GNNPP_TIE_LOWEST  0   /* colliding agent with the lowest index keeps its move          */
 #define GNNPP_TIE_HASHED  1   /* counter-based hash of (seed, episode, step, call)             */
 #define GNNPP_TIE_REPLAY  2   /* replay recorded random.choice outcomes (parity tests)         */
