@@ -37,7 +37,7 @@ EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get
            'gnnpp_filter_head_mode', 'gnnpp_train_pack_floats', 'gnnpp_train_pack', 'gnnpp_lsigf_input_grad', 'gnnpp_linear_fwd',
            'gnnpp_adam_step', 'gnnpp_policy_fwd', 'gnnpp_filter_head_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
            'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe', 'gnnpp_rollout_step', 'gnnpp_rollout_policy_step',
-           'gnnpp_rollout_policy_steps')
+           'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples')
 
 
 class GnnppError(RuntimeError):
@@ -202,6 +202,16 @@ class RolloutStruct(ctypes.Structure):
                 ('rng_cursor', ctypes.c_void_p), ('rng_max', ctypes.c_int)]
 
 
+class ScheduleStruct(ctypes.Structure):
+    """struct gnnpp_schedules (include/gnnpp.h)."""
+    _fields_ = [('grid', ctypes.c_void_p), ('grid_batched', ctypes.c_int), ('goal', ctypes.c_void_p),
+                ('pos', ctypes.c_void_p), ('case_start', ctypes.c_void_p), ('C', ctypes.c_int), ('N', ctypes.c_int),
+                ('H', ctypes.c_int), ('W', ctypes.c_int), ('T_total', ctypes.c_int), ('radius0', ctypes.c_double),
+                ('obs', ctypes.c_void_p), ('S', ctypes.c_void_p), ('S64', ctypes.c_void_p),
+                ('target', ctypes.c_void_p), ('radius', ctypes.c_void_p), ('growth', ctypes.c_void_p),
+                ('status', ctypes.c_void_p), ('step_info', ctypes.c_void_p)]
+
+
 _lib = None
 _measure_lib = None
 
@@ -271,6 +281,8 @@ def _bind(path):
     L.gnnpp_rollout_policy_step.restype = ci
     L.gnnpp_rollout_policy_steps.argtypes = [ctypes.POINTER(RolloutStruct)] + [vp] * 5 + [ci, ci, ci, vp]
     L.gnnpp_rollout_policy_steps.restype = ci
+    L.gnnpp_schedule_samples.argtypes = [ctypes.POINTER(ScheduleStruct), vp]
+    L.gnnpp_schedule_samples.restype = ci
     for f in ('gnnpp_filter_pack', 'gnnpp_lsigf_fwd', 'gnnpp_encoder_pack', 'gnnpp_encoder_fwd',
               'gnnpp_policy_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
            'gnnpp_rollout_move'):

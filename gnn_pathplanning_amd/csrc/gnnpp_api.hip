@@ -10,6 +10,7 @@
 #include "encoder_kernel_f32.hip"
 #include "rollout_kernels.hip"       // before the fused policy kernel, which can run the simulator step too
 #include "rollout_team_kernels.hip"  // teams of more than GNNPP_ROLLOUT_MAX_AGENTS agents
+#include "expert_kernels.hip"        // training samples from expert schedules (uses the rollout's observation / graph code)
 #include "encoder_kernel_h2.hip"
 #include "encoder_kernel_b3.hip"
 #include "lsigf_kernel.hip"
@@ -585,6 +586,16 @@ int gnnpp_rollout_policy_steps(const gnnpp_rollout* r, const float* enc_packed, 
         if (rc != GNNPP_OK) return rc;                   // (argument / shape errors surface at s = 0)
     }
     return GNNPP_OK;
+}
+
+// pointers and sizes first (GNNPP_ERR_ARG), then the supported range: nothing is enqueued on an error
+int gnnpp_schedule_samples(const gnnpp_schedules* s, void* stream) {
+    if (!s || !s->grid || !s->goal || !s->pos || !s->case_start || !s->obs || !s->S || !s->target || !s->radius ||
+        !s->growth || !s->status || !s->step_info || s->C <= 0 || s->T_total <= 0 || s->C > s->T_total || s->N <= 0 ||
+        s->N > GNNPP_ROLLOUT_MAX_AGENTS || s->H <= 0 || s->W <= 0 || !(s->radius0 > 0.0) || !(s->radius0 < 1e300))
+        return GNNPP_ERR_ARG;
+    if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;          // a graph of one node: deg = 0, the reference divides by it
+    return schedule_samples_launch(*s, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -1,0 +1,235 @@
+"""Training samples from expert schedules, on the device: the data side of the reference's "online expert" loop.
+
+    rollout (BatchedRollout) -> write_failure_cases -> any MAPF solver -> read_solution -> samples_from_schedules
+        -> SamplePool.draw -> training.train_step
+
+What the reference does with utils/multirobotsim_dcenlocal_onlineExpert.py::save_failure_cases (:705-730), the ECBS
+binary, and the four-process transformer onlineExpert/DataTransformer_local_onlineExpert.py (the offline
+offlineExpert/DataGen_Transformer.py:295-371, 466-515 computes the same tensors).  The solver stays outside; everything
+around it is here.  The tensors come from ONE gnnpp_schedule_samples call for all cases (csrc/expert_kernels.hip),
+bit-exact with the reference; there is no CPU fallback.
+
+The schedule's communication radius is NOT the rollout's: it starts at commR (5 in both transformers), grows by
+* 1.1 until every step of the case is connected, and the final radius builds every step's graph.
+Positions are (row, col) integers: the reference's (x, y).
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _native, formats
+
+MAX_AGENTS = 128                      # GNNPP_ROLLOUT_MAX_AGENTS
+BAD_MOVE, BAD_STATE, NO_RADIUS = 1, 2, 4          # GNNPP_SCHEDULE_* status bits
+
+
+class ScheduleSamples:
+    """Device tensors of one samples_from_schedules call: input [T,N,3,11,11] f32, GSO [T,N,N] f32, GSO64 (f64 or
+    None), target [T,N,5] f32, case_start [C+1] i32, radius [C] f64, growth [C] i32, step_growth [T] i32 (the growths
+    each step needs on its own)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __getitem__(self, key):
+        return self.__dict__[key]
+
+    def __len__(self):
+        return int(self.input.shape[0])
+
+    def case(self, c):
+        """(input, GSO, target) views of case c."""
+        a, b = self.bounds[c], self.bounds[c + 1]
+        return self.input[a:b], self.GSO[a:b], self.target[a:b]
+
+
+def enqueue_schedule_samples(grid, goal, pos, case_start, out, commR=5.0):
+    """The native call alone, on torch's current stream of the tensors' device: no allocation, no host
+    synchronisation, capturable in a HIP graph.  grid uint8 [C,H,W] | [H,W], goal [C,N,2] / pos [T,N,2] / case_start
+    [C+1] int32, all contiguous device tensors; out: a ScheduleSamples whose tensors match.  out.step_growth receives
+    the raw per-step word (growths | status bits << 16) and out.status the per-case bits: the caller checks them."""
+    dev = _native.require_gpu(grid, goal, pos, case_start, out.input, out.GSO, out.target)
+    s = _native.ScheduleStruct()
+    s.grid, s.grid_batched, s.goal, s.pos = grid.data_ptr(), int(grid.dim() == 3), goal.data_ptr(), pos.data_ptr()
+    s.case_start, s.C, s.N = case_start.data_ptr(), int(goal.shape[0]), int(goal.shape[1])
+    s.H, s.W, s.T_total = int(grid.shape[-2]), int(grid.shape[-1]), int(pos.shape[0])
+    s.radius0 = float(commR)
+    s.obs, s.S, s.target = out.input.data_ptr(), out.GSO.data_ptr(), out.target.data_ptr()
+    s.S64 = out.GSO64.data_ptr() if out.GSO64 is not None else None
+    s.radius, s.growth, s.status = out.radius.data_ptr(), out.growth.data_ptr(), out.status.data_ptr()
+    s.step_info = out.step_growth.data_ptr()
+    with _native.device_guard(dev):
+        _native.check(_native.lib().gnnpp_schedule_samples(ctypes.byref(s), _native.stream_ptr(dev)),
+                      'gnnpp_schedule_samples')
+
+
+def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False):
+    """grids [C,H,W] or [H,W] (1 = obstacle); goals [C,N,2]; schedules: list of C arrays [T_c,N,2] (states of a solved
+    case, agents that arrived waiting on their goal) -> ScheduleSamples.  A schedule with a move that is not one of
+    the five actions, or a state off the map / on an obstacle, raises GnnppError naming the case (the reference dies
+    with ValueError there); this reads the per-case status back, the only host synchronisation."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _native.GnnppError('samples_from_schedules needs a HIP device (no CPU fallback)')
+    _native.lib()
+    g = torch.as_tensor(np.asarray(grids) if not torch.is_tensor(grids) else grids)
+    goal = torch.as_tensor(np.asarray(goals) if not torch.is_tensor(goals) else goals).to(torch.int32)
+    C = len(schedules)
+    if C == 0 or goal.dim() != 3 or goal.shape[0] != C or goal.shape[2] != 2:
+        raise _native.GnnppError('goals must be [C,N,2] with one entry per schedule (C = %d)' % C)
+    N = int(goal.shape[1])
+    if g.dim() not in (2, 3) or (g.dim() == 3 and g.shape[0] != C):
+        raise _native.GnnppError('grids must be [H,W] or [C,H,W]')
+    if not 2 <= N <= MAX_AGENTS:
+        raise _native.GnnppError('teams of 2 to %d agents (got %d)' % (MAX_AGENTS, N))
+    sched = [torch.as_tensor(np.asarray(s) if not torch.is_tensor(s) else s).to(torch.int32) for s in schedules]
+    for c, s in enumerate(sched):
+        if s.dim() != 3 or s.shape[0] < 1 or tuple(s.shape[1:]) != (N, 2):
+            raise _native.GnnppError('schedule %d must be [T,%d,2] with T >= 1 (got %s)' % (c, N, tuple(s.shape)))
+    bounds = [0]
+    for s in sched:
+        bounds.append(bounds[-1] + int(s.shape[0]))
+    T = bounds[-1]
+    grid = g.to(torch.uint8).contiguous().to(dev)
+    goal = goal.contiguous().to(dev)
+    pos = torch.cat(sched, 0).contiguous().to(dev)
+    case_start = torch.tensor(bounds, dtype=torch.int32).to(dev)
+    out = ScheduleSamples(
+        input=torch.empty(T, N, 3, 11, 11, dtype=torch.float32, device=dev),
+        GSO=torch.empty(T, N, N, dtype=torch.float32, device=dev),
+        GSO64=torch.empty(T, N, N, dtype=torch.float64, device=dev) if keep_fp64_gso else None,
+        target=torch.empty(T, N, 5, dtype=torch.float32, device=dev),
+        case_start=case_start, bounds=bounds,
+        radius=torch.empty(C, dtype=torch.float64, device=dev),
+        growth=torch.empty(C, dtype=torch.int32, device=dev),
+        status=torch.empty(C, dtype=torch.int32, device=dev),
+        step_growth=torch.empty(T, dtype=torch.int32, device=dev))
+    out._keep = (grid, goal, pos)                       # inputs of the enqueued launches
+    enqueue_schedule_samples(grid, goal, pos, case_start, out, commR)
+    out.step_growth &= 0xffff                           # (the status bits of a step live above; reported per case)
+    bad = out.status.cpu()
+    if bool((bad != 0).any()):
+        c = int((bad != 0).nonzero()[0])
+        what = [w for bit, w in ((BAD_MOVE, 'a move that is not one of the five actions'),
+                                 (BAD_STATE, 'a state off the map or on an obstacle'),
+                                 (NO_RADIUS, 'no radius connects the team')) if int(bad[c]) & bit]
+        raise _native.GnnppError('schedule of case %d (of %d) cannot be transformed: %s (status %d; %d case(s) flagged)'
+                                 % (c, C, ' and '.join(what), int(bad[c]), int((bad != 0).sum())))
+    return out
+
+
+# ---- the files around the solver ---------------------------------------------------------------------
+def failure_case_yaml(grid, positions, goals):
+    """Text of save_failure_cases (multirobotsim_dcenlocal_onlineExpert.py:705-730) for one episode: map dimensions,
+    obstacles in row-major order, per agent `start` = where it stood when the episode ended, and its goal."""
+    grid = np.asarray(grid)
+    out = ['map:\n', '    dimensions: {}\n'.format([int(grid.shape[0]), int(grid.shape[1])]), '    obstacles:\n']
+    for x, y in np.argwhere(grid != 0):
+        out.append('    - {}\n'.format([int(x), int(y)]))
+    out.append('agents:\n')
+    for n, (p, gl) in enumerate(zip(np.asarray(positions), np.asarray(goals))):
+        out.append('  - name: agent{}\n    start: {}\n    goal: {}\n'.format(n, [int(p[0]), int(p[1])],
+                                                                           [int(gl[0]), int(gl[1])]))
+    return ''.join(out)
+
+
+def write_failure_cases(directory, rollout, ids=None, results=None):
+    """failureCases_ID{:05d}.yaml in `directory` for every episode of a BatchedRollout whose `success` is false.
+    ids: the dataset ID of each episode (default: its index); results: rollout.results() if already at hand.
+    Returns the list of (episode index, path) written."""
+    res = rollout.results() if results is None else results
+    grid, goal = rollout.grid.cpu().numpy(), rollout.goal.cpu().numpy()
+    pos = np.asarray(res['positions'])
+    ids = list(range(rollout.B)) if ids is None else [int(i) for i in ids]
+    if len(ids) != rollout.B:
+        raise _native.GnnppError('ids: one per episode (%d), got %d' % (rollout.B, len(ids)))
+    os.makedirs(directory, exist_ok=True)
+    written = []
+    for b in range(rollout.B):
+        if bool(res['success'][b]):
+            continue
+        path = os.path.join(directory, 'failureCases_ID{:05d}.yaml'.format(ids[b]))
+        with open(path, 'w') as f:
+            f.write(failure_case_yaml(grid[b] if rollout.grid_batched else grid, pos[b], goal[b]))
+        written.append((b, path))
+    return written
+
+
+def _yaml_of(src):
+    import yaml
+    if isinstance(src, (bytes, str)) and not os.path.exists(src):
+        return yaml.safe_load(src)
+    with open(src, 'r') as f:
+        return yaml.safe_load(f)
+
+
+def read_solution(input_yaml, solution_yaml):
+    """(grid [H,W] uint8, goal [N,2] int64, schedule [makespan+1,N,2] int64) of a failure-case file and the solver's
+    answer to it (paths or YAML text), following load_ExpertSolution / obtainSchedule: an agent whose plan is shorter
+    than the team's makespan waits on its goal."""
+    cfg, sol = _yaml_of(input_yaml), _yaml_of(solution_yaml)
+    H, W = cfg['map']['dimensions']
+    grid = np.zeros((H, W), dtype=np.uint8)
+    for x, y in cfg['map']['obstacles'] or []:
+        grid[x][y] = 1
+    agents = cfg['agents']
+    goal = np.array([a['goal'] for a in agents], dtype=np.int64)
+    T = int(sol['statistics']['makespan']) + 1
+    schedule = np.zeros((T, len(agents), 2), dtype=np.int64)
+    for n in range(len(agents)):
+        plan = sol['schedule']['agent{}'.format(n)]
+        for t in range(T):
+            schedule[t, n] = [plan[t]['x'], plan[t]['y']] if t < len(plan) else goal[n]
+    return grid, goal, schedule
+
+
+def save_samples_mat(path, grid, goal, schedule, samples, c=0):
+    """Case c of `samples` as the reference's training file (keys map, goal, inputState, inputTensor, target, GSO,
+    makespan; the transformer's makespan is the number of steps): formats.load_training_step and the reference's
+    dataloader read it.  GSO is the fp64 one when the samples kept it."""
+    a, b = samples.bounds[c], samples.bounds[c + 1]
+    gso = (samples.GSO64 if samples.GSO64 is not None else samples.GSO)[a:b]
+    formats.save_case_mat(path, np.asarray(grid, dtype=np.float64), np.asarray(goal, dtype=np.float64),
+                          np.asarray(schedule, dtype=np.float64), samples.target[a:b].cpu().numpy().astype(np.float64),
+                          b - a, input_tensor=samples.input[a:b].cpu().numpy(), gso=gso.cpu().numpy())
+
+
+class SamplePool:
+    """Device-resident training samples of ONE team size: append ScheduleSamples, draw batches by index gather."""
+
+    def __init__(self):
+        self.input = self.target = self.GSO = None
+
+    def __len__(self):
+        return 0 if self.input is None else int(self.input.shape[0])
+
+    def append(self, samples):
+        new = (samples.input, samples.target, samples.GSO)
+        if self.input is None:
+            self.input, self.target, self.GSO = (t.clone() for t in new)
+            return
+        if new[0].shape[1] != self.input.shape[1] or new[0].device != self.input.device:
+            raise _native.GnnppError('a SamplePool holds one team size on one device (%d agents on %s)'
+                                     % (self.input.shape[1], self.input.device))
+        self.input, self.target, self.GSO = (torch.cat((old, t), 0) for old, t in
+                                             zip((self.input, self.target, self.GSO), new))
+
+    def draw(self, batch_size, generator=None):
+        """(batch_input [B,N,3,11,11], batch_target [B,N,5], batch_GSO [B,N,N]) of batch_size samples drawn uniformly
+        without replacement (with, when the pool is smaller): what train_step / GraphedTrainStep.__call__ take.
+        generator: a torch.Generator of the pool's device, or of the CPU."""
+        n = len(self)
+        if n == 0:
+            raise _native.GnnppError('the pool is empty')
+        gdev = generator.device if generator is not None else self.input.device
+        if batch_size <= n:
+            idx = torch.randperm(n, generator=generator, device=gdev)[:batch_size]
+        else:
+            idx = torch.randint(n, (batch_size,), generator=generator, device=gdev)
+        return self.gather(idx)
+
+    def gather(self, idx):
+        idx = torch.as_tensor(idx, dtype=torch.long).to(self.input.device)
+        return self.input.index_select(0, idx), self.target.index_select(0, idx), self.GSO.index_select(0, idx)

@@ -504,6 +504,49 @@ int gnnpp_rollout_policy_steps(const gnnpp_rollout* r, const float* enc_packed, 
                                const float* gf_bias, const float* act_w, const float* act_b, int K,
                                int nsteps, int precision, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training samples from expert schedules (the reference's offlineExpert/DataGen_Transformer.py:295-371, 466-515 and
+ * onlineExpert/DataTransformer_local_onlineExpert.py): C solved cases, each a schedule of T_c states of N agents,
+ * T_total = sum T_c steps in all, become per step the observation tensor, the normalised communication graph and
+ * the one-hot expert action.  HOST struct of DEVICE pointers, like gnnpp_rollout.  Bit-exact with the reference:
+ *   target[t,n]  one-hot of pos[t+1,n] - pos[t,n] in the order [-1,0] [0,-1] [1,0] [0,1] [0,0]; after a case's last
+ *                state the next state is the goal (obtainSchedule)
+ *   obs[t]       AgentState.toSeqInputTensor (== gnnpp_rollout_observe of the step's positions)
+ *   graph        computeAdjacencyMatrix: the radius starts at radius0, is multiplied by 1.1 until the graph of a step
+ *                is connected, is carried from step to step, and the FINAL radius rebuilds every step of the case.
+ *                radius[c] = radius0 * 1.1 * ... (growth[c] fp64 multiplications);  S64 = (s_i * A_ij) * s_j with
+ *                s = sqrt(1.0 / deg) in fp64, S = (float)S64.
+ * status[c] != 0: the schedule is not one the reference would transform; obs / S / S64 / target of THAT case are
+ * left unwritten, every other case is unaffected.
+ * 2 <= N <= GNNPP_ROLLOUT_MAX_AGENTS (N = 1: GNNPP_ERR_UNSUPPORTED, N > GNNPP_ROLLOUT_MAX_AGENTS: GNNPP_ERR_ARG); the
+ * map must fit the LDS occupancy grid (H * W <= 61 000, H, W <= 16384), else GNNPP_ERR_UNSUPPORTED; nothing is
+ * enqueued on an error.  Three launches on `stream`, no host synchronisation, capturable in a HIP graph.
+ * ------------------------------------------------------------------------------------------ */
+#define GNNPP_SCHEDULE_BAD_MOVE  1   /* a move that is not one of the five deltas (the reference: ValueError)   */
+#define GNNPP_SCHEDULE_BAD_STATE 2   /* a state off the map or on an obstacle                                    */
+#define GNNPP_SCHEDULE_NO_RADIUS 4   /* no connected graph within 65535 radius growths (radius0 far too small)    */
+
+typedef struct gnnpp_schedules {
+    const unsigned char* grid;  /* [C,H,W] when grid_batched else [H,W]; 1 = obstacle                   */
+    int          grid_batched;
+    const int*   goal;          /* [C,N,2] (row, col)                                                   */
+    const int*   pos;           /* [T_total,N,2] the cases' states, concatenated                        */
+    const int*   case_start;    /* [C+1] first step of each case in pos; [0] = 0, [C] = T_total         */
+    int          C, N, H, W, T_total;
+    double       radius0;       /* 5.0 in both reference transformers                                   */
+    float*       obs;           /* out [T_total,N,3,11,11]                                              */
+    float*       S;             /* out [T_total,N,N]                                                    */
+    double*      S64;           /* out [T_total,N,N], or NULL                                           */
+    float*       target;        /* out [T_total,N,5] (what gnnpp_policy_loss reads)                     */
+    double*      radius;        /* out [C] the radius every step of the case was built with             */
+    int*         growth;        /* out [C] times the radius was multiplied by 1.1                       */
+    int*         status;        /* out [C] 0, or GNNPP_SCHEDULE_* bits                                  */
+    int*         step_info;     /* out [T_total]: growths step t needs on its own | its status bits << 16 (also
+                                   the hand-over between the call's launches)                           */
+} gnnpp_schedules;
+
+int gnnpp_schedule_samples(const gnnpp_schedules* s, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,199 @@
+"""CPU: gnnpp_schedule_samples (csrc/expert_kernels.hip), compiled unmodified for the host emulation, against what the
+REAL reference transformer made of the golden cases (tests/golden/expert_schedules.npz): equality, every element."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import expert_cases as ec  # noqa: E402
+
+pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
+                                reason='host clang++ from ROCm not present')
+
+ERR_ARG, ERR_UNSUPPORTED = -1, -2
+BAD_MOVE, BAD_STATE = 1, 2
+
+
+class Schedules(ctypes.Structure):
+    """struct gnnpp_schedules (include/gnnpp.h)."""
+    _fields_ = [('grid', ctypes.c_void_p), ('grid_batched', ctypes.c_int), ('goal', ctypes.c_void_p),
+                ('pos', ctypes.c_void_p), ('case_start', ctypes.c_void_p), ('C', ctypes.c_int), ('N', ctypes.c_int),
+                ('H', ctypes.c_int), ('W', ctypes.c_int), ('T_total', ctypes.c_int), ('radius0', ctypes.c_double),
+                ('obs', ctypes.c_void_p), ('S', ctypes.c_void_p), ('S64', ctypes.c_void_p),
+                ('target', ctypes.c_void_p), ('radius', ctypes.c_void_p), ('growth', ctypes.c_void_p),
+                ('status', ctypes.c_void_p), ('step_info', ctypes.c_void_p)]
+
+
+@pytest.fixture(scope='module')
+def lib():
+    import emu_lib
+    L = emu_lib.load()
+    L.gnnpp_schedule_samples.argtypes = [ctypes.POINTER(Schedules), ctypes.c_void_p]
+    L.gnnpp_schedule_samples.restype = ctypes.c_int
+    return L
+
+
+def call(lib, grids, goals, schedules, radius0=5.0, fp64=True, expect=0, poison=np.nan):
+    """One gnnpp_schedule_samples call on host arrays; outputs start out poisoned, so an element the call does not
+    write cannot pass for one it wrote."""
+    grid = np.ascontiguousarray(grids, dtype=np.uint8)
+    goal = np.ascontiguousarray(goals, dtype=np.int32)
+    C, N = goal.shape[:2]
+    pos = np.ascontiguousarray(np.concatenate(schedules, 0), dtype=np.int32)
+    start = np.ascontiguousarray(np.cumsum([0] + [len(s) for s in schedules]), dtype=np.int32)
+    T = int(start[-1])
+    out = {'obs': np.full((T, N, 3, 11, 11), poison, np.float32), 'S': np.full((T, N, N), poison, np.float32),
+           'S64': np.full((T, N, N), poison, np.float64), 'target': np.full((T, N, 5), poison, np.float32),
+           'radius': np.full(C, poison, np.float64), 'growth': np.full(C, -1, np.int32),
+           'status': np.full(C, -1, np.int32), 'step_info': np.full(T, -1, np.int32), 'start': start}
+    s = Schedules()
+    s.grid, s.grid_batched, s.goal, s.pos = grid.ctypes.data, int(grid.ndim == 3), goal.ctypes.data, pos.ctypes.data
+    s.case_start, s.C, s.N, s.H, s.W, s.T_total = start.ctypes.data, C, N, grid.shape[-2], grid.shape[-1], T
+    s.radius0 = radius0
+    s.obs, s.S, s.target = out['obs'].ctypes.data, out['S'].ctypes.data, out['target'].ctypes.data
+    s.S64 = out['S64'].ctypes.data if fp64 else None
+    s.radius, s.growth, s.status = out['radius'].ctypes.data, out['growth'].ctypes.data, out['status'].ctypes.data
+    s.step_info = out['step_info'].ctypes.data
+    assert lib.gnnpp_schedule_samples(ctypes.byref(s), None) == expect
+    return out
+
+
+def assert_case_equals_golden(out, c, m, g):
+    a, b = int(out['start'][c]), int(out['start'][c + 1])
+    assert out['status'][c] == 0
+    assert out['growth'][c] == m['growth']
+    assert out['radius'][c] == float.fromhex(m['radius'])
+    assert np.array_equal(out['obs'][a:b], g['input'].astype(np.float32))
+    assert np.array_equal(out['target'][a:b], g['target'].astype(np.float32))
+    assert np.array_equal(out['S64'][a:b], g['GSO'])
+    assert np.array_equal(out['S'][a:b], g['GSO'].astype(np.float32))
+    assert (out['step_info'][a:b] >> 16 == 0).all() and (out['step_info'][a:b] & 0xffff).max() == m['growth']
+
+
+@pytest.mark.parametrize('ci', range(8))
+def test_golden_case(lib, ci):
+    m, g = ec.load_golden()[ci]
+    out = call(lib, g['grid'], g['goal'][None], [g['schedule']])
+    assert_case_equals_golden(out, 0, m, g)
+
+
+def test_ragged_cases_in_one_call(lib):
+    """Cases of 25, 7 and 3 steps share a call: the 10-agent 20 x 20 case, its first 7 steps and its last 3 (each a
+    schedule of its own, with its own radius)."""
+    m, g = ec.load_golden()[0]
+    sched = g['schedule']
+    # a schedule cut at step T is a schedule whose "goal" is the state that followed
+    parts, goals = [sched, sched[:7], sched[-3:]], [g['goal'], sched[7], g['goal']]
+    out = call(lib, g['grid'], np.stack(goals), parts)
+    assert_case_equals_golden(out, 0, m, g)
+    assert list(out['start']) == [0, 25, 32, 35]
+    for c, part in enumerate(parts):
+        want = ec.reference_samples(g['grid'], goals[c], part)
+        a, b = int(out['start'][c]), int(out['start'][c + 1])
+        assert out['radius'][c] == want['radius'] and out['growth'][c] == want['growth']
+        assert np.array_equal(out['S64'][a:b], want['GSO'])
+        assert np.array_equal(out['obs'][a:b], want['input'])
+        assert np.array_equal(out['target'][a:b], want['target'])
+    assert len(set(out['growth'].tolist())) > 1        # (the parts really have radii of their own)
+
+
+def test_batched_maps_and_no_fp64_copy(lib):
+    """One map per case (grid_batched), S64 = NULL."""
+    gold = ec.load_golden()
+    (m0, g0), (m4, g4) = gold[0], gold[4]              # 10 and 24 agents: two calls; per call two maps
+    for m, g in ((m0, g0), (m4, g4)):
+        other = np.ascontiguousarray(g['grid'][::-1, ::-1])
+        flipped = (np.array(g['grid'].shape) - 1 - g['schedule']).astype(np.int32)
+        fgoal = (np.array(g['grid'].shape) - 1 - g['goal']).astype(np.int32)
+        out = call(lib, np.stack([other, g['grid']]), np.stack([fgoal, g['goal']]), [flipped, g['schedule']], fp64=False)
+        a = int(out['start'][1])
+        assert out['status'].tolist() == [0, 0] and out['growth'].tolist() == [m['growth']] * 2
+        assert np.array_equal(out['obs'][a:], g['input'].astype(np.float32))
+        assert np.array_equal(out['S'][a:], g['GSO'].astype(np.float32))
+        assert np.isnan(out['S64']).all()
+        want = ec.reference_samples(other, fgoal, flipped)
+        assert np.array_equal(out['obs'][:a], want['input']) and np.array_equal(out['target'][:a], want['target'])
+        assert np.array_equal(out['S'][:a], want['GSO'].astype(np.float32))
+
+
+def test_restatement_equals_reference():
+    """tests/expert_cases.py (the yardstick of the random cases) against the real reference's tensors."""
+    for m, g in ec.load_golden():
+        want = ec.reference_samples(g['grid'], g['goal'], g['schedule'])
+        assert want['radius'] == float.fromhex(m['radius']) and want['growth'] == m['growth']
+        assert np.array_equal(want['GSO'], g['GSO'])
+        assert np.array_equal(want['input'], g['input'].astype(np.float32))
+        assert np.array_equal(want['target'], g['target'].astype(np.float32))
+
+
+def test_status_bits_flag_only_their_case(lib):
+    m, g = ec.load_golden()[2]
+    sched = g['schedule'].copy()
+    jump = sched.copy()
+    diag = next(d for d in ([1, 1], [1, -1], [-1, 1], [-1, -1]) if g['grid'][tuple(jump[2, 1] + d)] == 0)
+    jump[3, 1] = jump[2, 1] + diag                      # a diagonal move into step 3, onto a free cell
+    obstacle = np.argwhere(g['grid'] != 0)[0]
+    stuck = sched.copy()
+    stuck[1, 0] = obstacle                              # a state on an obstacle (also breaks the moves around it)
+    off = sched.copy()
+    off[0, 4] = [-1, 3]                                 # a state off the map
+    late = sched.copy()
+    late[-1, 2] = g['goal'][2] + [2, 0]                 # the last state is two cells from the goal
+    out = call(lib, g['grid'], np.stack([g['goal']] * 6), [sched, jump, stuck, off, late, sched])
+    assert out['status'][0] == 0 and out['status'][5] == 0
+    assert out['status'][1] == BAD_MOVE
+    assert out['status'][2] & BAD_STATE and out['status'][3] & BAD_STATE
+    assert out['status'][4] & BAD_MOVE
+    T = len(sched)
+    for c in (0, 5):                                    # the legal cases next to them: untouched by their neighbours
+        view = {k: v[c * T:(c + 1) * T] if k in ('obs', 'S', 'S64', 'target', 'step_info') else v[c:c + 1]
+                for k, v in out.items() if k != 'start'}
+        view['start'] = np.array([0, T])
+        assert_case_equals_golden(view, 0, m, g)
+    for c in (1, 2, 3, 4):                              # a flagged case is not built
+        assert np.isnan(out['obs'][c * T:(c + 1) * T]).all() and np.isnan(out['S'][c * T:(c + 1) * T]).all()
+
+
+def test_argument_errors(lib):
+    m, g = ec.load_golden()[7]
+    ok = dict(grids=g['grid'], goals=g['goal'][None], schedules=[g['schedule']])
+    call(lib, **ok)
+    one = dict(grids=g['grid'], goals=g['goal'][None, :1], schedules=[g['schedule'][:, :1]])
+    out = call(lib, expect=ERR_UNSUPPORTED, **one)
+    assert np.isnan(out['obs']).all() and (out['status'] == -1).all()          # nothing enqueued
+    big = dict(grids=g['grid'], goals=np.zeros((1, 129, 2), np.int32), schedules=[np.zeros((2, 129, 2), np.int32)])
+    call(lib, expect=ERR_ARG, **big)
+    call(lib, radius0=0.0, expect=ERR_ARG, **ok)
+    call(lib, radius0=float('nan'), expect=ERR_ARG, **ok)
+    huge = dict(grids=np.zeros((300, 300), np.uint8), goals=g['goal'][None], schedules=[g['schedule']])
+    out = call(lib, expect=ERR_UNSUPPORTED, **huge)                            # the map does not fit the LDS grid
+    assert np.isnan(out['obs']).all()
+    assert lib.gnnpp_schedule_samples(None, None) == ERR_ARG
+    s = Schedules()
+    assert lib.gnnpp_schedule_samples(ctypes.byref(s), None) == ERR_ARG        # NULL pointers
+    assert lib.gnnpp_version() == 330
+
+
+def test_large_team_and_map_without_stage(lib):
+    """128 agents (both halves of every lane pair) and a 230 x 230 map: the occupancy grid leaves no room for the LDS
+    output stage, the rows go straight to memory."""
+    rng = np.random.default_rng(11)
+    grid, goal, paths = ec.random_case(rng, 128, 30, 30, density=0.1, max_steps=3)
+    sched = ec.schedule_of(paths, goal)
+    out = call(lib, grid, goal[None], [sched])
+    want = ec.reference_samples(grid, goal, sched)
+    assert out['status'][0] == 0 and out['radius'][0] == want['radius'] and out['growth'][0] == want['growth']
+    assert np.array_equal(out['obs'], want['input']) and np.array_equal(out['S64'], want['GSO'])
+    assert np.array_equal(out['target'], want['target'])
+    grid, goal, paths = ec.random_case(rng, 3, 230, 230, density=0.05, max_steps=2)
+    sched = ec.schedule_of(paths, goal)
+    out = call(lib, grid, goal[None], [sched])
+    want = ec.reference_samples(grid, goal, sched)
+    assert out['status'][0] == 0 and out['radius'][0] == want['radius'] and out['growth'][0] == want['growth']
+    assert np.array_equal(out['obs'], want['input']) and np.array_equal(out['S64'], want['GSO'])
