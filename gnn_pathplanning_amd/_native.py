@@ -37,7 +37,7 @@ EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get
            'gnnpp_filter_head_mode', 'gnnpp_train_pack_floats', 'gnnpp_train_pack', 'gnnpp_lsigf_input_grad', 'gnnpp_linear_fwd',
            'gnnpp_adam_step', 'gnnpp_policy_fwd', 'gnnpp_filter_head_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
            'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe', 'gnnpp_rollout_step', 'gnnpp_rollout_policy_step',
-           'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples')
+           'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples', 'gnnpp_mapf_workspace_bytes', 'gnnpp_mapf_solve')
 
 
 class GnnppError(RuntimeError):
@@ -212,6 +212,16 @@ class ScheduleStruct(ctypes.Structure):
                 ('status', ctypes.c_void_p), ('step_info', ctypes.c_void_p)]
 
 
+class MapfStruct(ctypes.Structure):
+    """struct gnnpp_mapf (include/gnnpp.h)."""
+    _fields_ = [('grid', ctypes.c_void_p), ('grid_batched', ctypes.c_int), ('start', ctypes.c_void_p),
+                ('goal', ctypes.c_void_p), ('order', ctypes.c_void_p), ('C', ctypes.c_int), ('N', ctypes.c_int),
+                ('H', ctypes.c_int), ('W', ctypes.c_int), ('R', ctypes.c_int), ('T_max', ctypes.c_int),
+                ('schedule', ctypes.c_void_p), ('arrival', ctypes.c_void_p), ('makespan', ctypes.c_void_p),
+                ('flowtime', ctypes.c_void_p), ('status', ctypes.c_void_p), ('failing', ctypes.c_void_p),
+                ('restart', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
+
+
 _lib = None
 _measure_lib = None
 
@@ -283,6 +293,10 @@ def _bind(path):
     L.gnnpp_rollout_policy_steps.restype = ci
     L.gnnpp_schedule_samples.argtypes = [ctypes.POINTER(ScheduleStruct), vp]
     L.gnnpp_schedule_samples.restype = ci
+    L.gnnpp_mapf_workspace_bytes.argtypes = [ci] * 4
+    L.gnnpp_mapf_workspace_bytes.restype = cs
+    L.gnnpp_mapf_solve.argtypes = [ctypes.POINTER(MapfStruct), vp]
+    L.gnnpp_mapf_solve.restype = ci
     for f in ('gnnpp_filter_pack', 'gnnpp_lsigf_fwd', 'gnnpp_encoder_pack', 'gnnpp_encoder_fwd',
               'gnnpp_policy_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
            'gnnpp_rollout_move'):

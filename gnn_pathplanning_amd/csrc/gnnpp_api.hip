@@ -11,6 +11,7 @@
 #include "rollout_kernels.hip"       // before the fused policy kernel, which can run the simulator step too
 #include "rollout_team_kernels.hip"  // teams of more than GNNPP_ROLLOUT_MAX_AGENTS agents
 #include "expert_kernels.hip"        // training samples from expert schedules (uses the rollout's observation / graph code)
+#include "mapf_kernels.hip"          // prioritized-planning MAPF solver (the expert of the online loop)
 #include "encoder_kernel_h2.hip"
 #include "encoder_kernel_b3.hip"
 #include "lsigf_kernel.hip"
@@ -596,6 +597,26 @@ int gnnpp_schedule_samples(const gnnpp_schedules* s, void* stream) {
         return GNNPP_ERR_ARG;
     if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;          // a graph of one node: deg = 0, the reference divides by it
     return schedule_samples_launch(*s, static_cast<hipStream_t>(stream));
+}
+
+size_t gnnpp_mapf_workspace_bytes(int C, int R, int H, int T_max) {
+    if (C <= 0 || R <= 0 || H <= 0 || H > GNNPP_MAPF_MAX_SIDE || T_max < 0 || T_max > GNNPP_MAPF_MAX_STEPS ||
+        (long long)C * R > 0x7fffffffLL)
+        return 0;
+    return mapf_workspace_bytes(C, R, H, T_max);
+}
+
+// pointers and sizes first (GNNPP_ERR_ARG), then the supported map size, then the workspace: nothing is enqueued on
+// an error
+int gnnpp_mapf_solve(const gnnpp_mapf* m, void* stream) {
+    if (!m || !m->grid || !m->start || !m->goal || !m->schedule || !m->arrival || !m->makespan || !m->flowtime ||
+        !m->status || !m->failing || !m->restart || !m->workspace || m->C <= 0 || m->N <= 0 ||
+        m->N > GNNPP_ROLLOUT_MAX_AGENTS || m->H <= 0 || m->W <= 0 || m->R <= 0 || (!m->order && m->R != 1) ||
+        m->T_max < 0 || m->T_max > GNNPP_MAPF_MAX_STEPS || (long long)m->C * m->R > 0x7fffffffLL)
+        return GNNPP_ERR_ARG;
+    if (m->H > GNNPP_MAPF_MAX_SIDE || m->W > GNNPP_MAPF_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
+    if (m->workspace_bytes < mapf_workspace_bytes(m->C, m->R, m->H, m->T_max)) return GNNPP_ERR_ARG;
+    return mapf_launch(*m, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

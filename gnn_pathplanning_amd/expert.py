@@ -7,7 +7,8 @@ What the reference does with utils/multirobotsim_dcenlocal_onlineExpert.py::save
 binary, and the four-process transformer onlineExpert/DataTransformer_local_onlineExpert.py (the offline
 offlineExpert/DataGen_Transformer.py:295-371, 466-515 computes the same tensors).  The solver stays outside; everything
 around it is here.  The tensors come from ONE gnnpp_schedule_samples call for all cases (csrc/expert_kernels.hip),
-bit-exact with the reference; there is no CPU fallback.
+bit-exact with the reference; there is no CPU fallback.  The prioritized expert itself runs on the device too (mapf.py):
+solve_failures plans the failed episodes of a rollout and samples_from_solutions turns the solved ones into samples.
 
 The schedule's communication radius is NOT the rollout's: it starts at commR (5 in both transformers), grows by
 * 1.1 until every step of the case is connected, and the final radius builds every step's graph.
@@ -118,6 +119,43 @@ def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64
         raise _native.GnnppError('schedule of case %d (of %d) cannot be transformed: %s (status %d; %d case(s) flagged)'
                                  % (c, C, ' and '.join(what), int(bad[c]), int((bad != 0).sum())))
     return out
+
+
+# ---- the solver on the device (mapf.py) ---------------------------------------------------------------
+def solve_failures(rollout, results=None, **kw):
+    """Plan every episode of a BatchedRollout whose `success` is false, straight from its device state: the agents'
+    final positions as starts, their goals, the episode's map (what write_failure_cases would put in the files).
+    kw: mapf.solve's max_steps, restarts, priorities, seed.  Returns mapf.Solutions of those F episodes with
+    `.episodes` (their indices in the rollout, numpy int64 [F]), or None when every episode succeeded."""
+    from . import mapf
+    res = rollout.results() if results is None else results
+    episodes = np.nonzero(~np.asarray(res['success'], dtype=bool))[0]
+    if len(episodes) == 0:
+        return None
+    idx = torch.as_tensor(episodes, device=rollout.device)
+    grid = rollout.grid.index_select(0, idx) if rollout.grid_batched else rollout.grid
+    sol = mapf.solve(grid, rollout.pos.index_select(0, idx), rollout.goal.index_select(0, idx), rollout.device, **kw)
+    sol.episodes = episodes
+    return sol
+
+
+def samples_from_solutions(solutions, grids, goals, commR=5.0):
+    """(ScheduleSamples of the solved cases of a mapf.Solutions, their case ids numpy int64 [S]) through
+    samples_from_schedules / enqueue_schedule_samples.  grids [C,H,W] or [H,W] and goals [C,N,2]: the cases' maps and
+    goals as solve() was given them (host or device).  Unsolved cases are left out (their ids are missing from the
+    list); (None, empty ids) when no case was solved."""
+    status = solutions.status.cpu().numpy()
+    ids = np.nonzero(status == 0)[0]
+    if len(ids) == 0:
+        return None, ids
+    dev = solutions.status.device
+    makespan = solutions.makespan.cpu().numpy()
+    idx = torch.as_tensor(ids, device=dev)
+    g = grids if torch.is_tensor(grids) else torch.as_tensor(np.asarray(grids))
+    g = g.to(dev).index_select(0, idx) if g.dim() == 3 else g
+    gl = (goals if torch.is_tensor(goals) else torch.as_tensor(np.asarray(goals))).to(dev).index_select(0, idx)
+    sched = [solutions.schedules[c, :int(makespan[c]) + 1] for c in ids]
+    return samples_from_schedules(g, gl, sched, dev, commR=commR), ids
 
 
 # ---- the files around the solver ---------------------------------------------------------------------

@@ -547,6 +547,63 @@ typedef struct gnnpp_schedules {
 
 int gnnpp_schedule_samples(const gnnpp_schedules* s, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MAPF solver: prioritized planning of C cases (the reference's SIPP expert option, offlineExpert/CasesSolver.py:517-539
+ * `mapf_prioritized_sipp`, a binary without source).  Per case: a grid (1 = obstacle), starts / goals [N,2] (row, col),
+ * R planning orders (permutations of the agents) and a horizon T_max.  Agents are planned one after another in the
+ * order, each against the finished plans of the agents before it; agents after it are ignored.
+ *   moves      up, left, down, right, stop; a move may not leave the map or enter an obstacle;
+ *   parking    an agent stays on its goal from its arrival a_j on;
+ *   conflicts  vertex: no cell an earlier agent (parked ones included) holds at the same t >= 1; swap: no move b -> a
+ *              from t to t+1 while an earlier agent moves a -> b (following into a cell vacated in the same step is
+ *              allowed, as in the reference simulator);
+ *   layers     R_0 = {start}; R_{t+1} = free cells no earlier agent holds at t+1, reached from R_t by a stop or a move
+ *              that is not a swap;
+ *   arrival    a_i = the smallest t >= t_min with goal in R_t, t_min = 1 + the last t <= T_max an earlier agent holds the
+ *              goal.  a_i > T_max (or the goal an earlier agent's parking cell): GNNPP_MAPF_NO_PATH, this agent is the
+ *              failing one and no later agent is planned;
+ *   path       walked back from (goal, a_i): the first predecessor in R_{t-1} in the order stop, then the cell that
+ *              entered by up, left, down, right, whose move is not a swap;
+ *   restarts   each order is planned on its own; the case keeps the best by: solved first, smallest flowtime sum a_i,
+ *              smallest makespan max a_i, lowest restart index (an unsolved restart has flowtime = makespan = -1).
+ * Outputs (every one written by the call):
+ *   schedule [C,T_max+1,N,2]  positions; agents wait on their goal after arriving; agents left unplanned: -1
+ *   arrival  [C,N]            a_i, -1 when unplanned;   makespan, flowtime [C]: -1 unless solved
+ *   status   [C]              0 = solved, GNNPP_MAPF_* bits;   failing [C]: agent index or -1;   restart [C]: chosen or -1
+ * A case with a start / goal off the map or on an obstacle, two equal starts or goals, or an order that is not a
+ * permutation is GNNPP_MAPF_BAD_CASE (all its outputs -1, status 2); other cases are unaffected.
+ * Limits: 1 <= N <= GNNPP_ROLLOUT_MAX_AGENTS, R >= 1, 0 <= T_max <= GNNPP_MAPF_MAX_STEPS (GNNPP_ERR_ARG);
+ * H, W <= GNNPP_MAPF_MAX_SIDE, else GNNPP_ERR_UNSUPPORTED.  order == NULL: the index order, R must be 1.
+ * workspace: gnnpp_mapf_workspace_bytes(C, R, H, T_max) bytes of device memory (no initial contents).  Deterministic,
+ * no atomics; two or three launches on `stream`, no host synchronisation, capturable in a HIP graph; nothing is
+ * enqueued on an error.
+ * ------------------------------------------------------------------------------------------ */
+#define GNNPP_MAPF_NO_PATH   1     /* an agent has no arrival within T_max                                     */
+#define GNNPP_MAPF_BAD_CASE  2     /* invalid starts / goals / order                                           */
+#define GNNPP_MAPF_MAX_SIDE  64    /* a map row is one 64-bit word, a map one wave of rows                       */
+#define GNNPP_MAPF_MAX_STEPS 1024  /* T_max bound (the default horizon 4 (H + W) is at most 512)               */
+
+typedef struct gnnpp_mapf {
+    const unsigned char* grid;  /* [C,H,W] when grid_batched else [H,W]; 1 = obstacle                   */
+    int          grid_batched;
+    const int*   start;         /* [C,N,2] (row, col)                                                   */
+    const int*   goal;          /* [C,N,2]                                                              */
+    const int*   order;         /* [C,R,N] planning orders, or NULL (index order, R = 1)                */
+    int          C, N, H, W, R, T_max;
+    int*         schedule;      /* out [C,T_max+1,N,2]                                                  */
+    int*         arrival;       /* out [C,N]                                                            */
+    int*         makespan;      /* out [C]                                                              */
+    int*         flowtime;      /* out [C] (ECBS's `cost`)                                              */
+    int*         status;        /* out [C]                                                              */
+    int*         failing;       /* out [C]                                                              */
+    int*         restart;       /* out [C]                                                              */
+    void*        workspace;     /* gnnpp_mapf_workspace_bytes(C, R, H, T_max) bytes                      */
+    size_t       workspace_bytes;
+} gnnpp_mapf;
+
+size_t gnnpp_mapf_workspace_bytes(int C, int R, int H, int T_max);   /* 0 on invalid arguments */
+int gnnpp_mapf_solve(const gnnpp_mapf* m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

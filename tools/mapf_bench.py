@@ -1,0 +1,92 @@
+"""Time one gnnpp_mapf_solve call: cases per second and agent-plans per second.
+
+    python tools/mapf_bench.py [--reps 10] [--out profiles/mapf_solve.json] [--only NAME] [--cpu-cases 16]
+
+Configurations (random maps of tests/expert_cases.random_map at density 0.1, horizon 4 (H + W)): 512 cases x 10 agents
+on 20 x 20 with R = 1 and R = 4 orders, 256 x 20 on 20 x 20, 128 x 64 on 40 x 40.  Outputs and workspace are
+preallocated; the call is timed with HIP events after 3 warm-up calls, mean over --reps calls.  An agent-plan is one
+agent planned in one restart (C * R * N per call, whether or not the case is solved).  Beside each GPU rate: the
+sequential numpy restatement (tests/mapf_cases.py) on the first --cpu-cases cases of the same inputs, on the host, as
+context (it is the yardstick, not a tuned CPU solver).  --only NAME runs one configuration (for a profiler run).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+CONFIGS = (('c512_n10_20x20_r1', 512, 10, 20, 1), ('c512_n10_20x20_r4', 512, 10, 20, 4),
+           ('c256_n20_20x20_r1', 256, 20, 20, 1), ('c128_n64_40x40_r1', 128, 64, 40, 1))
+
+
+def timed(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(reps):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e-3 / reps                           # seconds per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--only', default=None)
+    ap.add_argument('--cpu-cases', type=int, default=16)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'needs the MI355X: a CPU run measures nothing'
+    import mapf_cases as mc
+    from gnn_pathplanning_amd import mapf
+    dev = torch.device('cuda:0')
+    records = []
+    for name, C, N, side, R in CONFIGS:
+        if a.only and name != a.only:
+            continue
+        rng = np.random.default_rng(C * N + side)
+        cases = mc.random_cases(rng, C, N, side, density=0.1)
+        T = mc.default_horizon(side, side)
+        grid = torch.from_numpy(np.stack([c[0] for c in cases])).to(dev)
+        start = torch.from_numpy(np.stack([c[1] for c in cases]).astype(np.int32)).to(dev)
+        goal = torch.from_numpy(np.stack([c[2] for c in cases]).astype(np.int32)).to(dev)
+        orders = np.stack([np.stack([np.arange(N)] + [rng.permutation(N) for _ in range(R - 1)]) for _ in cases])
+        order = torch.from_numpy(orders.astype(np.int32)).to(dev) if R > 1 else None
+        out = mapf.empty_solutions(C, N, side, T, dev, R)
+        sec = timed(lambda: mapf.enqueue_solve(grid, start, goal, order, out), a.reps)
+        solved = int((out.status == 0).sum().item())
+        k = min(a.cpu_cases, C)
+        t0 = time.perf_counter()
+        cpu = [mc.solve_case(g, s, gl, T, None if R == 1 else list(orders[c])) for c, (g, s, gl) in enumerate(cases[:k])]
+        cpu_sec = (time.perf_counter() - t0) / k
+        same = all(int(out.status[c]) == w['status'] and int(out.flowtime[c]) == w['flowtime'] for c, w in enumerate(cpu))
+        rec = {'config': name, 'what': 'gnnpp_mapf_solve, one call, HIP events, mean of %d calls after 3' % a.reps,
+               'cases': C, 'agents': N, 'map': '%dx%d' % (side, side), 'restarts': R, 'T_max': T,
+               'ms_per_call': round(sec * 1e3, 4), 'cases_per_s': round(C / sec),
+               'agent_plans_per_s': round(C * R * N / sec), 'solved': solved,
+               'makespan_max': int(out.makespan.max().item()),
+               'workspace_MB': round(out.workspace.numel() / 2 ** 20, 1),
+               'cpu_yardstick_cases_per_s': round(1 / cpu_sec, 2), 'cpu_yardstick_cases_timed': k,
+               'cpu_yardstick_agrees': same}
+        print(json.dumps(rec), flush=True)
+        records.append(rec)
+        del out
+        torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, 'w') as f:
+            json.dump({'device': torch.cuda.get_device_name(0), 'records': records}, f, indent=1)
+            f.write('\n')
+
+
+if __name__ == '__main__':
+    main()
