@@ -37,7 +37,8 @@ EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get
            'gnnpp_filter_head_mode', 'gnnpp_train_pack_floats', 'gnnpp_train_pack', 'gnnpp_lsigf_input_grad', 'gnnpp_linear_fwd',
            'gnnpp_adam_step', 'gnnpp_policy_fwd', 'gnnpp_filter_head_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
            'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe', 'gnnpp_rollout_step', 'gnnpp_rollout_policy_step',
-           'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples', 'gnnpp_mapf_workspace_bytes', 'gnnpp_mapf_solve')
+           'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples', 'gnnpp_mapf_workspace_bytes', 'gnnpp_mapf_solve',
+           'gnnpp_mapf_team_workspace_bytes', 'gnnpp_mapf_team_solve')
 
 
 class GnnppError(RuntimeError):
@@ -297,6 +298,10 @@ def _bind(path):
     L.gnnpp_mapf_workspace_bytes.restype = cs
     L.gnnpp_mapf_solve.argtypes = [ctypes.POINTER(MapfStruct), vp]
     L.gnnpp_mapf_solve.restype = ci
+    L.gnnpp_mapf_team_workspace_bytes.argtypes = [ci] * 5
+    L.gnnpp_mapf_team_workspace_bytes.restype = cs
+    L.gnnpp_mapf_team_solve.argtypes = [ctypes.POINTER(MapfStruct), vp]
+    L.gnnpp_mapf_team_solve.restype = ci
     for f in ('gnnpp_filter_pack', 'gnnpp_lsigf_fwd', 'gnnpp_encoder_pack', 'gnnpp_encoder_fwd',
               'gnnpp_policy_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
            'gnnpp_rollout_move'):

@@ -12,6 +12,7 @@
 #include "rollout_team_kernels.hip"  // teams of more than GNNPP_ROLLOUT_MAX_AGENTS agents
 #include "expert_kernels.hip"        // training samples from expert schedules (uses the rollout's observation / graph code)
 #include "mapf_kernels.hip"          // prioritized-planning MAPF solver (the expert of the online loop)
+#include "mapf_team_kernels.hip"     // ... for teams of up to 1024 agents on maps of up to 256 x 256 (one workgroup per case)
 #include "encoder_kernel_h2.hip"
 #include "encoder_kernel_b3.hip"
 #include "lsigf_kernel.hip"
@@ -617,6 +618,26 @@ int gnnpp_mapf_solve(const gnnpp_mapf* m, void* stream) {
     if (m->H > GNNPP_MAPF_MAX_SIDE || m->W > GNNPP_MAPF_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
     if (m->workspace_bytes < mapf_workspace_bytes(m->C, m->R, m->H, m->T_max)) return GNNPP_ERR_ARG;
     return mapf_launch(*m, static_cast<hipStream_t>(stream));
+}
+
+size_t gnnpp_mapf_team_workspace_bytes(int C, int R, int H, int W, int T_max) {
+    if (C <= 0 || R <= 0 || H <= 0 || H > GNNPP_MAPF_TEAM_MAX_SIDE || W <= 0 || W > GNNPP_MAPF_TEAM_MAX_SIDE || T_max < 0 ||
+        T_max > GNNPP_MAPF_TEAM_MAX_STEPS || (long long)C * R > 0x7fffffffLL)
+        return 0;
+    return mapf_team_workspace_bytes(C, R, H, W, T_max);
+}
+
+// the order of gnnpp_mapf_solve's checks; the workspace must hold the summary and at least one slot
+int gnnpp_mapf_team_solve(const gnnpp_mapf* m, void* stream) {
+    if (!m || !m->grid || !m->start || !m->goal || !m->schedule || !m->arrival || !m->makespan || !m->flowtime ||
+        !m->status || !m->failing || !m->restart || !m->workspace || m->C <= 0 || m->N <= 0 ||
+        m->N > GNNPP_ROLLOUT_MAX_TEAM || m->H <= 0 || m->W <= 0 || m->R <= 0 || (!m->order && m->R != 1) ||
+        m->T_max < 0 || m->T_max > GNNPP_MAPF_TEAM_MAX_STEPS || (long long)m->C * m->R > 0x7fffffffLL)
+        return GNNPP_ERR_ARG;
+    if (m->H > GNNPP_MAPF_TEAM_MAX_SIDE || m->W > GNNPP_MAPF_TEAM_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
+    const int slots = mapf_team_slots((long long)m->C * m->R, m->R, m->C, m->H, m->W, m->T_max, m->workspace_bytes);
+    if (slots < 1) return GNNPP_ERR_ARG;
+    return mapf_team_launch(*m, slots, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -125,8 +125,10 @@ def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64
 def solve_failures(rollout, results=None, **kw):
     """Plan every episode of a BatchedRollout whose `success` is false, straight from its device state: the agents'
     final positions as starts, their goals, the episode's map (what write_failure_cases would put in the files).
-    kw: mapf.solve's max_steps, restarts, priorities, seed.  Returns mapf.Solutions of those F episodes with
-    `.episodes` (their indices in the rollout, numpy int64 [F]), or None when every episode succeeded."""
+    kw: mapf.solve's max_steps, restarts, priorities, seed.  Teams of more than mapf.MAX_AGENTS agents and maps with a
+    side beyond mapf.MAX_SIDE go to mapf.solve_team (which also takes workspace_bytes), everything else to mapf.solve.
+    Returns mapf.Solutions of those F episodes with `.episodes` (their indices in the rollout, numpy int64 [F]), or
+    None when every episode succeeded."""
     from . import mapf
     res = rollout.results() if results is None else results
     episodes = np.nonzero(~np.asarray(res['success'], dtype=bool))[0]
@@ -134,7 +136,9 @@ def solve_failures(rollout, results=None, **kw):
         return None
     idx = torch.as_tensor(episodes, device=rollout.device)
     grid = rollout.grid.index_select(0, idx) if rollout.grid_batched else rollout.grid
-    sol = mapf.solve(grid, rollout.pos.index_select(0, idx), rollout.goal.index_select(0, idx), rollout.device, **kw)
+    team = rollout.N > mapf.MAX_AGENTS or max(int(rollout.grid.shape[-2]), int(rollout.grid.shape[-1])) > mapf.MAX_SIDE
+    sol = (mapf.solve_team if team else mapf.solve)(grid, rollout.pos.index_select(0, idx),
+                                                    rollout.goal.index_select(0, idx), rollout.device, **kw)
     sol.episodes = episodes
     return sol
 
@@ -144,6 +148,10 @@ def samples_from_solutions(solutions, grids, goals, commR=5.0):
     samples_from_schedules / enqueue_schedule_samples.  grids [C,H,W] or [H,W] and goals [C,N,2]: the cases' maps and
     goals as solve() was given them (host or device).  Unsolved cases are left out (their ids are missing from the
     list); (None, empty ids) when no case was solved."""
+    if int(solutions.arrival.shape[1]) > MAX_AGENTS:
+        raise _native.GnnppError('samples_from_solutions: samples are built for teams of at most %d agents; these '
+                                 'solutions have %d (mapf.solve_team plans larger teams, the sample builder '
+                                 'gnnpp_schedule_samples does not take them yet)' % (MAX_AGENTS, solutions.arrival.shape[1]))
     status = solutions.status.cpu().numpy()
     ids = np.nonzero(status == 0)[0]
     if len(ids) == 0:

@@ -6,7 +6,9 @@ The reference's expert solvers are prebuilt binaries without source (offlineExpe
 --chosen_solver ecbs | cbs | mapf_prioritized_sipp).  This is the prioritized option, restated exactly (include/gnnpp.h,
 gnnpp_mapf): agents are planned one after another in a planning order, each against the finished plans of the agents
 before it (vertex, swap and parking conflicts), by a bit-parallel search over time; one call plans C cases with R
-orders each (csrc/mapf_kernels.hip).  Restart 0 is the index order, further restarts seeded random permutations; a
+orders each (csrc/mapf_kernels.hip: one wave per case, teams of up to 128 agents on maps of up to 64 x 64 -- solve;
+csrc/mapf_team_kernels.hip: one workgroup per case, up to 1024 agents on maps of up to 256 x 256 -- solve_team; the
+same contract and, where both apply, the same outputs).  Restart 0 is the index order, further restarts seeded random permutations; a
 case keeps its best restart (solved, then smallest flowtime, smallest makespan, lowest index).  There is no CPU
 fallback.  Positions are (row, col) integers: the reference's (x, y).
 """
@@ -20,6 +22,9 @@ from . import _native
 MAX_AGENTS = 128                      # GNNPP_ROLLOUT_MAX_AGENTS
 MAX_SIDE = 64                         # GNNPP_MAPF_MAX_SIDE
 MAX_STEPS = 1024                      # GNNPP_MAPF_MAX_STEPS
+MAX_TEAM = 1024                       # GNNPP_ROLLOUT_MAX_TEAM        (solve_team)
+MAX_TEAM_SIDE = 256                   # GNNPP_MAPF_TEAM_MAX_SIDE
+MAX_TEAM_STEPS = 2048                 # GNNPP_MAPF_TEAM_MAX_STEPS
 NO_PATH, BAD_CASE = 1, 2              # GNNPP_MAPF_* status bits
 
 
@@ -75,18 +80,56 @@ def workspace_bytes(C, R, H, T):
     return n
 
 
-def empty_solutions(C, N, H, T, device, restarts=1):
-    """Output tensors and workspace of a call on C cases of N agents, maps of H rows, horizon T, `restarts` orders."""
+_workspace_bytes = workspace_bytes      # (empty_solutions has a parameter of that name)
+
+
+def team_workspace_bytes(C, R, H, W, T):
+    """Workspace of a solve_team call with a slot for each of its min(C R, 256) workgroups.  enqueue_solve_team takes
+    any workspace that holds the summary and at least one slot (team_workspace_min_bytes) and plans as many items at a
+    time as slots fit."""
+    n = _native.lib().gnnpp_mapf_team_workspace_bytes(int(C), int(R), int(H), int(W), int(T))
+    if n == 0:
+        raise _native.GnnppError('no MAPF team workspace for C=%d R=%d H=%d W=%d T_max=%d' % (C, R, H, W, T))
+    return n
+
+
+def team_slot_bytes(H, W, T):
+    """One workspace slot: six planes of H ceil(W / 64) 64-bit words per time step 0 .. T."""
+    return (int(T) + 1) * 6 * int(H) * ((int(W) + 63) // 64) * 8
+
+
+def team_workspace_min_bytes(C, R, H, W, T):
+    """The summary and one slot: the smallest workspace enqueue_solve_team accepts."""
+    return team_workspace_bytes(C, R, H, W, T) - (min(int(C) * int(R), 256) - 1) * team_slot_bytes(H, W, T)
+
+
+def empty_solutions(C, N, H, T, device, restarts=1, W=None, team=False, workspace_bytes=None):
+    """Output tensors and workspace of a call on C cases of N agents, maps of H rows, horizon T, `restarts` orders.
+    team=True: for enqueue_solve_team (W, the maps' columns, is needed then); workspace_bytes: its workspace, at least
+    team_workspace_min_bytes (default: team_workspace_bytes, a slot per workgroup)."""
     dev = torch.device(device)
 
     def i32(*shape):
         return torch.empty(shape, dtype=torch.int32, device=dev)
+    if team:
+        if W is None:
+            raise _native.GnnppError('empty_solutions(team=True) needs W, the number of map columns')
+        nbytes = team_workspace_bytes(C, restarts, H, W, T)
+        if workspace_bytes is not None:
+            least = team_workspace_min_bytes(C, restarts, H, W, T)
+            if int(workspace_bytes) < least:
+                raise _native.GnnppError('workspace_bytes = %d holds no slot: at least %d bytes' % (workspace_bytes, least))
+            nbytes = min(nbytes, int(workspace_bytes))
+    else:
+        if workspace_bytes is not None:
+            raise _native.GnnppError('workspace_bytes applies to team=True only')
+        nbytes = _workspace_bytes(C, restarts, H, T)
     return Solutions(schedules=i32(C, T + 1, N, 2), arrival=i32(C, N), makespan=i32(C), flowtime=i32(C),
                      status=i32(C), failing=i32(C), restart=i32(C),
-                     workspace=torch.empty(workspace_bytes(C, restarts, H, T), dtype=torch.uint8, device=dev))
+                     workspace=torch.empty(nbytes, dtype=torch.uint8, device=dev))
 
 
-def enqueue_solve(grid, start, goal, order, out):
+def enqueue_solve(grid, start, goal, order, out, _team=False):
     """The native call alone, on torch's current stream of the tensors' device: no allocation, no host
     synchronisation, capturable in a HIP graph.  grid uint8 [C,H,W] | [H,W]; start, goal int32 [C,N,2]; order int32
     [C,R,N] or None (the index order); out: from empty_solutions (horizon T = out.schedules.shape[1] - 1).  All
@@ -104,8 +147,15 @@ def enqueue_solve(grid, start, goal, order, out):
     m.flowtime, m.status, m.failing = out.flowtime.data_ptr(), out.status.data_ptr(), out.failing.data_ptr()
     m.restart = out.restart.data_ptr()
     m.workspace, m.workspace_bytes = out.workspace.data_ptr(), out.workspace.numel()
+    name = 'gnnpp_mapf_team_solve' if _team else 'gnnpp_mapf_solve'
     with _native.device_guard(dev):
-        _native.check(_native.lib().gnnpp_mapf_solve(ctypes.byref(m), _native.stream_ptr(dev)), 'gnnpp_mapf_solve')
+        _native.check(getattr(_native.lib(), name)(ctypes.byref(m), _native.stream_ptr(dev)), name)
+
+
+def enqueue_solve_team(grid, start, goal, order, out):
+    """enqueue_solve for teams of up to MAX_TEAM agents on maps of up to MAX_TEAM_SIDE rows and columns
+    (gnnpp_mapf_team_solve); out: from empty_solutions(..., W=W, team=True)."""
+    enqueue_solve(grid, start, goal, order, out, _team=True)
 
 
 def _int32(x):
@@ -118,25 +168,48 @@ def solve(grids, starts, goals, device, max_steps=None, restarts=1, priorities=N
     cases), permutations of the agents; by default restart 0 is the index order and restarts 1 .. restarts-1 are
     random permutations drawn from numpy's default_rng(seed).  Returns Solutions; unsolved and invalid cases are
     reported in .status (NO_PATH, BAD_CASE), never raised."""
+    return _solve('mapf.solve', False, MAX_AGENTS, MAX_SIDE, MAX_STEPS, grids, starts, goals, device, max_steps,
+                  restarts, priorities, seed, None)
+
+
+def solve_team(grids, starts, goals, device, max_steps=None, restarts=1, priorities=None, seed=0, workspace_bytes=None):
+    """solve() for teams of up to MAX_TEAM agents on maps of up to MAX_TEAM_SIDE x MAX_TEAM_SIDE cells and horizons of
+    up to MAX_TEAM_STEPS (csrc/mapf_team_kernels.hip): the same arguments, default orders, Solutions and, for a case
+    both accept, the same outputs.  workspace_bytes: a cap on the workspace (default: a slot for each of the call's
+    min(C R, 256) workgroups -- 12.6 MB per slot at 128 x 128 and T_max = 1024, 100.7 MB at 256 x 256 and 2048); with
+    less, fewer items are planned at a time, with the same results; less than one slot raises GnnppError."""
+    return _solve('mapf.solve_team', True, MAX_TEAM, MAX_TEAM_SIDE, MAX_TEAM_STEPS, grids, starts, goals, device,
+                  max_steps, restarts, priorities, seed, workspace_bytes)
+
+
+def default_orders(C, N, restarts, seed):
+    """[C,restarts,N] int64: restart 0 the index order, the others permutations from numpy's default_rng(seed)."""
+    rng = np.random.default_rng(seed)
+    perm = np.argsort(rng.random((C, int(restarts) - 1, N)), axis=-1)
+    return np.concatenate([np.broadcast_to(np.arange(N), (C, 1, N)), perm], 1)
+
+
+def _solve(what, team, max_agents, max_side, max_steps_limit, grids, starts, goals, device, max_steps, restarts,
+           priorities, seed, workspace_bytes):
     dev = torch.device(device)
     if dev.type != 'cuda':
-        raise _native.GnnppError('mapf.solve needs a HIP device (no CPU fallback)')
+        raise _native.GnnppError('%s needs a HIP device (no CPU fallback)' % what)
     g = grids if torch.is_tensor(grids) else torch.as_tensor(np.asarray(grids))
     start, goal = _int32(starts), _int32(goals)
     if start.dim() != 3 or start.shape[2] != 2 or tuple(goal.shape) != tuple(start.shape) or start.shape[0] < 1:
         raise _native.GnnppError('starts and goals must both be [C,N,2] with C >= 1 (got %s and %s)'
                                  % (tuple(start.shape), tuple(goal.shape)))
     C, N = int(start.shape[0]), int(start.shape[1])
-    if not 1 <= N <= MAX_AGENTS:
-        raise _native.GnnppError('teams of 1 to %d agents (got %d)' % (MAX_AGENTS, N))
+    if not 1 <= N <= max_agents:
+        raise _native.GnnppError('teams of 1 to %d agents (got %d)' % (max_agents, N))
     if g.dim() not in (2, 3) or (g.dim() == 3 and g.shape[0] != C):
         raise _native.GnnppError('grids must be [H,W] or [C,H,W] with one map per case')
     H, W = int(g.shape[-2]), int(g.shape[-1])
-    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise _native.GnnppError('maps of at most %d x %d cells (got %d x %d)' % (MAX_SIDE, MAX_SIDE, H, W))
+    if not (1 <= H <= max_side and 1 <= W <= max_side):
+        raise _native.GnnppError('maps of at most %d x %d cells (got %d x %d)' % (max_side, max_side, H, W))
     T = 4 * (H + W) if max_steps is None else int(max_steps)
-    if not 0 <= T <= MAX_STEPS:
-        raise _native.GnnppError('max_steps must be in 0 .. %d (got %d)' % (MAX_STEPS, T))
+    if not 0 <= T <= max_steps_limit:
+        raise _native.GnnppError('max_steps must be in 0 .. %d (got %d)' % (max_steps_limit, T))
     order = None
     if priorities is not None:
         order = _int32(priorities)
@@ -146,10 +219,7 @@ def solve(grids, starts, goals, device, max_steps=None, restarts=1, priorities=N
             raise _native.GnnppError('priorities must be [C,R,N] or [R,N] (C = %d, N = %d), got %s'
                                      % (C, N, tuple(order.shape)))
     elif int(restarts) > 1:
-        rng = np.random.default_rng(seed)
-        perm = np.argsort(rng.random((C, int(restarts) - 1, N)), axis=-1)
-        order = torch.from_numpy(np.concatenate([np.broadcast_to(np.arange(N), (C, 1, N)), perm], 1))
-        order = order.to(torch.int32)
+        order = torch.from_numpy(default_orders(C, N, restarts, seed)).to(torch.int32)
     elif int(restarts) < 1:
         raise _native.GnnppError('restarts must be >= 1 (got %d)' % restarts)
     R = 1 if order is None else int(order.shape[1])
@@ -157,7 +227,10 @@ def solve(grids, starts, goals, device, max_steps=None, restarts=1, priorities=N
     grid = g.to(torch.uint8).contiguous().to(dev)
     start, goal = start.contiguous().to(dev), goal.contiguous().to(dev)
     order = order.contiguous().to(dev) if order is not None else None
-    out = empty_solutions(C, N, H, T, dev, R)
+    if team:
+        out = empty_solutions(C, N, H, T, dev, R, W=W, team=True, workspace_bytes=workspace_bytes)
+    else:
+        out = empty_solutions(C, N, H, T, dev, R)
     out._keep = (grid, start, goal, order)              # inputs of the enqueued launches
-    enqueue_solve(grid, start, goal, order, out)
+    enqueue_solve(grid, start, goal, order, out, _team=team)
     return out

@@ -604,6 +604,22 @@ typedef struct gnnpp_mapf {
 size_t gnnpp_mapf_workspace_bytes(int C, int R, int H, int T_max);   /* 0 on invalid arguments */
 int gnnpp_mapf_solve(const gnnpp_mapf* m, void* stream);
 
+/* The same solver for large maps and teams: the same struct, the same contract and the same outputs, computed by one
+ * workgroup per (case, restart) instead of one wave (a map row is ceil(W / 64) words, one thread per word).  For every
+ * case BOTH calls accept, every output of the two calls is identical.
+ * Limits: 1 <= N <= GNNPP_ROLLOUT_MAX_TEAM, R >= 1, 0 <= T_max <= GNNPP_MAPF_TEAM_MAX_STEPS (GNNPP_ERR_ARG);
+ * H, W <= GNNPP_MAPF_TEAM_MAX_SIDE, else GNNPP_ERR_UNSUPPORTED (checked in this order, then the workspace).
+ * workspace: a summary of C * R items followed by slots of (T_max + 1) * 6 * H * ceil(W / 64) 64-bit words, one per
+ * concurrently planned item.  gnnpp_mapf_team_workspace_bytes returns the size for min(C * R, 256) slots (one workgroup
+ * per compute unit at most).  The call accepts any buffer that holds the summary and at least ONE slot and runs
+ * min(C * R, 256, slots that fit) workgroups (a full set for 256 x 256 maps at T_max = 2048 would be 25 GB); the outputs
+ * do not depend on the number of slots.  Less than one slot: GNNPP_ERR_ARG.  Nothing is enqueued on an error. */
+#define GNNPP_MAPF_TEAM_MAX_SIDE  256   /* a map row is up to four 64-bit words, a map up to 1024 threads           */
+#define GNNPP_MAPF_TEAM_MAX_STEPS 2048  /* T_max bound (the default horizon 4 (H + W) of a 256 x 256 map)           */
+
+size_t gnnpp_mapf_team_workspace_bytes(int C, int R, int H, int W, int T_max);   /* 0 on invalid arguments */
+int gnnpp_mapf_team_solve(const gnnpp_mapf* m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
-"""Time one gnnpp_mapf_solve call: cases per second and agent-plans per second.
+"""Time one gnnpp_mapf_solve / gnnpp_mapf_team_solve call: cases per second and agent-plans per second.
 
     python tools/mapf_bench.py [--reps 10] [--out profiles/mapf_solve.json] [--only NAME] [--cpu-cases 16]
+    python tools/mapf_bench.py --team [--reps 10] [--out profiles/mapf_team_solve.json] [--only NAME] [--cpu-cases 2]
 
 Configurations (random maps of tests/expert_cases.random_map at density 0.1, horizon 4 (H + W)): 512 cases x 10 agents
 on 20 x 20 with R = 1 and R = 4 orders, 256 x 20 on 20 x 20, 128 x 64 on 40 x 40.  Outputs and workspace are
@@ -8,6 +9,13 @@ preallocated; the call is timed with HIP events after 3 warm-up calls, mean over
 agent planned in one restart (C * R * N per call, whether or not the case is solved).  Beside each GPU rate: the
 sequential numpy restatement (tests/mapf_cases.py) on the first --cpu-cases cases of the same inputs, on the host, as
 context (it is the yardstick, not a tuned CPU solver).  --only NAME runs one configuration (for a profiler run).
+
+--team: mapf.solve_team's call (one workgroup per case) at the B x N shapes of the large-team rollouts -- 64 cases x 160
+agents on 64 x 64 (R = 1 and R = 4), 16 x 512 on 100 x 100, 8 x 1024 on 128 x 128 -- and, for comparison with the
+one-wave call on inputs both accept, 128 x 64 on 40 x 40 (timed through BOTH calls, outputs compared).  A case is planned
+by one workgroup from its first agent to its last, so a call lasts as long as its slowest case: us_per_step_or_hop = call
+time / (2 x the largest flowtime), the time of one forward search step or one walk-back hop (a flowtime of F means F steps
+forward and F hops back; commit, t_min scan and the per-case set-up are inside this figure, so it is an upper bound).
 """
 import argparse
 import json
@@ -24,6 +32,9 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 CONFIGS = (('c512_n10_20x20_r1', 512, 10, 20, 1), ('c512_n10_20x20_r4', 512, 10, 20, 4),
            ('c256_n20_20x20_r1', 256, 20, 20, 1), ('c128_n64_40x40_r1', 128, 64, 40, 1))
+TEAM_CONFIGS = (('team_c128_n64_40x40_r1', 128, 64, 40, 1), ('team_c64_n160_64x64_r1', 64, 160, 64, 1),
+                ('team_c64_n160_64x64_r4', 64, 160, 64, 4), ('team_c16_n512_100x100_r1', 16, 512, 100, 1),
+                ('team_c8_n1024_128x128_r1', 8, 1024, 128, 1))
 
 
 def timed(fn, reps, warmup=3):
@@ -44,14 +55,17 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--out', default=None)
     ap.add_argument('--only', default=None)
-    ap.add_argument('--cpu-cases', type=int, default=16)
+    ap.add_argument('--cpu-cases', type=int, default=None)
+    ap.add_argument('--team', action='store_true')
     a = ap.parse_args()
+    if a.cpu_cases is None:
+        a.cpu_cases = 2 if a.team else 16
     assert torch.cuda.is_available(), 'needs the MI355X: a CPU run measures nothing'
     import mapf_cases as mc
     from gnn_pathplanning_amd import mapf
     dev = torch.device('cuda:0')
     records = []
-    for name, C, N, side, R in CONFIGS:
+    for name, C, N, side, R in (TEAM_CONFIGS if a.team else CONFIGS):
         if a.only and name != a.only:
             continue
         rng = np.random.default_rng(C * N + side)
@@ -62,22 +76,40 @@ def main():
         goal = torch.from_numpy(np.stack([c[2] for c in cases]).astype(np.int32)).to(dev)
         orders = np.stack([np.stack([np.arange(N)] + [rng.permutation(N) for _ in range(R - 1)]) for _ in cases])
         order = torch.from_numpy(orders.astype(np.int32)).to(dev) if R > 1 else None
-        out = mapf.empty_solutions(C, N, side, T, dev, R)
-        sec = timed(lambda: mapf.enqueue_solve(grid, start, goal, order, out), a.reps)
+        extra = {}
+        if a.team:
+            out = mapf.empty_solutions(C, N, side, T, dev, R, W=side, team=True)
+            sec = timed(lambda: mapf.enqueue_solve_team(grid, start, goal, order, out), a.reps)
+            flow = out.flowtime.clamp(min=0)
+            extra = {'flowtime_sum': int(flow.sum().item()), 'flowtime_max': int(flow.max().item()),
+                     'us_per_step_or_hop': round(sec * 1e6 / max(1, 2 * int(flow.max().item())), 4)}
+            if N <= mapf.MAX_AGENTS and side <= mapf.MAX_SIDE:          # the one-wave call on the same inputs
+                small = mapf.empty_solutions(C, N, side, T, dev, R)
+                sec_small = timed(lambda: mapf.enqueue_solve(grid, start, goal, order, small), a.reps)
+                extra['one_wave_call_ms'] = round(sec_small * 1e3, 4)
+                extra['one_wave_call_same_outputs'] = all(
+                    torch.equal(getattr(out, k), getattr(small, k))
+                    for k in ('schedules', 'arrival', 'makespan', 'flowtime', 'status', 'failing', 'restart'))
+                del small
+        else:
+            out = mapf.empty_solutions(C, N, side, T, dev, R)
+            sec = timed(lambda: mapf.enqueue_solve(grid, start, goal, order, out), a.reps)
         solved = int((out.status == 0).sum().item())
-        k = min(a.cpu_cases, C)
+        k = min(a.cpu_cases, C, 1 if N >= 512 else C)        # (--cpu-cases 0: a profiler run, no yardstick)
         t0 = time.perf_counter()
         cpu = [mc.solve_case(g, s, gl, T, None if R == 1 else list(orders[c])) for c, (g, s, gl) in enumerate(cases[:k])]
-        cpu_sec = (time.perf_counter() - t0) / k
+        cpu_sec = (time.perf_counter() - t0) / max(k, 1)
         same = all(int(out.status[c]) == w['status'] and int(out.flowtime[c]) == w['flowtime'] for c, w in enumerate(cpu))
-        rec = {'config': name, 'what': 'gnnpp_mapf_solve, one call, HIP events, mean of %d calls after 3' % a.reps,
+        rec = {'config': name, 'what': '%s, one call, HIP events, mean of %d calls after 3' % (
+               'gnnpp_mapf_team_solve' if a.team else 'gnnpp_mapf_solve', a.reps),
                'cases': C, 'agents': N, 'map': '%dx%d' % (side, side), 'restarts': R, 'T_max': T,
                'ms_per_call': round(sec * 1e3, 4), 'cases_per_s': round(C / sec),
                'agent_plans_per_s': round(C * R * N / sec), 'solved': solved,
                'makespan_max': int(out.makespan.max().item()),
                'workspace_MB': round(out.workspace.numel() / 2 ** 20, 1),
-               'cpu_yardstick_cases_per_s': round(1 / cpu_sec, 2), 'cpu_yardstick_cases_timed': k,
+               'cpu_yardstick_cases_per_s': round(1 / cpu_sec, 2) if k else None, 'cpu_yardstick_cases_timed': k,
                'cpu_yardstick_agrees': same}
+        rec.update(extra)
         print(json.dumps(rec), flush=True)
         records.append(rec)
         del out
