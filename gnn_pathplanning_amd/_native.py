@@ -38,7 +38,8 @@ EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get
            'gnnpp_adam_step', 'gnnpp_policy_fwd', 'gnnpp_filter_head_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
            'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe', 'gnnpp_rollout_step', 'gnnpp_rollout_policy_step',
            'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples', 'gnnpp_mapf_workspace_bytes', 'gnnpp_mapf_solve',
-           'gnnpp_mapf_team_workspace_bytes', 'gnnpp_mapf_team_solve')
+           'gnnpp_mapf_team_workspace_bytes', 'gnnpp_mapf_team_solve', 'gnnpp_schedule_team_workspace_bytes',
+           'gnnpp_schedule_team_samples')
 
 
 class GnnppError(RuntimeError):
@@ -294,6 +295,10 @@ def _bind(path):
     L.gnnpp_rollout_policy_steps.restype = ci
     L.gnnpp_schedule_samples.argtypes = [ctypes.POINTER(ScheduleStruct), vp]
     L.gnnpp_schedule_samples.restype = ci
+    L.gnnpp_schedule_team_workspace_bytes.argtypes = [ci, ci]
+    L.gnnpp_schedule_team_workspace_bytes.restype = cs
+    L.gnnpp_schedule_team_samples.argtypes = [ctypes.POINTER(ScheduleStruct), vp, cs, vp]
+    L.gnnpp_schedule_team_samples.restype = ci
     L.gnnpp_mapf_workspace_bytes.argtypes = [ci] * 4
     L.gnnpp_mapf_workspace_bytes.restype = cs
     L.gnnpp_mapf_solve.argtypes = [ctypes.POINTER(MapfStruct), vp]

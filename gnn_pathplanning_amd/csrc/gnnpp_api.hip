@@ -11,6 +11,7 @@
 #include "rollout_kernels.hip"       // before the fused policy kernel, which can run the simulator step too
 #include "rollout_team_kernels.hip"  // teams of more than GNNPP_ROLLOUT_MAX_AGENTS agents
 #include "expert_kernels.hip"        // training samples from expert schedules (uses the rollout's observation / graph code)
+#include "expert_team_kernels.hip"   // ... for teams of up to GNNPP_ROLLOUT_MAX_TEAM agents (one thread per agent, row tiles of S)
 #include "mapf_kernels.hip"          // prioritized-planning MAPF solver (the expert of the online loop)
 #include "mapf_team_kernels.hip"     // ... for teams of up to 1024 agents on maps of up to 256 x 256 (one workgroup per case)
 #include "encoder_kernel_h2.hip"
@@ -598,6 +599,23 @@ int gnnpp_schedule_samples(const gnnpp_schedules* s, void* stream) {
         return GNNPP_ERR_ARG;
     if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;          // a graph of one node: deg = 0, the reference divides by it
     return schedule_samples_launch(*s, static_cast<hipStream_t>(stream));
+}
+
+size_t gnnpp_schedule_team_workspace_bytes(int N, int T_total) {
+    if (N <= 0 || N > GNNPP_ROLLOUT_MAX_TEAM || T_total <= 0) return 0;
+    return schedule_team_workspace_bytes(N, T_total);
+}
+
+// the order of gnnpp_schedule_samples' checks, with the workspace among the arguments
+int gnnpp_schedule_team_samples(const gnnpp_schedules* s, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!s || !s->grid || !s->goal || !s->pos || !s->case_start || !s->obs || !s->S || !s->target || !s->radius ||
+        !s->growth || !s->status || !s->step_info || s->C <= 0 || s->T_total <= 0 || s->C > s->T_total || s->N <= 0 ||
+        s->N > GNNPP_ROLLOUT_MAX_TEAM || s->H <= 0 || s->W <= 0 || !(s->radius0 > 0.0) || !(s->radius0 < 1e300) ||
+        !workspace || (reinterpret_cast<size_t>(workspace) & 7) != 0 ||
+        workspace_bytes < schedule_team_workspace_bytes(s->N, s->T_total))
+        return GNNPP_ERR_ARG;
+    if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;          // a graph of one node: deg = 0, the reference divides by it
+    return schedule_team_samples_launch(*s, static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 size_t gnnpp_mapf_workspace_bytes(int C, int R, int H, int T_max) {

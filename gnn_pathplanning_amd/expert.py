@@ -7,8 +7,10 @@ What the reference does with utils/multirobotsim_dcenlocal_onlineExpert.py::save
 binary, and the four-process transformer onlineExpert/DataTransformer_local_onlineExpert.py (the offline
 offlineExpert/DataGen_Transformer.py:295-371, 466-515 computes the same tensors).  The solver stays outside; everything
 around it is here.  The tensors come from ONE gnnpp_schedule_samples call for all cases (csrc/expert_kernels.hip),
-bit-exact with the reference; there is no CPU fallback.  The prioritized expert itself runs on the device too (mapf.py):
-solve_failures plans the failed episodes of a rollout and samples_from_solutions turns the solved ones into samples.
+bit-exact with the reference; there is no CPU fallback.  Teams of up to MAX_TEAM = 1024 agents go through
+samples_from_schedules_team: ONE gnnpp_schedule_team_samples call (csrc/expert_team_kernels.hip), the same tensors.
+The prioritized expert itself runs on the device too (mapf.py): solve_failures plans the failed episodes of a rollout
+and samples_from_solutions turns the solved ones into samples (team=True: teams of any size up to MAX_TEAM).
 
 The schedule's communication radius is NOT the rollout's: it starts at commR (5 in both transformers), grows by
 * 1.1 until every step of the case is connected, and the final radius builds every step's graph.
@@ -23,6 +25,7 @@ import torch
 from . import _native, formats
 
 MAX_AGENTS = 128                      # GNNPP_ROLLOUT_MAX_AGENTS
+MAX_TEAM = 1024                       # GNNPP_ROLLOUT_MAX_TEAM
 BAD_MOVE, BAD_STATE, NO_RADIUS = 1, 2, 4          # GNNPP_SCHEDULE_* status bits
 
 
@@ -52,6 +55,13 @@ def enqueue_schedule_samples(grid, goal, pos, case_start, out, commR=5.0):
     [C+1] int32, all contiguous device tensors; out: a ScheduleSamples whose tensors match.  out.step_growth receives
     the raw per-step word (growths | status bits << 16) and out.status the per-case bits: the caller checks them."""
     dev = _native.require_gpu(grid, goal, pos, case_start, out.input, out.GSO, out.target)
+    s = _schedule_struct(grid, goal, pos, case_start, out, commR)
+    with _native.device_guard(dev):
+        _native.check(_native.lib().gnnpp_schedule_samples(ctypes.byref(s), _native.stream_ptr(dev)),
+                      'gnnpp_schedule_samples')
+
+
+def _schedule_struct(grid, goal, pos, case_start, out, commR):
     s = _native.ScheduleStruct()
     s.grid, s.grid_batched, s.goal, s.pos = grid.data_ptr(), int(grid.dim() == 3), goal.data_ptr(), pos.data_ptr()
     s.case_start, s.C, s.N = case_start.data_ptr(), int(goal.shape[0]), int(goal.shape[1])
@@ -61,9 +71,26 @@ def enqueue_schedule_samples(grid, goal, pos, case_start, out, commR=5.0):
     s.S64 = out.GSO64.data_ptr() if out.GSO64 is not None else None
     s.radius, s.growth, s.status = out.radius.data_ptr(), out.growth.data_ptr(), out.status.data_ptr()
     s.step_info = out.step_growth.data_ptr()
+    return s
+
+
+def enqueue_schedule_team_samples(grid, goal, pos, case_start, out, commR=5.0):
+    """enqueue_schedule_samples for teams of 2 to MAX_TEAM agents: gnnpp_schedule_team_samples alone, same arguments,
+    same outputs; out.workspace: a contiguous device tensor of at least gnnpp_schedule_team_workspace_bytes(N, T)
+    bytes (any contents)."""
+    dev = _native.require_gpu(grid, goal, pos, case_start, out.input, out.GSO, out.target, out.workspace)
+    s = _schedule_struct(grid, goal, pos, case_start, out, commR)
+    ws = out.workspace
     with _native.device_guard(dev):
-        _native.check(_native.lib().gnnpp_schedule_samples(ctypes.byref(s), _native.stream_ptr(dev)),
-                      'gnnpp_schedule_samples')
+        _native.check(_native.lib().gnnpp_schedule_team_samples(ctypes.byref(s), ws.data_ptr(),
+                                                                ws.numel() * ws.element_size(), _native.stream_ptr(dev)),
+                      'gnnpp_schedule_team_samples')
+
+
+def team_output_bytes(T_total, N, keep_fp64_gso=False):
+    """Bytes of the input, GSO and target tensors (+ the fp64 GSO) of T_total steps of N agents: 5.7 MB per step at
+    N = 1024."""
+    return T_total * N * (1452 + 4 * N + 20) + (8 * N * N * T_total if keep_fp64_gso else 0)
 
 
 def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False):
@@ -71,10 +98,23 @@ def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64
     case, agents that arrived waiting on their goal) -> ScheduleSamples.  A schedule with a move that is not one of
     the five actions, or a state off the map / on an obstacle, raises GnnppError naming the case (the reference dies
     with ValueError there); this reads the per-case status back, the only host synchronisation."""
+    return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, False)
+
+
+def samples_from_schedules_team(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False):
+    """samples_from_schedules for teams of 2 to MAX_TEAM = 1024 agents on maps of up to 65 536 cells: same arguments,
+    same ScheduleSamples (the same bytes for every team both take), same errors naming the bad case.  The outputs are
+    team_output_bytes(T, N, keep_fp64_gso) bytes; a call that would not fit the device's free memory raises GnnppError
+    with that figure before anything is allocated."""
+    return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, True)
+
+
+def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, team):
+    name = 'samples_from_schedules_team' if team else 'samples_from_schedules'
     dev = torch.device(device)
     if dev.type != 'cuda':
-        raise _native.GnnppError('samples_from_schedules needs a HIP device (no CPU fallback)')
-    _native.lib()
+        raise _native.GnnppError('%s needs a HIP device (no CPU fallback)' % name)
+    L = _native.lib()
     g = torch.as_tensor(np.asarray(grids) if not torch.is_tensor(grids) else grids)
     goal = torch.as_tensor(np.asarray(goals) if not torch.is_tensor(goals) else goals).to(torch.int32)
     C = len(schedules)
@@ -83,8 +123,9 @@ def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64
     N = int(goal.shape[1])
     if g.dim() not in (2, 3) or (g.dim() == 3 and g.shape[0] != C):
         raise _native.GnnppError('grids must be [H,W] or [C,H,W]')
-    if not 2 <= N <= MAX_AGENTS:
-        raise _native.GnnppError('teams of 2 to %d agents (got %d)' % (MAX_AGENTS, N))
+    most = MAX_TEAM if team else MAX_AGENTS
+    if not 2 <= N <= most:
+        raise _native.GnnppError('teams of 2 to %d agents (got %d)' % (most, N))
     sched = [torch.as_tensor(np.asarray(s) if not torch.is_tensor(s) else s).to(torch.int32) for s in schedules]
     for c, s in enumerate(sched):
         if s.dim() != 3 or s.shape[0] < 1 or tuple(s.shape[1:]) != (N, 2):
@@ -93,6 +134,14 @@ def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64
     for s in sched:
         bounds.append(bounds[-1] + int(s.shape[0]))
     T = bounds[-1]
+    workspace = None
+    if team:
+        need = team_output_bytes(T, N, keep_fp64_gso)
+        free = torch.cuda.mem_get_info(dev)[0]
+        if need > free:
+            raise _native.GnnppError('%s: the tensors of %d steps of %d agents take %d bytes (%.1f GB), the device has '
+                                     '%d bytes free: pass fewer cases per call' % (name, T, N, need, need / 1e9, free))
+        workspace = torch.empty(L.gnnpp_schedule_team_workspace_bytes(N, T), dtype=torch.uint8, device=dev)
     grid = g.to(torch.uint8).contiguous().to(dev)
     goal = goal.contiguous().to(dev)
     pos = torch.cat(sched, 0).contiguous().to(dev)
@@ -108,7 +157,11 @@ def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64
         status=torch.empty(C, dtype=torch.int32, device=dev),
         step_growth=torch.empty(T, dtype=torch.int32, device=dev))
     out._keep = (grid, goal, pos)                       # inputs of the enqueued launches
-    enqueue_schedule_samples(grid, goal, pos, case_start, out, commR)
+    if team:
+        out.workspace = workspace
+        enqueue_schedule_team_samples(grid, goal, pos, case_start, out, commR)
+    else:
+        enqueue_schedule_samples(grid, goal, pos, case_start, out, commR)
     out.step_growth &= 0xffff                           # (the status bits of a step live above; reported per case)
     bad = out.status.cpu()
     if bool((bad != 0).any()):
@@ -128,7 +181,8 @@ def solve_failures(rollout, results=None, **kw):
     kw: mapf.solve's max_steps, restarts, priorities, seed.  Teams of more than mapf.MAX_AGENTS agents and maps with a
     side beyond mapf.MAX_SIDE go to mapf.solve_team (which also takes workspace_bytes), everything else to mapf.solve.
     Returns mapf.Solutions of those F episodes with `.episodes` (their indices in the rollout, numpy int64 [F]), or
-    None when every episode succeeded."""
+    None when every episode succeeded.  samples_from_solutions turns them into training samples (team=True for teams
+    of more than MAX_AGENTS agents)."""
     from . import mapf
     res = rollout.results() if results is None else results
     episodes = np.nonzero(~np.asarray(res['success'], dtype=bool))[0]
@@ -143,15 +197,16 @@ def solve_failures(rollout, results=None, **kw):
     return sol
 
 
-def samples_from_solutions(solutions, grids, goals, commR=5.0):
+def samples_from_solutions(solutions, grids, goals, commR=5.0, team=False):
     """(ScheduleSamples of the solved cases of a mapf.Solutions, their case ids numpy int64 [S]) through
-    samples_from_schedules / enqueue_schedule_samples.  grids [C,H,W] or [H,W] and goals [C,N,2]: the cases' maps and
+    samples_from_schedules / enqueue_schedule_samples, or with team=True through samples_from_schedules_team (teams of
+    up to MAX_TEAM agents, what mapf.solve_team plans).  grids [C,H,W] or [H,W] and goals [C,N,2]: the cases' maps and
     goals as solve() was given them (host or device).  Unsolved cases are left out (their ids are missing from the
     list); (None, empty ids) when no case was solved."""
-    if int(solutions.arrival.shape[1]) > MAX_AGENTS:
+    if not team and int(solutions.arrival.shape[1]) > MAX_AGENTS:
         raise _native.GnnppError('samples_from_solutions: samples are built for teams of at most %d agents; these '
-                                 'solutions have %d (mapf.solve_team plans larger teams, the sample builder '
-                                 'gnnpp_schedule_samples does not take them yet)' % (MAX_AGENTS, solutions.arrival.shape[1]))
+                                 'solutions have %d (pass team=True: samples_from_schedules_team takes teams of up to '
+                                 '%d agents)' % (MAX_AGENTS, solutions.arrival.shape[1], MAX_TEAM))
     status = solutions.status.cpu().numpy()
     ids = np.nonzero(status == 0)[0]
     if len(ids) == 0:
@@ -163,7 +218,7 @@ def samples_from_solutions(solutions, grids, goals, commR=5.0):
     g = g.to(dev).index_select(0, idx) if g.dim() == 3 else g
     gl = (goals if torch.is_tensor(goals) else torch.as_tensor(np.asarray(goals))).to(dev).index_select(0, idx)
     sched = [solutions.schedules[c, :int(makespan[c]) + 1] for c in ids]
-    return samples_from_schedules(g, gl, sched, dev, commR=commR), ids
+    return (samples_from_schedules_team if team else samples_from_schedules)(g, gl, sched, dev, commR=commR), ids
 
 
 # ---- the files around the solver ---------------------------------------------------------------------

@@ -547,6 +547,22 @@ typedef struct gnnpp_schedules {
 
 int gnnpp_schedule_samples(const gnnpp_schedules* s, void* stream);
 
+/* The same samples for teams of up to GNNPP_ROLLOUT_MAX_TEAM agents: the same struct, the same contract and the same
+ * outputs, computed with one thread per agent and row tiles of S instead of one wave per step (expert_team_kernels.hip).
+ * For every call BOTH entry points accept, every output of the two is identical, step_info included.
+ * Limits: 2 <= N <= GNNPP_ROLLOUT_MAX_TEAM (N = 1: GNNPP_ERR_UNSUPPORTED, N > GNNPP_ROLLOUT_MAX_TEAM: GNNPP_ERR_ARG);
+ * H * W <= GNNPP_ROLLOUT_TEAM_MAX_CELLS (the occupancy grid lives in LDS), else GNNPP_ERR_UNSUPPORTED; NULL pointers,
+ * C > T_total, radius0 outside (0, 1e300), a workspace that is NULL, not 8-byte aligned or smaller than
+ * gnnpp_schedule_team_workspace_bytes(N, T_total): GNNPP_ERR_ARG.  The checks come before any HIP call and nothing is
+ * enqueued on an error.
+ * workspace: device memory, no initial contents: s = sqrt(1 / deg) of every agent of every step in fp64
+ * ([T_total, N]), the hand-over from the degree launch to the launches that store S by row tiles.
+ * Outputs are indexed in size_t (T_total * N * N may pass 2^31).  When N % 4 == 0 and S / S64 are 16-byte aligned the
+ * graphs are stored 16 bytes per lane; any other alignment is accepted and gives the same bytes.
+ * Five launches on `stream`, no atomics, no host synchronisation, capturable in a HIP graph. */
+size_t gnnpp_schedule_team_workspace_bytes(int N, int T_total);   /* 0 on invalid arguments */
+int gnnpp_schedule_team_samples(const gnnpp_schedules* s, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MAPF solver: prioritized planning of C cases (the reference's SIPP expert option, offlineExpert/CasesSolver.py:517-539
  * `mapf_prioritized_sipp`, a binary without source).  Per case: a grid (1 = obstacle), starts / goals [N,2] (row, col),

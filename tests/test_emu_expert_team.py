@@ -1,0 +1,281 @@
+"""CPU: gnnpp_schedule_team_samples (csrc/expert_team_kernels.hip), compiled unmodified for the host emulation, against
+what the REAL reference transformer made of teams of 130 ... 1024 agents (tests/golden/expert_schedules_team.npz),
+against gnnpp_schedule_samples on everything both accept, and against the sequential restatement
+tests/expert_cases.py::reference_samples on random cases: equality, every element."""
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import expert_cases as ec  # noqa: E402
+
+pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
+                                reason='host clang++ from ROCm not present')
+
+ERR_ARG, ERR_UNSUPPORTED = -1, -2
+BAD_MOVE, BAD_STATE = 1, 2
+OUTPUTS = ('obs', 'S', 'S64', 'target', 'radius', 'growth', 'status', 'step_info')
+
+
+class Schedules(ctypes.Structure):
+    """struct gnnpp_schedules (include/gnnpp.h)."""
+    _fields_ = [('grid', ctypes.c_void_p), ('grid_batched', ctypes.c_int), ('goal', ctypes.c_void_p),
+                ('pos', ctypes.c_void_p), ('case_start', ctypes.c_void_p), ('C', ctypes.c_int), ('N', ctypes.c_int),
+                ('H', ctypes.c_int), ('W', ctypes.c_int), ('T_total', ctypes.c_int), ('radius0', ctypes.c_double),
+                ('obs', ctypes.c_void_p), ('S', ctypes.c_void_p), ('S64', ctypes.c_void_p),
+                ('target', ctypes.c_void_p), ('radius', ctypes.c_void_p), ('growth', ctypes.c_void_p),
+                ('status', ctypes.c_void_p), ('step_info', ctypes.c_void_p)]
+
+
+def load_team_golden():
+    """[(meta, dict of arrays)] of tests/golden/expert_schedules_team.npz (tools/gen_expert_golden_team.py)."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'expert_schedules_team.npz'))
+    meta = json.loads(bytes(z['meta']).decode())
+    keys = ('grid', 'goal', 'schedule', 'input', 'GSO', 'target')
+    return [(m, {k: z['c%d_%s' % (ci, k)] for k in keys}) for ci, m in enumerate(meta)]
+
+
+@pytest.fixture(scope='module')
+def lib():
+    import emu_lib
+    L = emu_lib.load()
+    L.gnnpp_schedule_samples.argtypes = [ctypes.POINTER(Schedules), ctypes.c_void_p]
+    L.gnnpp_schedule_samples.restype = ctypes.c_int
+    L.gnnpp_schedule_team_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.gnnpp_schedule_team_workspace_bytes.restype = ctypes.c_size_t
+    L.gnnpp_schedule_team_samples.argtypes = [ctypes.POINTER(Schedules), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.gnnpp_schedule_team_samples.restype = ctypes.c_int
+    return L
+
+
+def call(lib, grids, goals, schedules, radius0=5.0, fp64=True, expect=0, poison=np.nan, team=True, workspace='exact',
+         misalign=False):
+    """One call on host arrays; outputs start out poisoned, so an element the call does not write cannot pass for one
+    it wrote.  team=False: gnnpp_schedule_samples.  workspace: 'exact' (what the library asks for), 'short' (8 bytes
+    less) or None.  misalign: S and S64 start 4 / 8 bytes past a 16-byte boundary (the scalar store path)."""
+    grid = np.ascontiguousarray(grids, dtype=np.uint8)
+    goal = np.ascontiguousarray(goals, dtype=np.int32)
+    C, N = goal.shape[:2]
+    pos = np.ascontiguousarray(np.concatenate(schedules, 0), dtype=np.int32)
+    start = np.ascontiguousarray(np.cumsum([0] + [len(s) for s in schedules]), dtype=np.int32)
+    T = int(start[-1])
+
+    def graph(dtype):
+        size = np.dtype(dtype).itemsize
+        raw = np.full(T * N * N + 32 // size, poison, dtype)
+        off = (-raw.ctypes.data % 16) // size + (1 if misalign else 0)
+        return raw[off:off + T * N * N].reshape(T, N, N)
+
+    out = {'obs': np.full((T, N, 3, 11, 11), poison, np.float32), 'S': graph(np.float32), 'S64': graph(np.float64),
+           'target': np.full((T, N, 5), poison, np.float32),
+           'radius': np.full(C, poison, np.float64), 'growth': np.full(C, -1, np.int32),
+           'status': np.full(C, -1, np.int32), 'step_info': np.full(T, -1, np.int32), 'start': start}
+    assert (out['S'].ctypes.data % 16 != 0) == misalign and (out['S64'].ctypes.data % 16 != 0) == misalign
+    s = Schedules()
+    s.grid, s.grid_batched, s.goal, s.pos = grid.ctypes.data, int(grid.ndim == 3), goal.ctypes.data, pos.ctypes.data
+    s.case_start, s.C, s.N, s.H, s.W, s.T_total = start.ctypes.data, C, N, grid.shape[-2], grid.shape[-1], T
+    s.radius0 = radius0
+    s.obs, s.S, s.target = out['obs'].ctypes.data, out['S'].ctypes.data, out['target'].ctypes.data
+    s.S64 = out['S64'].ctypes.data if fp64 else None
+    s.radius, s.growth, s.status = out['radius'].ctypes.data, out['growth'].ctypes.data, out['status'].ctypes.data
+    s.step_info = out['step_info'].ctypes.data
+    if not team:
+        assert lib.gnnpp_schedule_samples(ctypes.byref(s), None) == expect
+        return out
+    need = lib.gnnpp_schedule_team_workspace_bytes(N, T)
+    ws = np.full(max(need, 8) // 8 + 1, poison, np.float64)
+    nbytes = {'exact': need, 'short': need - 8, None: need}[workspace]
+    assert lib.gnnpp_schedule_team_samples(ctypes.byref(s), ws.ctypes.data if workspace else None, nbytes, None) == expect
+    return out
+
+
+def assert_case_equals_golden(out, c, m, g):
+    a, b = int(out['start'][c]), int(out['start'][c + 1])
+    assert out['status'][c] == 0
+    assert out['growth'][c] == m['growth']
+    assert out['radius'][c] == float.fromhex(m['radius'])
+    assert np.array_equal(out['obs'][a:b], g['input'].astype(np.float32))
+    assert np.array_equal(out['target'][a:b], g['target'].astype(np.float32))
+    assert np.array_equal(out['S64'][a:b], g['GSO'])
+    assert np.array_equal(out['S'][a:b], g['GSO'].astype(np.float32))
+    assert (out['step_info'][a:b] >> 16 == 0).all() and (out['step_info'][a:b] & 0xffff).max() == m['growth']
+
+
+def assert_same_bytes(x, y):
+    for k in OUTPUTS:
+        assert x[k].tobytes() == y[k].tobytes(), k       # (NaN poison included: the same elements are left unwritten)
+
+
+def assert_case_equals_restatement(out, c, grid, goal, sched, fp64=True):
+    want = ec.reference_samples(grid, goal, sched)
+    a, b = int(out['start'][c]), int(out['start'][c + 1])
+    assert out['status'][c] == 0 and out['radius'][c] == want['radius'] and out['growth'][c] == want['growth']
+    assert np.array_equal(out['obs'][a:b], want['input']) and np.array_equal(out['target'][a:b], want['target'])
+    assert np.array_equal(out['S'][a:b], want['GSO'].astype(np.float32))
+    if fp64:
+        assert np.array_equal(out['S64'][a:b], want['GSO'])
+    return want
+
+
+def test_team_golden_file_keeps_what_it_must():
+    gold = load_team_golden()
+    sizes = [m['N'] for m, _ in gold]
+    assert 1024 in sizes and any(n % 64 for n in sizes) and any(n % 4 for n in sizes) and min(sizes) > 128
+    assert any(m['growth'] == 0 for m, _ in gold) and any(m['growth'] >= 10 for m, _ in gold)
+
+
+@pytest.mark.parametrize('ci', range(5))
+def test_team_golden_case(lib, ci):
+    m, g = load_team_golden()[ci]
+    out = call(lib, g['grid'], g['goal'][None], [g['schedule']])
+    assert_case_equals_golden(out, 0, m, g)
+
+
+@pytest.mark.parametrize('ci', range(8))
+def test_small_team_golden_case_same_bytes_as_one_wave_call(lib, ci):
+    m, g = ec.load_golden()[ci]
+    out = call(lib, g['grid'], g['goal'][None], [g['schedule']])
+    assert_case_equals_golden(out, 0, m, g)
+    assert_same_bytes(out, call(lib, g['grid'], g['goal'][None], [g['schedule']], team=False))
+
+
+def test_ragged_cases_and_batched_maps_same_bytes_as_one_wave_call(lib):
+    """Cases of 20, 7 and 3 steps with a map each (24 agents: 16-byte stores; 10 agents: 4-byte stores)."""
+    for ci in (4, 0):
+        m, g = ec.load_golden()[ci]
+        sched = g['schedule']
+        shape = np.array(g['grid'].shape)
+        parts = [sched, (shape - 1 - sched[:7]).astype(np.int32), sched[-3:]]
+        goals = [g['goal'], (shape - 1 - sched[7]).astype(np.int32), g['goal']]
+        grids = np.stack([g['grid'], np.ascontiguousarray(g['grid'][::-1, ::-1]), g['grid']])
+        for fp64 in (False, True):
+            out = call(lib, grids, np.stack(goals), parts, fp64=fp64)
+            assert_same_bytes(out, call(lib, grids, np.stack(goals), parts, fp64=fp64, team=False))
+            assert out['status'].tolist() == [0, 0, 0]
+            if not fp64:
+                assert np.isnan(out['S64']).all()
+        assert_case_equals_golden(out, 0, m, g)
+        for c in (1, 2):
+            assert_case_equals_restatement(out, c, grids[c], goals[c], parts[c])
+
+
+def test_unaligned_graph_outputs_give_the_same_bytes(lib):
+    """S / S64 off the 16-byte boundary take the 4-byte store path: same values."""
+    m, g = load_team_golden()[0]
+    out = call(lib, g['grid'], g['goal'][None], [g['schedule']], misalign=True)
+    assert_case_equals_golden(out, 0, m, g)
+
+
+@pytest.mark.parametrize('N,side,steps', [(129, 40, 3), (130, 60, 3), (191, 50, 2), (512, 90, 2)])
+def test_random_case_against_restatement(lib, N, side, steps):
+    rng = np.random.default_rng(1000 + N)
+    grid, goal, paths = ec.random_case(rng, N, side, side, density=0.1, max_steps=steps)
+    sched = ec.schedule_of(paths, goal)
+    out = call(lib, grid, goal[None], [sched])
+    assert_case_equals_restatement(out, 0, grid, goal, sched)
+
+
+def test_cases_of_different_growths_in_one_call_without_fp64_copy(lib):
+    """A team spread over the map and one kept in a box share a call: each gets its own radius."""
+    rng = np.random.default_rng(77)
+    N, side = 132, 48
+    wide = ec.random_case(rng, N, side, side, density=0.05, max_steps=3)
+    tight = ec.random_case(rng, N, side, side, density=0.05, box=(8, 8, 20), max_steps=2)
+    scheds = [ec.schedule_of(paths, goal) for _, goal, paths in (wide, tight)]
+    out = call(lib, np.stack([wide[0], tight[0]]), np.stack([wide[1], tight[1]]), scheds, fp64=False)
+    wants = [assert_case_equals_restatement(out, c, case[0], case[1], scheds[c], fp64=False)
+             for c, case in enumerate((wide, tight))]
+    assert wants[0]['growth'] != wants[1]['growth']
+    assert np.isnan(out['S64']).all()
+    for c in (0, 1):                                    # step_info: every step's own growths, the case's the largest
+        a, b = int(out['start'][c]), int(out['start'][c + 1])
+        own = [ec.schedule_gso(scheds[c][t:t + 1])[2] for t in range(b - a)]
+        assert out['step_info'][a:b].tolist() == own
+
+
+def test_status_bits_flag_only_their_case(lib):
+    rng = np.random.default_rng(5)
+    N = 140
+    grid, goal, paths = ec.random_case(rng, N, 44, 44, density=0.1, max_steps=4)
+    sched = ec.schedule_of(paths, goal).astype(np.int32)
+    assert len(sched) == 4
+    jump = sched.copy()
+    diag = next(d for d in ([1, 1], [1, -1], [-1, 1], [-1, -1])
+                if 0 <= min(jump[2, 133] + d) and max(jump[2, 133] + d) < 44 and grid[tuple(jump[2, 133] + d)] == 0)
+    jump[3, 133] = jump[2, 133] + diag                  # a diagonal move into step 3, onto a free cell
+    stuck = sched.copy()
+    stuck[1, 70] = np.argwhere(grid != 0)[0]            # a state on an obstacle (also breaks the moves around it)
+    off = sched.copy()
+    off[0, 139] = [-1, 3]                               # a state off the map
+    off2 = sched.copy()
+    off2[2, 0] = [5, 44]
+    out = call(lib, grid, np.stack([goal] * 6), [sched, jump, stuck, off, off2, sched])
+    assert out['status'][0] == 0 and out['status'][5] == 0
+    assert out['status'][1] == BAD_MOVE
+    assert out['status'][2] & BAD_STATE and out['status'][3] & BAD_STATE and out['status'][4] & BAD_STATE
+    assert out['step_info'][3 * 4] & 0xffff == 0        # no graph search for a step with a state off the map
+    alone = call(lib, grid, goal[None], [sched])
+    assert_case_equals_restatement(alone, 0, grid, goal, sched)
+    T = len(sched)
+    for c in (0, 5):                                    # the legal cases next to them: untouched by their neighbours
+        for k in ('obs', 'S', 'S64', 'target', 'step_info'):
+            assert np.array_equal(out[k][c * T:(c + 1) * T], alone[k]), k
+        assert out['radius'][c] == alone['radius'][0] and out['growth'][c] == alone['growth'][0]
+    for c in (1, 2, 3, 4):                              # a flagged case is not built
+        for k in ('obs', 'S', 'S64', 'target'):
+            assert np.isnan(out[k][c * T:(c + 1) * T]).all(), k
+
+
+def test_argument_errors(lib):
+    m, g = ec.load_golden()[7]
+    ok = dict(grids=g['grid'], goals=g['goal'][None], schedules=[g['schedule']])
+    call(lib, **ok)
+
+    def nothing_written(out):
+        assert all(np.isnan(out[k]).all() for k in ('obs', 'S', 'S64', 'target', 'radius'))
+        assert (out['status'] == -1).all() and (out['growth'] == -1).all() and (out['step_info'] == -1).all()
+
+    one = dict(grids=g['grid'], goals=g['goal'][None, :1], schedules=[g['schedule'][:, :1]])
+    nothing_written(call(lib, expect=ERR_UNSUPPORTED, **one))
+    full = dict(grids=g['grid'], goals=np.zeros((1, 1024, 2), np.int32), schedules=[np.zeros((1, 1024, 2), np.int32)])
+    call(lib, expect=0, **full)                         # (1024 agents are taken: all on one cell, flagged or not)
+    big = dict(grids=g['grid'], goals=np.zeros((1, 1025, 2), np.int32), schedules=[np.zeros((1, 1025, 2), np.int32)])
+    assert lib.gnnpp_schedule_team_workspace_bytes(1025, 1) == 0
+    nothing_written(call(lib, expect=ERR_ARG, **big))
+    nothing_written(call(lib, radius0=0.0, expect=ERR_ARG, **ok))
+    nothing_written(call(lib, radius0=float('nan'), expect=ERR_ARG, **ok))
+    nothing_written(call(lib, radius0=1e300, expect=ERR_ARG, **ok))
+    nothing_written(call(lib, workspace='short', expect=ERR_ARG, **ok))
+    nothing_written(call(lib, workspace=None, expect=ERR_ARG, **ok))
+    limit = dict(grids=np.zeros((256, 256), np.uint8), goals=g['goal'][None], schedules=[g['schedule']])
+    assert call(lib, expect=0, **limit)['status'][0] == 0                      # the cell limit itself is taken
+    huge = dict(grids=np.zeros((256, 257), np.uint8), goals=g['goal'][None], schedules=[g['schedule']])
+    nothing_written(call(lib, expect=ERR_UNSUPPORTED, **huge))                 # the map does not fit the LDS grid
+    more_cases = dict(grids=g['grid'], goals=np.stack([g['goal']] * 2), schedules=[g['schedule'][:1]])
+    s = Schedules()
+    ws = np.zeros(64, np.float64)
+    assert lib.gnnpp_schedule_team_samples(None, ws.ctypes.data, 512, None) == ERR_ARG
+    assert lib.gnnpp_schedule_team_samples(ctypes.byref(s), ws.ctypes.data, 512, None) == ERR_ARG      # NULL pointers
+    # C > T_total: two cases, one step
+    out = {'goal': np.ascontiguousarray(more_cases['goals'], np.int32)}
+    grid = np.ascontiguousarray(g['grid'], np.uint8)
+    pos = np.ascontiguousarray(g['schedule'][:1], np.int32)
+    start = np.array([0, 1, 1], np.int32)
+    bufs = [np.full(4096, np.nan, np.float64) for _ in range(8)]
+    s.grid, s.goal, s.pos, s.case_start = grid.ctypes.data, out['goal'].ctypes.data, pos.ctypes.data, start.ctypes.data
+    s.C, s.N, s.H, s.W, s.T_total, s.radius0 = 2, 2, grid.shape[0], grid.shape[1], 1, 5.0
+    (s.obs, s.S, s.S64, s.target, s.radius, s.growth, s.status, s.step_info) = [b.ctypes.data for b in bufs]
+    assert lib.gnnpp_schedule_team_samples(ctypes.byref(s), ws.ctypes.data, 512, None) == ERR_ARG
+    assert all(np.isnan(b).all() for b in bufs)
+    assert lib.gnnpp_schedule_team_workspace_bytes(0, 5) == 0 and lib.gnnpp_schedule_team_workspace_bytes(5, 0) == 0
+    assert lib.gnnpp_schedule_team_workspace_bytes(1024, 2100) >= 1024 * 2100 * 8
+    big129 = dict(grids=g['grid'], goals=np.zeros((1, 129, 2), np.int32), schedules=[np.zeros((2, 129, 2), np.int32)])
+    call(lib, expect=ERR_ARG, team=False, **big129)     # the one-wave call keeps its limit
+    assert lib.gnnpp_version() == 330
