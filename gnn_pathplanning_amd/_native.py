@@ -39,7 +39,8 @@ EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get
            'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe', 'gnnpp_rollout_step', 'gnnpp_rollout_policy_step',
            'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples', 'gnnpp_mapf_workspace_bytes', 'gnnpp_mapf_solve',
            'gnnpp_mapf_team_workspace_bytes', 'gnnpp_mapf_team_solve', 'gnnpp_schedule_team_workspace_bytes',
-           'gnnpp_schedule_team_samples')
+           'gnnpp_schedule_team_samples', 'gnnpp_lsigf_team_workspace_bytes', 'gnnpp_lsigf_team_fwd',
+           'gnnpp_filter_head_team_fwd', 'gnnpp_policy_team_fwd')
 
 
 class GnnppError(RuntimeError):
@@ -283,6 +284,14 @@ def _bind(path):
     L.gnnpp_filter_head_fwd.argtypes = [vp] * 7 + [ci] * 8 + [vp, vp]
     L.gnnpp_filter_head_fwd.restype = ci
     L.gnnpp_decode_actions.argtypes = [vp, vp, ci, ci, vp]
+    L.gnnpp_lsigf_team_workspace_bytes.argtypes = [ci] * 6
+    L.gnnpp_lsigf_team_workspace_bytes.restype = cs
+    L.gnnpp_lsigf_team_fwd.argtypes = [vp] * 6 + [cs] + [ci] * 11 + [vp]
+    L.gnnpp_lsigf_team_fwd.restype = ci
+    L.gnnpp_filter_head_team_fwd.argtypes = [vp] * 8 + [cs] + [ci] * 8 + [vp]
+    L.gnnpp_filter_head_team_fwd.restype = ci
+    L.gnnpp_policy_team_fwd.argtypes = [vp] * 9 + [ci] * 6 + [vp, vp, vp, cs]
+    L.gnnpp_policy_team_fwd.restype = ci
     L.gnnpp_filter_head_mode.argtypes = [ci, ci, ci, ci]
     L.gnnpp_filter_head_mode.restype = ci
     for f in ('gnnpp_rollout_observe', 'gnnpp_rollout_gso', 'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe',

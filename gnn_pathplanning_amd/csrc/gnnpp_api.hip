@@ -19,6 +19,7 @@
 #include "lsigf_kernel.hip"
 #include "policy_filter_kernel.hip"
 #include "lsigf_small_kernel.hip"
+#include "lsigf_team_kernel.hip"   // forward filter / head / policy step for graphs of up to 1024 nodes, spread over workgroups
 #include "train_encoder.hip"
 #include "train_ops.hip"
 
@@ -215,6 +216,69 @@ int gnnpp_filter_head_fwd(const float* x, const void* S, const float* packed, co
     a.s_is_f64 = s_is_f64; a.s_batched = 1; a.x_node_major = 1; a.y_node_major = 1; a.relu = 1;
     a.range_flag = range_flag; a.prec = precision;
     return lsigf_launch(a, static_cast<hipStream_t>(stream));
+}
+
+size_t gnnpp_lsigf_team_workspace_bytes(int B, int N, int G, int K, int E, int s_batched) {
+    if (B <= 0 || N <= 0 || N > GNNPP_ROLLOUT_MAX_TEAM || G <= 0 || G > 128 || K <= 0 || E <= 0) return 0;
+    return team_layout(B, N, G, K, E, s_batched).total;
+}
+
+// Validation shared by the three team calls: GNNPP_OK when the launch sequence may be enqueued.
+static int team_check(const void* x, const void* S, const void* packed, const void* workspace, size_t workspace_bytes,
+                      int B, int N, int G, int F, int K, int E, int s_batched, int precision) {
+    if (!x || !packed || !workspace || B <= 0 || N <= 0 || G <= 0 || F <= 0 || K <= 0 || E <= 0 || precision < 0 ||
+        precision > 2 || N > GNNPP_ROLLOUT_MAX_TEAM)
+        return GNNPP_ERR_ARG;
+    if (K > 1 && !S) return GNNPP_ERR_ARG;
+    if (G > 128 || F > 128 || precision == GNNPP_PREC_SPLIT_F16) return GNNPP_ERR_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) || workspace_bytes < team_layout(B, N, G, K, E, s_batched).total)
+        return GNNPP_ERR_ARG;
+    return GNNPP_OK;
+}
+
+int gnnpp_lsigf_team_fwd(const float* x, const void* S, const float* packed, const float* bias, float* y,
+                         void* workspace, size_t workspace_bytes, int B, int N, int G, int F, int K, int E,
+                         int s_is_f64, int s_batched, int relu, int bias_per_node, int precision, void* stream) {
+    if (!y) return GNNPP_ERR_ARG;
+    const int rc = team_check(x, S, packed, workspace, workspace_bytes, B, N, G, F, K, E, s_batched, precision);
+    if (rc) return rc;
+    TeamArgs a = {};
+    a.x = x; a.S = S; a.wpk = packed; a.bias = bias; a.y = y;
+    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
+    a.s_is_f64 = s_is_f64; a.s_batched = s_batched != 0; a.relu = relu; a.bias_per_node = bias && bias_per_node;
+    return team_launch(a, workspace, precision, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_filter_head_team_fwd(const float* x, const void* S, const float* packed, const float* bias,
+                               const float* act_w, const float* act_b, float* logits, void* workspace,
+                               size_t workspace_bytes, int B, int N, int G, int F, int K, int E,
+                               int s_is_f64, int precision, void* stream) {
+    if (!act_w || !act_b || !logits) return GNNPP_ERR_ARG;
+    const int rc = team_check(x, S, packed, workspace, workspace_bytes, B, N, G, F, K, E, 1, precision);
+    if (rc) return rc;
+    TeamArgs a = {};
+    a.x = x; a.S = S; a.wpk = packed; a.bias = bias; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
+    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
+    a.s_is_f64 = s_is_f64; a.s_batched = 1; a.relu = 1;
+    return team_launch(a, workspace, precision, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_policy_team_fwd(const float* obs, const void* S, const float* enc_packed, const float* filt_packed,
+                          const float* gf_bias, const float* act_w, const float* act_b, float* feat_ws,
+                          float* logits, int B, int N, int K, int E, int s_is_f64, int precision,
+                          int* range_flag, void* stream, void* workspace, size_t workspace_bytes) {
+    if (!obs || !enc_packed || !act_w || !act_b || !logits) return GNNPP_ERR_ARG;
+    int rc = team_check(feat_ws, S, filt_packed, workspace, workspace_bytes, B, N, GNNPP_FEAT, GNNPP_FEAT, K, E, 1,
+                        precision);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = encoder_launch(obs, enc_packed, feat_ws, B * N, range_flag, precision, st);
+    if (rc) return rc;
+    TeamArgs a = {};
+    a.x = feat_ws; a.S = S; a.wpk = filt_packed; a.bias = gf_bias; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
+    a.B = B; a.N = N; a.G = GNNPP_FEAT; a.F = GNNPP_FEAT; a.K = K; a.E = E;
+    a.s_is_f64 = s_is_f64; a.s_batched = 1; a.relu = 1;
+    return team_launch(a, workspace, precision, st);
 }
 
 int gnnpp_filter_head_mode(int B, int N, int K, int precision) {

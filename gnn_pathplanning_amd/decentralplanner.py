@@ -321,9 +321,15 @@ class DecentralPlannerNet(nn.Module):
         self.F = [_FEATURES] + widths
         self.E = int(getattr(self.config, 'numEdgeFeatures', 1))
         self.bias = True
+        # Optional config field `largeGraphFilter`: how the eval-mode, no-grad forward treats teams of more than
+        # graphML.MAX_NODES agents -- 'dense' (default: exact fp32 GEMMs over the dense GSO) or 'lists' (the team
+        # kernels: neighbour lists, the graph spread over workgroups; _forward_eval).  Training, inputs that require
+        # grad and precision='split_f16' keep the dense form under either value.
+        self.largeGraphFilter = gml.large_graph_filter(getattr(self.config, 'largeGraphFilter', None))
         gfl = []
         for l in range(self.L):
-            gfl += [gml.GraphFilterBatch(self.F[l], self.F[l + 1], self.K[l], self.E, self.bias),
+            gfl += [gml.GraphFilterBatch(self.F[l], self.F[l + 1], self.K[l], self.E, self.bias,
+                                         largeGraphFilter=self.largeGraphFilter),
                     nn.ReLU(inplace=True)]
         self.GFL = nn.Sequential(*gfl)
         self.actionsMLP = nn.Sequential(nn.Linear(self.F[-1], _ACTIONS, bias=True))
@@ -562,6 +568,8 @@ class DecentralPlannerNet(nn.Module):
         K = _native.PackCache.key_of
         keys = (K(enc_t), K(head)) + tuple(K((gf.weight,)) for gf in gfs)
         bufs = (self._enc_cache.buf, self._head_cache.buf) + tuple(gf._packed.buf for gf in gfs)
+        if self.largeGraphFilter == 'lists':               # the team calls' workspaces are baked into a graph like the packs
+            bufs += tuple(gml._team_ws.values())
         return keys, bufs
 
     def forward_logits(self, inputTensor, _slot=None):
@@ -600,6 +608,8 @@ class DecentralPlannerNet(nn.Module):
         enc = self.packed_encoder()
         gfs, act = self._mods
         dev = _native.require_gpu(obs, S, gfs[0].weight, act.weight)
+        if Ns > gml.MAX_NODES and self.largeGraphFilter == 'lists' and prec != _native.PREC_SPLIT_F16:
+            return self._forward_eval_team(obs, S, B, N, Ns, prec, slot, enc, gfs, act, dev)
         if Ns > gml.MAX_NODES:
             # larger graphs than one workgroup's LDS holds: encoder kernel, then every filter layer as dense
             # exact-fp32 GEMMs (graphML._lsigf_large) and the head as one small library GEMM
@@ -665,6 +675,64 @@ class DecentralPlannerNet(nn.Module):
         # last layer wider than 128 features: the 5-row head is one small library GEMM
         out = torch.nn.functional.linear(x[:, :N], act.weight.detach().float(), act.bias.detach().float())
         return out.permute(1, 0, 2).contiguous()
+
+    def _feat_workspace(self, rows, st, dev):
+        """Feature workspace between the encoder and the filter kernels: one per (rows, stream)."""
+        wkey = (rows, st.value)
+        if self._ws is None or self._ws_key != wkey or self._ws.device != dev:
+            if wkey not in self._ws_all or self._ws_all[wkey].device != dev:
+                if len(self._ws_all) > 16:
+                    self._ws_all.clear()
+                self._ws_all[wkey] = torch.empty(rows, 128, dtype=torch.float32, device=dev)
+            self._ws, self._ws_key = self._ws_all[wkey], wkey
+        return self._ws
+
+    def _forward_eval_team(self, obs, S, B, N, Ns, prec, slot, enc, gfs, act, dev):
+        """largeGraphFilter='lists' on a team of more than graphML.MAX_NODES agents: the team kernels
+        (csrc/lsigf_team_kernel.hip).  The reference's planner (one layer, 128 features, GSO of numAgents nodes) is ONE
+        gnnpp_policy_team_fwd call; anything else runs the encoder, one gnnpp_lsigf_team_fwd per layer and
+        gnnpp_filter_head_team_fwd for the last.  What those calls do not serve raises GnnppError: nothing falls back."""
+        if Ns > gml.TEAM_MAX_NODES or any(gf.G > 128 or gf.F > 128 for gf in gfs):
+            raise _native.GnnppError("largeGraphFilter='lists' serves graphs of up to %d nodes and layers of up to 128 "
+                                     "features (this planner: %d nodes, widths %s); use largeGraphFilter='dense'"
+                                     % (gml.TEAM_MAX_NODES, Ns, self.F))
+        L = _native.lib()
+        s64 = int(S.dtype is torch.float64)
+        gl = gfs[-1]
+        gb_p, aw_p, ab_p, _keep = self._head_cache.get(
+            (gl.bias, act.weight, act.bias) if gl.bias is not None else (act.weight, act.bias),
+            lambda: self._head_pointers(gl, act))
+        with _native.device_guard(dev):
+            st = _native.stream_ptr(dev)
+            if self.L == 1 and Ns == N and gl.F == 128:
+                feat = self._feat_workspace(B * N, st, dev)
+                ws = gml.team_workspace(B, N, 128, gl.K, self.E, True, dev, st.value)
+                logits = (torch.empty(N, B, 5, dtype=torch.float32, device=dev) if slot is None
+                          else slot.acquire(N, B, dev, st.value))
+                rc = L.gnnpp_policy_team_fwd(obs.data_ptr(), S.data_ptr(), enc.data_ptr(), gl.packed_taps().data_ptr(),
+                                             gb_p, aw_p, ab_p, feat.data_ptr(), logits.data_ptr(), B, N, gl.K, self.E,
+                                             s64, prec, None, st, ws.data_ptr(), ws.numel())
+                _native.check(rc, 'gnnpp_policy_team_fwd')
+                return logits
+            x = self.encode(obs, prec)
+            if Ns != N:                                    # zero features on the GSO's extra nodes, outputs dropped
+                xp = torch.zeros(B, Ns, 128, dtype=torch.float32, device=dev)
+                xp[:, :N] = x
+                x = xp
+            for l, gf in enumerate(gfs):
+                if l < self.L - 1:
+                    x = gml.lsigf_team(gf.weight, S, x, gf.bias, relu=True, precision=prec, packed=gf.packed_taps())
+                    if Ns != N:                            # every layer zero-pads its input again (graphML.py:2464-2476)
+                        x[:, N:].zero_()
+                    continue
+                bias = gf.bias.detach().reshape(-1).contiguous().float() if gf.bias is not None else None
+                ws = gml.team_workspace(B, Ns, gf.G, gf.K, self.E, True, dev, st.value)
+                logits = torch.empty(Ns, B, 5, dtype=torch.float32, device=dev)
+                rc = L.gnnpp_filter_head_team_fwd(_ptr(x), _ptr(S), _ptr(gf.packed_taps()), _ptr(bias), aw_p, ab_p,
+                                                  _ptr(logits), _ptr(ws), ws.numel(), B, Ns, gf.G, gf.F, gf.K, self.E,
+                                                  s64, prec, st)
+                _native.check(rc, 'gnnpp_filter_head_team_fwd')
+                return logits[:N] if Ns != N else logits
 
     def _forward_train(self, inputTensor):
         """Differentiable train-mode forward with the reference's semantics (decentralplanner.py:278-318).

@@ -77,6 +77,72 @@ def _bias_arg(b, F_out, N):
     return b.detach().contiguous().float(), 1
 
 
+# How an eval-mode, no-grad filter call treats graphs of more than MAX_NODES nodes: 'dense' (default) = _lsigf_large
+# (exact fp32 GEMMs over the dense S), 'lists' = lsigf_team (neighbour lists, the graph spread over workgroups; G, F <=
+# 128, not split-f16).  The two round differently, which is why the default stays.  Training always takes the dense form.
+LARGE_GRAPH_FILTERS = ('dense', 'lists')
+TEAM_MAX_NODES = 1024   # GNNPP_ROLLOUT_MAX_TEAM
+
+
+def large_graph_filter(name):
+    name = 'dense' if name is None else name
+    if name not in LARGE_GRAPH_FILTERS:
+        raise _native.GnnppError('unknown largeGraphFilter %r (one of %s)' % (name, list(LARGE_GRAPH_FILTERS)))
+    return name
+
+
+_team_ws = {}                 # (B, N, G, K, E, batched, device index, stream) -> workspace of the team calls
+
+
+def team_workspace(B, N, G, K, E, batched, dev, stream):
+    """The workspace of gnnpp_lsigf_team_fwd / _filter_head_team_fwd / _policy_team_fwd (neighbour lists + tap signals),
+    one per (shape, stream): calls on different streams may be in flight together."""
+    key = (B, N, G, K, E, bool(batched), dev.index, stream)
+    ws = _team_ws.get(key)
+    if ws is None:
+        nbytes = _native.lib().gnnpp_lsigf_team_workspace_bytes(B, N, G, K, E, int(bool(batched)))
+        if nbytes == 0:
+            raise _native.GnnppError('the team filter kernels do not serve N=%d nodes, G=%d features (N <= %d, G <= 128)'
+                                     % (N, G, TEAM_MAX_NODES))
+        if len(_team_ws) > 16:
+            _team_ws.clear()
+        ws = _team_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def lsigf_team(h, S, x, b, relu=False, precision=None, workspace=None, packed=None):
+    """The forward filter on neighbour lists for graphs of up to TEAM_MAX_NODES nodes (gnnpp_lsigf_team_fwd), node-major:
+    h [F,E,K,G], S [B,E,N,N] | [E,N,N] (fp32 or fp64), x [B,N,G], b [F,1] | [F,N] | None -> [B,N,F].  No autograd.
+    workspace: a uint8 device tensor of gnnpp_lsigf_team_workspace_bytes (None: cached per shape and stream).
+    G or F > 128 and precision='split_f16' raise GnnppError: there is no fallback behind this call."""
+    dev = _native.require_gpu(h, S, x, b)
+    L = _native.lib()
+    precision = _native.precision_code(DEFAULT_PRECISION if precision is None else precision)
+    F_out, E, K, G = h.shape
+    B, N = x.shape[0], x.shape[1]
+    batched = S.dim() == 4
+    assert x.shape[2] == G and S.shape[-1] == N and S.shape[-2] == N and S.shape[-3] == E
+    assert not batched or S.shape[0] == B
+    xc = x.detach().contiguous()
+    if xc.dtype != torch.float32:
+        xc = xc.float()
+    Sc = S.detach().contiguous()
+    if Sc.dtype not in (torch.float32, torch.float64):
+        Sc = Sc.float()
+    if packed is None:
+        packed = pack_filter_taps(h)
+    bias, per_node = _bias_arg(b, F_out, N)
+    y = torch.empty(B, N, F_out, dtype=torch.float32, device=dev)
+    with _native.device_guard(dev):
+        st = _native.stream_ptr(dev)
+        ws = workspace if workspace is not None else team_workspace(B, N, G, K, E, batched, dev, st.value)
+        rc = L.gnnpp_lsigf_team_fwd(_ptr(xc), _ptr(Sc), _ptr(packed), _ptr(bias), _ptr(y), _ptr(ws), ws.numel(), B, N,
+                                    G, F_out, K, E, int(Sc.dtype == torch.float64), int(batched), int(relu), per_node,
+                                    int(precision), st)
+    _native.check(rc, 'gnnpp_lsigf_team_fwd')
+    return y
+
+
 def _large_tap_signals(h, S, x, batched):
     """Z [B,N,E*K,G]: every tap signal z_{e,k} = S_e^T z_{e,k-1} of a node-major x [B,N,G], one gnnpp_gemm_kmajor call per
     (e, k >= 1) over the batch; and the fp32 GSO it used."""
@@ -153,7 +219,7 @@ def _lsigf_large_backward(h, S32, Z, dy, batched, need_dh, need_dx):
 
 
 def _lsigf_device(h, S, x, b, batched, Nin, packed=None, relu=False, transposed=False,
-                  save_taps=False, node_major=False, precision=None, out_mask=None):
+                  save_taps=False, node_major=False, precision=None, out_mask=None, large='dense'):
     """Shared driver: h [F,E,K,G], S [E,N,N] | [B,E,N,N], x [B,G,Nin] -> y [B,F,Nin]
     (and, with save_taps, zs [E*K, B*N, G]).  Any F: the C entry point splits wide filters.
     node_major: x [B,N,G] -> y [B,N,F] (rows = nodes, the layout the kernel keeps in LDS anyway).
@@ -170,11 +236,17 @@ def _lsigf_device(h, S, x, b, batched, Nin, packed=None, relu=False, transposed=
         if transposed or save_taps:
             raise _native.GnnppError('graphs with N=%d > %d nodes: the LDS-resident kernels do not apply '
                                      '(training goes through _LSIGFFunction\'s dense path)' % (N, MAX_NODES))
+        # large='lists': the team kernels -- except under split-f16, which keeps the dense form; a shape they do not
+        # serve (G or F > 128, N > TEAM_MAX_NODES) is an error there, not a silent change of route
+        if large == 'lists' and precision != _native.PREC_SPLIT_F16:
+            filt = lambda xn: lsigf_team(h, S, xn, b, relu, precision, packed=packed)      # noqa: E731
+        else:
+            filt = lambda xn: _lsigf_large(h, S, xn, b, batched, relu)                     # noqa: E731
         if node_major:
-            return _lsigf_large(h, S, x, b, batched, relu)
+            return filt(x)
         xn = torch.zeros(B, N, G, dtype=torch.float32, device=dev)                 # zero padding of missing nodes
         xn[:, :Nin] = x.detach().permute(0, 2, 1)
-        return _lsigf_large(h, S, xn, b, batched, relu)[:, :Nin].permute(0, 2, 1).contiguous()
+        return filt(xn)[:, :Nin].permute(0, 2, 1).contiguous()
     xc = x.detach().contiguous()
     if xc.dtype != torch.float32:
         xc = xc.float()
@@ -450,8 +522,10 @@ def BatchLSIGF(h, S, x, b=None, precision=None):
 class _GraphFilterBase(nn.Module):
     _batched = False
 
-    def __init__(self, G, F, K, E=1, bias=True, precision=None):
+    def __init__(self, G, F, K, E=1, bias=True, precision=None, largeGraphFilter=None):
         super().__init__()
+        # eval-mode, no-grad calls on graphs of more than MAX_NODES nodes: 'dense' (default) | 'lists' (LARGE_GRAPH_FILTERS)
+        self.largeGraphFilter = large_graph_filter(largeGraphFilter)
         self.G = G
         self.F = F
         self.K = K
@@ -498,7 +572,7 @@ class _GraphFilterBase(nn.Module):
             return _LSIGFFunction.apply(self.weight, self.S, x, self.bias, self._batched,
                                         self.packed_taps(), False, False, self.precision)
         return _lsigf_device(self.weight, self.S, x, self.bias, self._batched, Nin,
-                             packed=self.packed_taps(), precision=self.precision)
+                             packed=self.packed_taps(), precision=self.precision, large=self.largeGraphFilter)
 
     def forward_node_major(self, x, relu=False, packed=None, packed_T=None, fold=0):
         """The same filter on x [B,N,G] -> [B,N,F] (rows = nodes; optionally followed by ReLU in the same launch),

@@ -64,7 +64,9 @@ extern "C" {
                                         G / F), else GNNPP_ERR_UNSUPPORTED.  Larger graphs: the same
                                         filter as dense GEMMs, one gnnpp_gemm_kmajor call per shift
                                         (A = S with strides (1, N), B = z_{k-1}) and one for the tap
-                                        contraction -- what graphML._lsigf_large does              */
+                                        contraction -- what graphML._lsigf_large does --, or, forward
+                                        only and up to GNNPP_ROLLOUT_MAX_TEAM nodes, the gnnpp_*_team_fwd
+                                        calls below, which spread a graph over many workgroups        */
 
 int         gnnpp_version(void);
 const char* gnnpp_error_string(int code);
@@ -406,6 +408,45 @@ int gnnpp_filter_head_mode(int B, int N, int K, int precision);
  * then argmax == argmax of the logits, first maximum wins like torch.max).
  * logits [N,B,5] -> actions [B,N] int32. */
 int gnnpp_decode_actions(const float* logits, int* actions, int B, int N, void* stream);
+
+/* The forward filter, the filter + ReLU + action head and the policy step for TEAM graphs: 1 <= N <=
+ * GNNPP_ROLLOUT_MAX_TEAM (1024) nodes, the sizes gnnpp_rollout_*, gnnpp_expert_samples_team and gnnpp_mapf_team run
+ * (csrc/lsigf_team_kernel.hip).  The function is that of gnnpp_lsigf_fwd / gnnpp_filter_head_fwd / gnnpp_policy_fwd
+ * (z_k = z_{k-1} S: node n gathers from the non-zeros of COLUMN n), at any N in range -- not only beyond GNNPP_MAX_ROWS.
+ * A graph is spread over many workgroups: one launch turns the dense S into per-column neighbour lists, one launch
+ * per tap k = 1 .. K-2 shifts the signal through them (exact fp32, ascending row order), the last launch fuses the
+ * last shift with the tap contraction, bias, ReLU and the store (or the action head).
+ *   x [B,N,G] and y [B,N,F] node-major only (Nin == N: the caller zero-pads); logits [N,B,5];
+ *   packed: what gnnpp_filter_pack wrote; bias [F], [F,N] (bias_per_node) or NULL;
+ *   S fp32 or fp64 (s_is_f64), [B,E,N,N] (s_batched) or [E,N,N], any values, symmetric or not; NULL allowed at K = 1;
+ *   1 <= G, F <= 128 (any value), K >= 1, E >= 1; gnnpp_policy_team_fwd: G = F = 128, S batched;
+ *   precision: GNNPP_PREC_FP32 (bf16x3 planes, six products on v_mfma_f32_16x16x32_bf16) or GNNPP_PREC_FP32_MFMA;
+ *     GNNPP_PREC_SPLIT_F16 returns GNNPP_ERR_UNSUPPORTED (gnnpp_policy_team_fwd keeps `range_flag` for the day it
+ *     does not; it is never written);
+ *   workspace: gnnpp_lsigf_team_workspace_bytes(B, N, G, K, E, s_batched) bytes (0 for arguments out of range),
+ *     16-byte aligned, not NULL, not overlapping x / y / logits; its content is scratch.  Layout, every region 16-byte
+ *     aligned, graphs = (s_batched ? B : 1) * E, Np = N rounded up to 4, Gz = G rounded up to 4:
+ *       int32 cnt [graphs][N] | uint16 idx [graphs][N][Np] | fp32 val [graphs][N][Np]   (K > 1: the dense worst case,
+ *       so the host never needs a degree) | fp32 z [E][K-2][B][N][Gz]   (K > 2).
+ * Errors: N > GNNPP_ROLLOUT_MAX_TEAM, NULL pointers, non-positive sizes, a precision outside 0 .. 2, a workspace that
+ * is too small or misaligned: GNNPP_ERR_ARG.  G or F > 128, split-f16: GNNPP_ERR_UNSUPPORTED.  On any error nothing is
+ * enqueued and nothing is written.
+ * No allocation, no host synchronisation, no atomics; every output and workspace element has one writer (two calls
+ * give the same bytes); capturable in a HIP graph. */
+size_t gnnpp_lsigf_team_workspace_bytes(int B, int N, int G, int K, int E, int s_batched);
+int gnnpp_lsigf_team_fwd(const float* x, const void* S, const float* packed, const float* bias, float* y,
+                         void* workspace, size_t workspace_bytes, int B, int N, int G, int F, int K, int E,
+                         int s_is_f64, int s_batched, int relu, int bias_per_node, int precision, void* stream);
+int gnnpp_filter_head_team_fwd(const float* x, const void* S, const float* packed, const float* bias,
+                               const float* act_w, const float* act_b, float* logits, void* workspace,
+                               size_t workspace_bytes, int B, int N, int G, int F, int K, int E,
+                               int s_is_f64, int precision, void* stream);
+/* gnnpp_policy_fwd's arguments, then the workspace (sized for G = 128, s_batched = 1): the encoder launch into
+ * feat_ws [B*N,128], then the three steps above with the action head. */
+int gnnpp_policy_team_fwd(const float* obs, const void* S, const float* enc_packed, const float* filt_packed,
+                          const float* gf_bias, const float* act_w, const float* act_b, float* feat_ws,
+                          float* logits, int B, int N, int K, int E, int s_is_f64, int precision,
+                          int* range_flag, void* stream, void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * Batched rollout step around the forward (B independent episodes resident on the device):
