@@ -616,7 +616,9 @@ class DecentralPlannerNet(nn.Module):
             x = self.encode(obs, prec)
             if Ns != N:
                 x = torch.cat([x, x.new_zeros(B, Ns - N, x.shape[2])], 1)
-            for gf in gfs:
+            for l, gf in enumerate(gfs):
+                if l and Ns != N:                          # every layer zero-pads its input again (graphML.py:2464-2476)
+                    x[:, N:].zero_()
                 x = gml._lsigf_large(gf.weight, S, x, gf.bias, True, relu=True)
             out = torch.nn.functional.linear(x[:, :N], act.weight.detach().float(), act.bias.detach().float())
             return out.permute(1, 0, 2).contiguous()
@@ -650,7 +652,7 @@ class DecentralPlannerNet(nn.Module):
                 return logits
             # general form: encoder kernel, then one filter kernel per layer (node-major in / out, bias
             # + ReLU fused), the last one with the action head.  A GSO larger than numAgents carries
-            # zero features on the extra nodes, whose outputs are dropped.
+            # zero features on the extra nodes into EVERY layer, whose outputs there are dropped.
             x = torch.zeros(B, Ns, 128, dtype=torch.float32, device=dev) if Ns != N else None
             feat = self.encode(obs, prec)
             if x is not None:
@@ -671,6 +673,8 @@ class DecentralPlannerNet(nn.Module):
                 rc = L.gnnpp_lsigf_fwd(_ptr(x), _ptr(S), _ptr(gf.packed_taps()), _ptr(bias), _ptr(y),
                                        B, Ns, Ns, gf.G, gf.F, gf.K, self.E, s64, 1, 1, 1, 1, 0, prec, flag, st)
                 _native.check(rc, 'gnnpp_lsigf_fwd')
+                if Ns != N and not last:                   # every layer zero-pads its input again (graphML.py:2464-2476)
+                    y[:, N:].zero_()
                 x = y
         # last layer wider than 128 features: the 5-row head is one small library GEMM
         out = torch.nn.functional.linear(x[:, :N], act.weight.detach().float(), act.bias.detach().float())
@@ -744,7 +748,8 @@ class DecentralPlannerNet(nn.Module):
         their backward products on gnnpp_gemm_kmajor_multi; every weight re-ordering of the step in one
         gnnpp_train_pack launch per weight version; both ReLU backward passes around the filter folded into the
         launches that produce the masked gradients.  No library GEMM and no aten kernel is left in the step (r06).  A
-        GSO with more nodes than numAgents (graphML.py:2464-2469 zero-pads the signal) is honoured as in eval mode."""
+        GSO with more nodes than numAgents (graphML.py:2464-2476: every layer zero-pads its input and drops the extra
+        nodes' outputs) is honoured as in eval mode."""
         if self.S is None:
             raise TypeError('addGSO() must be called before forward()')
         _native.require_gpu(inputTensor, self.S, self.compressMLP[0].weight)
@@ -776,18 +781,18 @@ class DecentralPlannerNet(nn.Module):
         direct = Ns == N and Ns <= gml.MAX_NODES
         # (`direct`: the head's and the filter's parameter-gradient products wait for the compress layer's backward launch)
         x = _LinearFunction.apply(feat, fc.weight, fc.bias, 2 if direct else 1, False, 2 if direct else 0)   # [B,N,F]
-        if Ns != N:                                # Nin < N: zero signal on the extra nodes (graphML.py:2464-2469)
-            x = torch.cat([x, x.new_zeros(B, Ns - N, x.shape[2])], 1)
         # every activation stays node-major [B,N,*] (the layout the filter kernel keeps in LDS): no transposing
         # copy between encoder, filter layers and head; each GFL ReLU runs inside its filter launch
         for l in range(self.L):
             gf = self.GFL[2 * l]
             gf.addGSO(self.S)
+            if Ns != N:                            # Nin < N: EVERY layer puts a zero signal on the extra nodes
+                x = torch.cat([x, x.new_zeros(B, Ns - N, x.shape[2])], 1)         # (graphML.py:2464-2469) ...
             fold = ((2 if l == 0 else 0) | (1 if l == self.L - 1 else 0)) if direct else 0
             x = gf.forward_node_major(x, relu=True, packed=packs[1] if packs else None,
                                       packed_T=packs[2] if packs else None, fold=fold | (4 if direct else 0))  # [B,Ns,F_l]
-        if Ns != N:
-            x = x[:, :N]                           # ... whose outputs are dropped (index_select, :2471-2476)
+            if Ns != N:                            # ... and drops its outputs there (index_select, :2471-2476): neither
+                x = x[:, :N]                       # an activation nor a cotangent passes them from layer to layer
         act = self.actionsMLP[0]
         return _LinearFunction.apply(x, act.weight, act.bias, 0, direct, 1 if direct else 0).permute(1, 0, 2)   # [N,B,5]
 

@@ -176,10 +176,10 @@ def test_team_rollout_run_ends_done(dev):
 
 def test_team_two_layer_two_edge_features_larger_gso(dev):
     """L = 2, E = 2, widths 64 and 48, a GSO of 150 nodes for 130 agents: per-layer gnnpp_lsigf_team_fwd and
-    gnnpp_filter_head_team_fwd through the module API, against the policy oracle.  The 'dense' route is printed, not
-    asserted: with several layers AND a GSO larger than the team it carries the first layer's outputs on the extra nodes
-    into the second layer, where the reference (graphML.py:2464-2476) and the oracle zero-pad again -- measured
-    |dense - lists| = 0.067 on these inputs, with 'lists' within 1e-4 of the oracle.  That route is left as it is here."""
+    gnnpp_filter_head_team_fwd through the module API, against the policy oracle -- and the 'dense' route on the same
+    inputs, held to the same 1e-4.  With several layers AND a GSO larger than the team every layer zero-pads its input
+    again (graphML.py:2464-2476, and the oracle): a route that carries the first layer's outputs on the extra nodes
+    into the second layer is 0.067 off on these inputs."""
     B, N, Ns = 3, 130, 150
     torch.manual_seed(5)
     cfg = dict(nGraphFilterTaps=[2, 3], dimNodeSignals=[64, 48], numEdgeFeatures=2)
@@ -203,9 +203,11 @@ def test_team_two_layer_two_edge_features_larger_gso(dev):
     assert logits.shape == (N, B, 5)
     with torch.no_grad():
         want = torch.stack(orc.policy_forward(sd, S, obs), 0)
-    err, err_d = (logits.cpu() - want).abs().max().item(), (logits - ld).abs().max().item()
-    print('|lists - oracle| = %.3g, |lists - dense| = %.3g' % (err, err_d))
+    assert ld.shape == (N, B, 5)
+    err, err_d = (logits.cpu() - want).abs().max().item(), (ld.cpu() - want).abs().max().item()
+    print('|lists - oracle| = %.3g, |dense - oracle| = %.3g' % (err, err_d))
     assert err <= 1e-4
+    assert err_d <= 1e-4
 
 
 def test_team_unserved_combinations(dev):

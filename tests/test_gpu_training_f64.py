@@ -163,16 +163,25 @@ def centre_pre_activations(sd, S, obs, N):
 
 # ---- the planner under test ----------------------------------------------------------------------------------------
 class Cfg:
-    def __init__(self, N, K, dev, L=1, E=1):
+    """K: taps of every layer, or a list of L values; widths: output features per layer (default: 128 each)."""
+
+    def __init__(self, N, K, dev, L=1, E=1, widths=None):
         self.num_agents, self.device = N, dev
-        self.nGraphFilterTaps = [K] * L if L > 1 else K
-        if L > 1:
+        if isinstance(K, (list, tuple)):
+            assert len(K) == L
+            self.nGraphFilterTaps = list(K)
+        else:
+            self.nGraphFilterTaps = [K] * L if L > 1 else K
+        if widths is not None:
+            assert len(widths) == L
+            self.dimNodeSignals = list(widths)
+        elif L > 1:
             self.dimNodeSignals = [128] * L
         self.numEdgeFeatures = E
 
 
 def make_case(B, N, K=3, L=1, E=1, Ns=None, seed=0, edge=None, fp64_gso=False, real_obs=False, tie=False,
-              margin=None):
+              margin=None, widths=None):
     """Parameters (the planner's own init + non-trivial BatchNorm state), observations, GSO and targets.
 
     margin (default: from 640 agent-samples on): keep the step's decisions away from their discontinuities.  A ReLU
@@ -184,7 +193,7 @@ def make_case(B, N, K=3, L=1, E=1, Ns=None, seed=0, edge=None, fp64_gso=False, r
     (set from the float64 forward); the small ones run in the plain regime."""
     from gnn_pathplanning_amd.decentralplanner import DecentralPlannerNet
     torch.manual_seed(seed)
-    sd = {k: v.clone() for k, v in DecentralPlannerNet(Cfg(N, K, 'cpu', L, E)).state_dict().items()}
+    sd = {k: v.clone() for k, v in DecentralPlannerNet(Cfg(N, K, 'cpu', L, E, widths)).state_dict().items()}
     g = torch.Generator().manual_seed(seed + 1)
     for li in range(5):
         bn = 'ConvLayers.%d.' % BN[li]
@@ -230,7 +239,7 @@ def make_case(B, N, K=3, L=1, E=1, Ns=None, seed=0, edge=None, fp64_gso=False, r
     return sd, obs, S, tgt
 
 
-def run_planner(dev, sd, obs, S, tgt, N, K, L, E, via_step, monkeypatch, adam=None):
+def run_planner(dev, sd, obs, S, tgt, N, K, L, E, via_step, monkeypatch, adam=None, widths=None):
     """The HIP training step: forward (encoder features captured at the autograd Function), loss, backward --
     through training.train_step() (fused loss launch, deferred parameter-gradient products, one FusedAdam step) or
     through policy_loss(...).backward()."""
@@ -242,16 +251,16 @@ def run_planner(dev, sd, obs, S, tgt, N, K, L, E, via_step, monkeypatch, adam=No
         mp.setattr(dp._EncoderTrainFunction, 'apply', lambda *a: seen.setdefault('feat', orig(*a)))
         # train_step's fused loss launch: the logits [N,B,5] it is handed
         mp.setattr(training, '_policy_loss_and_grad', lambda lg, t: (seen.setdefault('logits', lg), orig_loss(lg, t))[1])
-        res = _step(dev, dp, sd, obs, S, tgt, N, K, L, E, via_step, adam)
+        res = _step(dev, dp, sd, obs, S, tgt, N, K, L, E, via_step, adam, widths)
     res['feat'] = seen['feat'].detach().cpu()
     if via_step:
         res['logits'] = seen['logits'].detach().permute(1, 0, 2).cpu()
     return res
 
 
-def _step(dev, dp, sd, obs, S, tgt, N, K, L, E, via_step, adam):
+def _step(dev, dp, sd, obs, S, tgt, N, K, L, E, via_step, adam, widths=None):
     from gnn_pathplanning_amd.training import FusedAdam, policy_loss, train_step
-    net = dp.DecentralPlannerNet(Cfg(N, K, dev, L, E)).to(dev)
+    net = dp.DecentralPlannerNet(Cfg(N, K, dev, L, E, widths)).to(dev)
     net.load_state_dict(sd)
     net.train()
     res = {}
@@ -311,11 +320,16 @@ def check_against_f64(got, w64, w32, B, N):
 
 
 def one_case(dev, monkeypatch, B, N, K=3, L=1, E=1, Ns=None, seed=0, edge=None, fp64_gso=False, real_obs=False,
-             tie=False, via_step=True, adam=(1e-3, 1e-5, None)):
-    sd, obs, S, tgt = make_case(B, N, K, L, E, Ns, seed, edge, fp64_gso, real_obs, tie)
+             tie=False, via_step=True, adam=(1e-3, 1e-5, None), widths=None):
+    sd, obs, S, tgt = make_case(B, N, K, L, E, Ns, seed, edge, fp64_gso, real_obs, tie, widths=widths)
     w64 = statement(sd, S, obs, tgt, N, torch.float64)
     w32 = statement(sd, S, obs, tgt, N, torch.float32)
-    got = run_planner(dev, sd, obs, S, tgt, N, K, L, E, via_step, monkeypatch, adam if via_step else None)
+    got = run_planner(dev, sd, obs, S, tgt, N, K, L, E, via_step, monkeypatch, adam if via_step else None, widths)
+    # every parameter's gradient is compared -- those below the filter stack (GFL.0, compressMLP, the encoder) are the
+    # ones that change when a cotangent on the extra nodes of a larger GSO is carried from layer to layer
+    assert set(got['grads']) == set(w64['grads']) == set(w32['grads'])
+    assert {'compressMLP.0.weight', 'compressMLP.0.bias', 'actionsMLP.0.weight'} <= set(got['grads'])
+    assert {'GFL.%d.%s' % (2 * l, n) for l in range(L) for n in ('weight', 'bias')} <= set(got['grads'])
     bad = check_against_f64(got, w64, w32, B, N)
     if via_step:
         bad += check_adam(sd, got, adam)
@@ -366,12 +380,24 @@ def test_training_step_against_float64(dev, monkeypatch, B, N):
 
 @pytest.mark.parametrize('B,N,K,L,E,Ns,fp64_gso', [(5, 6, 3, 1, 1, 9, False), (6, 7, 1, 1, 1, None, False),
                                                    (6, 7, 4, 1, 1, None, True), (4, 5, 2, 1, 2, None, False),
-                                                   (4, 5, 3, 2, 1, None, False), (3, 4, 2, 2, 2, None, True)])
+                                                   (4, 5, 3, 2, 1, None, False), (3, 4, 2, 2, 2, None, True),
+                                                   (4, 5, 3, 2, 1, 8, False), (3, 4, 2, 2, 2, 7, True),
+                                                   (3, 5, 2, 3, 1, 8, False), (2, 100, 2, 2, 1, 120, False)])
 def test_planner_variants_against_float64(dev, monkeypatch, B, N, K, L, E, Ns, fp64_gso):
     """A GSO with more nodes than agents, K = 1 and 4, E = 2 edge features, two filter layers (the multilayer path
-    without the step's packed filter), an fp64 GSO; through plain policy_loss(...).backward() as well."""
+    without the step's packed filter), an fp64 GSO; through plain policy_loss(...).backward() as well.  Several layers
+    AND a larger GSO (L = 2, L = 2 with E = 2 and an fp64 GSO, L = 3, and 100 agents on 120 nodes: the dense training
+    form): every layer zero-pads its input again (graphML.py:2464-2476), so neither an activation nor a cotangent on
+    the extra nodes passes from one layer to the next -- the statement (filter_stack) re-pads per layer."""
     one_case(dev, monkeypatch, B, N, K, L, E, Ns, seed=B + 10 * N + 100 * K, fp64_gso=fp64_gso)
     one_case(dev, monkeypatch, B, N, K, L, E, Ns, seed=B + 10 * N + 100 * K, fp64_gso=fp64_gso, via_step=False)
+
+
+def test_planner_unequal_widths_larger_gso_against_float64(dev, monkeypatch):
+    """Two layers of unequal widths (128 -> 64 -> 48) and taps (2, 3), E = 2, on a GSO of 9 nodes for 6 agents."""
+    kw = dict(K=[2, 3], L=2, E=2, Ns=9, seed=4242, widths=[64, 48])
+    one_case(dev, monkeypatch, 4, 6, **kw)
+    one_case(dev, monkeypatch, 4, 6, via_step=False, **kw)
 
 
 @pytest.mark.parametrize('knob,value', [(KNOB_WGS, 16), (KNOB_WGS, 2048), (KNOB_MERGED, 0), (KNOB_FUSED, 0)])
