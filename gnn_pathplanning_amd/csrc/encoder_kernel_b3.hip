@@ -50,6 +50,22 @@ constexpr size_t kB3Smem = kB3Region + kB3TableBytes;              // 79 360: tw
 constexpr size_t kB3SmemFused = kB3Region + kB3TableBytesFused;    // 81 920: exactly half of the CU's LDS
 static_assert(2 * kObsFloatsLds * 4 <= kB3Region && kB3SsmOff + 16 * 17 * 4 <= kB3TableBytesFused &&
               2 * kB3SmemFused <= (size_t)kLdsBytes, "b3 LDS map");
+// ONE-PLANE tiles (every pixel exactly one bf16: the simulator's {0, 1} observations) keep their pixels PACKED: the h
+// half alone, 2 bytes per pixel, in the same padded 12x12 images (6 dwords per row; a 2x2 window's columns 2 wx .. 2 wx
+// + 3 are the two dwords wx, wx + 1 of a row).  Channel stride kPkChan, agent stride kPkAgent dwords.  Banks (64, one
+// dword each): a read of b3_l0_stream touches a (agent) * 231 + {o, 73 + o, 146 + o} for the lanes q < 3 and one more
+// offset for q = 3; 231 = 39 (mod 64) spreads the 16 agents over 16 banks that the offsets 0 / 73 / 146 (+ 9 / + 18 mod
+// 64) interleave.  Within the range searched exhaustively (72 <= chan < 100, 3 chan <= agent < 3 chan + 70, odd and even
+// strides; nothing is claimed beyond it) no pair makes all seven dword accesses of a half-window conflict-free -- the
+// q = 3 lanes' offsets are fixed by the geometry, not free like the q < 3 lanes' --; this pair is the minimum found: never
+// more than 2 lanes on a bank, 43 doubled lanes in the 448 lane accesses of a half-window.
+constexpr int kPkChan = 73;
+constexpr int kPkAgent = 231;
+constexpr int kPkBytes = kTileAgents * kPkAgent * 4;      // 14 784
+constexpr int kB3ForcePlanes = 256;                        // kernel argument stop_flags, bit 8
+constexpr int kL0Held = 2;                                 // windows per wave whose output waits for the pixels' last read
+static_assert(kPkChan >= kPadHW * kPadHW / 2 && kPkAgent >= 3 * kPkChan && (kPkAgent & 1) && kPkBytes % 16 == 0 &&
+              kPkBytes <= 2 * kObsFloatsLds * 4, "packed pixel image");
 // fused tail: z ping-pong (fp32 rows, stride kZs) | K plane buffers (row stride 800 B) | partial logits
 constexpr int kB3ZBytes = 16 * kZs * 4;                    // 8 704
 constexpr int kB3PRow = 3 * 256 + 32;                      // 800: three 256-byte planes + pad (bank spread as kZs)
@@ -432,21 +448,42 @@ __device__ __forceinline__ void b3_l0_generic(const float* __restrict__ pk, cons
     }
 }
 
-// L0 of one wave: windows wave, wave + 4, .. (7 for wave 0, 6 otherwise) x their 4 positions, one stream.
-//   position P:  [request the words of P + DEPTH]  |  [v_perm the words of P into plane fragments; its MFMAs;
-//   BatchNorm + ReLU / running max of P - 1]   -- the second group is one scheduling region: the VALU work slots in
-//   between the MFMAs.  ONE_PLANE (plane skipping, see the staging code): only the h | m word array is read, only the
-//   h plane is built, three MFMAs (wh, wm, wl against xh) per channel tile instead of six.
-template <bool ONE_PLANE, bool CP>
+// CP: the first window a wave writes BEFORE the barrier (win = 4 kL0Held) lies behind the packed pixels for every team size
+__host__ __device__ constexpr bool cp_direct_windows_clear_pixels() {
+    for (int N = 1; N <= kCpMaxAgents; ++N) {
+        const int T1 = (25 * N + 15) >> 4, l1in = kB3Region - (T1 + 1) * kCpRow;
+        if (l1in + ((4 * kL0Held * N) >> 4) * kCpRow < kPkBytes) return false;
+    }
+    return true;
+}
+
+// L0 of one wave on a ONE-PLANE tile (packed pixels, see kPkChan): windows wave, wave + 4, .. (7 for wave 0, 6 otherwise)
+// x their 4 positions, one stream.  The two positions (oy, ox = 0 / 1) of a HALF-window share their pixels: rows A = 2 wy
+// + oy, B = A + 1, C = A + 2 of the padded image, dwords c0 = wx, c1 = wx + 1 of each.  A lane (q < 3: channel q) reads
+// them ONCE per half-window -- five LDS instructions (two ds_read2_b32, three ds_read_b32; the word path issued sixteen
+// ds_read_b32) -- and builds each position's B fragment with four v_perm whose selectors are per-lane constants:
+//      role      a     b     c     d     e     f     g
+//      q < 3     A.c0  A.c1  A.c1  B.c0  B.c1  C.c0  C.c1                    (relative dwords 0 1 1 6 7 12 13)
+//      q = 3     X0    X1    X2    Z     -     Z     -       X_c = channel c, row C, dword c1 (the (2, 2) taps of ox = 0, 1)
+//   dword 0 = perm(a, b)   q < 3: taps (0,0) (0,1) = columns ox, ox + 1 of A     q = 3: halves ox of X0, X1
+//   dword 1 = perm(c, d)   tap (0,2) | (1,0) = half ox of A.c1, of B.c0          half ox of X2, of Z
+//   dword 2 = perm(d, e)   taps (1,1) (1,2) = columns ox + 1, ox + 2 of B        half ox of Z, twice
+//   dword 3 = perm(f, g)   taps (2,0) (2,1) = columns ox, ox + 1 of C            half ox of Z, twice
+// Z = channel 0, row A, dword c0 is what the word path read for the five k-slots of q = 3 that carry no weight (its
+// address offset 0): every B fragment is the word path's to the bit, non-finite pixels included.  (q = 3 needs five
+// different dwords where q < 3 needs six of which two pairs are neighbours: hence its own address per instruction, and
+// `c` a second read of A.c1.)
+//   half-window H:  [request the dwords of H + DEPTH]  |  per position: [four v_perm; its MFMAs; BatchNorm + ReLU /
+//   running max of the position before]   -- the second group is one scheduling region, as in the word form.
+// Only the h plane exists: three MFMAs (wl, wm, wh against xh) per channel tile.
+template <bool CP>
 __device__ __forceinline__ void b3_l0_stream(const float* __restrict__ pk, const unsigned* obsw,
                                              const float* sstab, char* smem, const CpGeom& g,
-                                             v4f (&res)[ONE_PLANE ? 3 : 5][2], int wave, int lane) {
-    constexpr int DEPTH = ONE_PLANE ? 3 : 1;              // positions the word requests run ahead
-    constexpr int NHELD = ONE_PLANE ? 3 : 5;              // windows (per wave) whose output must wait for the barrier
-    static_assert((4 * NHELD) * 3 * kB3Frag >= (ONE_PLANE ? 1 : 2) * kObsFloatsLds * 4, "held windows cover the pixels");
-    // (CP: window win >= 4 NHELD is written at l1in + ((win N) >> 4) rows >= 40 KB for every N <= kCpMaxAgents, behind
-    // the 27 KB of h | m pixel words the ONE_PLANE stream reads: cp_direct_windows_clear_pixels below)
-    constexpr int NW = ONE_PLANE ? 8 : 16;                // words per position
+                                             v4f (&res)[kL0Held][2], int wave, int lane) {
+    constexpr int DEPTH = 2;                              // half-windows the pixel requests run ahead
+    constexpr int NHELD = kL0Held;                        // windows (per wave) whose output must wait for the barrier
+    static_assert((4 * NHELD) * 3 * kB3Frag >= kPkBytes, "held windows cover the pixels");
+    static_assert(!CP || cp_direct_windows_clear_pixels(), "column-packed windows written early lie behind the pixels");
     const int a = lane & 15, q = lane >> 4;
     v8b A0[2][3];
 #pragma unroll
@@ -454,53 +491,52 @@ __device__ __forceinline__ void b3_l0_stream(const float* __restrict__ pk, const
 #pragma unroll
         for (int p = 0; p < 3; ++p)
             A0[i][p] = as_b8(*reinterpret_cast<const v4f*>(pk + EncLayout::kB0 + ((i * 3 + p) * 64 + lane) * 4));
-    int aoff[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-        aoff[e] = a * kAgentStride + (q < 3 ? q * (kPadHW * kPadHW) + (e / 3) * kPadHW + e % 3
-                                            : e < 3 ? e * (kPadHW * kPadHW) + 2 * kPadHW + 2 : 0);
+    // this lane's dword index of the five reads (roles a + e | b | c | d | f + g), relative to the half-window's offset
+    const int ab = a * kPkAgent, pb = ab + q * kPkChan;
+    int adr[5];
+    adr[0] = q < 3 ? pb : ab + 13;
+    adr[1] = q < 3 ? pb + 1 : ab + kPkChan + 13;
+    adr[2] = q < 3 ? pb + 1 : ab + 2 * kPkChan + 13;
+    adr[3] = q < 3 ? pb + 6 : ab;
+    adr[4] = q < 3 ? pb + 12 : ab;
+    unsigned selA[2], selC[2], selD[2];                   // [ox]
+    selA[0] = q < 3 ? 0x03020100u : 0x05040100u;  selA[1] = q < 3 ? 0x05040302u : 0x07060302u;
+    selC[0] = q < 3 ? 0x05040302u : 0x01000100u;  selC[1] = q < 3 ? 0x07060504u : 0x03020302u;
+    selD[0] = q < 3 ? 0x03020100u : 0x01000100u;  selD[1] = q < 3 ? 0x05040302u : 0x03020302u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (pinned: nothing of this is rematerialised -- a v_cndmask -- next to its use)
+    asm volatile("" : "+v"(adr[0]), "+v"(adr[1]), "+v"(adr[2]), "+v"(adr[3]), "+v"(adr[4]));
+    asm volatile("" : "+v"(selA[0]), "+v"(selA[1]), "+v"(selC[0]), "+v"(selC[1]), "+v"(selD[0]), "+v"(selD[1]));
+#endif
     v4f sc[2], sh[2];
     load_ss(sstab + EncLayout::kBssL0, 32, 0, q, sc[0], sh[0]);
     load_ss(sstab + EncLayout::kBssL0, 32, 1, q, sc[1], sh[1]);
-    unsigned d[DEPTH + 1][NW];
+    unsigned d[DEPTH + 1][7];                             // roles a b c d e f g
     v4f acc[2][2];
     v4f run[2];
-    auto request = [&](unsigned (&dd)[NW], int P) {        // the pixel words of position P (window P / 4)
-        const int win = wave + 4 * (P >> 2), pp = P & 3;
+    auto request = [&](unsigned (&dd)[7], int H) {         // the pixels of half-window H (window H / 2, oy = H & 1)
+        const int win = wave + 4 * (H >> 1);
         const int wy = win / 5, wx = win - wy * 5;
-        const unsigned* base = obsw + (2 * wy + (pp >> 1)) * kPadHW + 2 * wx + (pp & 1);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            dd[e] = base[aoff[e]];
-            if (!ONE_PLANE) dd[8 + e] = base[kObsFloatsLds + aoff[e]];
-        }
+        const unsigned* base = obsw + (2 * wy + (H & 1)) * (kPadHW / 2) + wx;
+        dd[0] = base[adr[0]];
+        dd[4] = base[adr[0] + 7];
+        dd[1] = base[adr[1]];
+        dd[2] = base[adr[2]];
+        dd[3] = base[adr[3]];
+        dd[5] = base[adr[4]];
+        dd[6] = base[adr[4] + 1];
     };
-    auto compute = [&](const unsigned (&dd)[NW], v4f (&ac)[2]) {
-        unsigned bh[4], bm[4], bl[4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            bh[w] = __builtin_amdgcn_perm(dd[2 * w + 1], dd[2 * w], 0x05040100u);
-            if (!ONE_PLANE) {
-                bm[w] = __builtin_amdgcn_perm(dd[2 * w + 1], dd[2 * w], 0x07060302u);
-                bl[w] = __builtin_amdgcn_perm(dd[8 + 2 * w + 1], dd[8 + 2 * w], 0x05040100u);
-            }
-        }
-        const v4u bhv = {bh[0], bh[1], bh[2], bh[3]};
+    auto compute = [&](const unsigned (&dd)[7], auto oxc, v4f (&ac)[2]) {
+        constexpr int ox = decltype(oxc)::value;
+        const v4u bhv = {__builtin_amdgcn_perm(dd[1], dd[0], selA[ox]),
+                         __builtin_amdgcn_perm(dd[3], dd[2], ox ? 0x07060302u : 0x05040100u),
+                         __builtin_amdgcn_perm(dd[4], dd[3], selC[ox]),
+                         __builtin_amdgcn_perm(dd[6], dd[5], selD[ox])};
         const v8b Bh = __builtin_bit_cast(v8b, bhv);
-        if (ONE_PLANE) {
 #pragma unroll
-            for (int p = 2; p >= 0; --p)                      // small planes first: wl xh, wm xh, wh xh
+        for (int p = 2; p >= 0; --p)                          // small planes first: wl xh, wm xh, wh xh
 #pragma unroll
-                for (int i = 0; i < 2; ++i) ac[i] = mfma16b(A0[i][p], Bh, p == 2 ? vzero() : ac[i]);
-        } else {
-            const v4u bmv = {bm[0], bm[1], bm[2], bm[3]}, blv = {bl[0], bl[1], bl[2], bl[3]};
-            const v8b B[3] = {Bh, __builtin_bit_cast(v8b, bmv), __builtin_bit_cast(v8b, blv)};
-#pragma unroll
-            for (int term = 0; term < kB3Terms; ++term)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-                    ac[i] = mfma16b(A0[i][b3_term_a(term)], B[b3_term_b(term)], term == 0 ? vzero() : ac[i]);
-        }
+            for (int i = 0; i < 2; ++i) ac[i] = mfma16b(A0[i][p], Bh, p == 2 ? vzero() : ac[i]);
     };
     // (An inline-asm v_max_f32 here -- to spare the canonicalising v_max x, x, x the compiler puts in front of fmaxf on
     // MFMA results -- was measured WRONG on the GPU: asm consumers of MFMA results get no hazard wait states.)
@@ -533,17 +569,17 @@ __device__ __forceinline__ void b3_l0_stream(const float* __restrict__ pk, const
             b3_store_window<CP>(smem, g, win, lane, pl);
         }
     };
-    // positions [P0, P1): every index below is a compile-time constant (explicit unrolling: the register arrays must
-    // never be indexed dynamically)
+    // positions [P0, P1) (both multiples of 4): every index below is a compile-time constant (explicit unrolling: the
+    // register arrays must never be indexed dynamically)
     auto prologue = [&](auto p0c, auto p1c, auto kc) {
-        constexpr int P = decltype(p0c)::value + decltype(kc)::value;
-        if constexpr (P < decltype(p1c)::value) request(d[P % (DEPTH + 1)], P);
+        constexpr int H = decltype(p0c)::value / 2 + decltype(kc)::value;
+        if constexpr (H < decltype(p1c)::value / 2) request(d[H % (DEPTH + 1)], H);
     };
     auto body = [&](auto p0c, auto p1c, auto kc) {
-        constexpr int P0 = decltype(p0c)::value, P1 = decltype(p1c)::value, P = P0 + decltype(kc)::value;
-        if constexpr (P + DEPTH < P1) request(d[(P + DEPTH) % (DEPTH + 1)], P + DEPTH);
+        constexpr int P0 = decltype(p0c)::value, P1 = decltype(p1c)::value, P = P0 + decltype(kc)::value, H = P >> 1;
+        if constexpr ((P & 1) == 0 && H + DEPTH < P1 / 2) request(d[(H + DEPTH) % (DEPTH + 1)], H + DEPTH);
         __builtin_amdgcn_sched_barrier(0);
-        compute(d[P % (DEPTH + 1)], acc[P & 1]);
+        compute(d[H % (DEPTH + 1)], std::integral_constant<int, (P & 1)>{}, acc[P & 1]);
         if constexpr (P > P0) {
             epilogue(acc[(P - 1) & 1], P - 1);
             if constexpr (((P - 1) & 3) == 3) window_done(std::integral_constant<int, ((P - 1) >> 2)>{});
@@ -990,9 +1026,13 @@ __device__ __forceinline__ void cp_layer2(const WStreamB& ws, v4f (&ring)[kRingH
 template <bool FUSED, int KT, bool CP = false>
 __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kernel_b3(const float* __restrict__ obs,
                                                                  const float* __restrict__ pk,
-                                                                 float* __restrict__ feat, int M, int stop,
+                                                                 float* __restrict__ feat, int M, int stop_flags,
                                                                  const PolicyTail pt) {
     constexpr int END = FUSED ? kb_FILT + 24 * KT : kb_END;
+    // stop_flags: bits 0..7 = the measure build's early exit (GNNPP_STOP_AT), bit 8 = GNNPP_TUNE_ENCODER_ONE_PLANE is 0:
+    // every tile takes the three-plane word path (b3_l0_generic), whatever its pixels
+    [[maybe_unused]] const int stop = stop_flags & 255;
+    const bool force_planes = (stop_flags & kB3ForcePlanes) != 0;
     extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
     v4f* const R4 = reinterpret_cast<v4f*>(gnnpp_smem);              // region R as 16-byte fragments' lanes
     unsigned* const obsw = reinterpret_cast<unsigned*>(gnnpp_smem);  // observation words (h | m << 16), l at + kObsFloatsLds
@@ -1054,6 +1094,7 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
     for (int i = 0; i < kRingH; ++i) h2_ring_load<END>(ws, ring, i);
 
     // ---- observations: all loads first, zero-fill while they fly, then split + scatter -------------------
+    bool one_plane;
     {
         constexpr int NV4 = (kTileAgents * kObsFloats + 3) / 4 + 1;
         constexpr int PER = (NV4 + kThreads - 1) / kThreads;
@@ -1075,70 +1116,98 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
                 for (int c = 0; c < 4; ++c) v[k][c] = src[min(max(e0 + c, 0), valid - 1)];
             }
         }
-        for (int i = tid; i < 2 * kObsFloatsLds / 4; i += kThreads) R4[i] = vzero();
+        // PLANE SKIPPING, decided BEFORE the scatter: when every pixel of the tile is exactly one bf16 (the simulator's
+        // observations are {0, 1}: AgentState.toInputTensor, dataloader/statetransformer.py:82-130) the m and l planes are
+        // identically zero; L0 then does not issue their products -- skipping exact zeros, the result is the same to the
+        // bit -- and the pixels are stored PACKED (kPkChan).  A value is one bf16 iff its low 16 bits are clear (then
+        // m = l = 0; otherwise m or l is not).  Each wave publishes its flag in front of the barrier that ends the
+        // zero-fill, every thread reads all four behind it.  (A lane's elements outside the tile are copies of valid
+        // ones or other agents' pixels: they can only make the flag conservative.)
+        unsigned lowbits = 0;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const v4u vb = __builtin_bit_cast(v4u, v[k]);
+            lowbits |= vb[0] | vb[1] | vb[2] | vb[3];
+        }
+        const bool wave_inexact = __ballot((lowbits & 0xffffu) != 0u) != 0ull;
+        if (lane == 0) planeflag[wave] = (wave_inexact || force_planes) ? 1u : 0u;
+        // the packed image; a tile that needs the word images (27 KiB h | m, 27 KiB l) clears the rest behind the barrier
+        for (int i = tid; i < kPkBytes / 16; i += kThreads) R4[i] = vzero();
         if (CP && tid < kCpRow / 16)                       // the row of zeros behind L1's input rows
             *reinterpret_cast<v4f*>(gnnpp_smem + geom.l1in + geom.T1 * kCpRow + tid * 16) = vzero();
-        unsigned residual = 0;                             // any non-zero m / l plane among this thread's pixels
 #pragma unroll
         for (int i = 0; i < 3; ++i)
             if (tid + i * kThreads < EncLayout::kBssFloats) sstab[tid + i * kThreads] = ssv[i];
         __syncthreads();
+        {
+            const v4u pf = *reinterpret_cast<const v4u*>(planeflag);
+            one_plane = __builtin_amdgcn_readfirstlane((int)(pf[0] | pf[1] | pf[2] | pf[3])) == 0;   // (workgroup-uniform)
+        }
         // Scatter into the padded images, BRANCH-FREE (this loop is VALU-issue-bound and runs in both workgroups of a
-        // CU at the same time: every instruction counts).  Flat element e of [agent][3][11][11] -> word
-        //   o = agent * kAgentStride + ch * 144 + (y + 1) * 12 + x + 1 = base + r + y + 13,   r = 11 y + x in 0..120;
+        // CU at the same time: every instruction counts).  Flat element e of [agent][3][11][11] -> pixel
+        //   o = agent * AS + ch * CS + (y + 1) * 12 + x + 1 = base + r + y + 13,   r = 11 y + x in 0..120
+        // (words, AS = kAgentStride, CS = 144 -- or, packed, halfwords, AS = 2 kPkAgent, CS = 2 kPkChan);
         // a thread's four consecutive elements cross at most ONE channel / agent boundary (r wraps at 121).  Divisions
         // by constants as 24-bit multiplies + shifts (exact on the ranges used); elements outside the tile go to a
         // dump word behind the images instead of around a branch.
         const unsigned dump = 2 * kObsFloatsLds + lane;
+        auto scatter = [&](auto packedc) {
+            constexpr bool PACKED = decltype(packedc)::value;
+            constexpr unsigned AS = PACKED ? 2 * kPkAgent : kAgentStride, CS = PACKED ? 2 * kPkChan : kPadHW * kPadHW;
+            unsigned short* const obsh = reinterpret_cast<unsigned short*>(gnnpp_smem);
 #pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int e0 = (tid + k * kThreads) * 4 - shift;
-            const unsigned es = (unsigned)max(e0, 0);
-            const unsigned ag = __umul24(es, 46223u) >> 24;                   // es / 363   (es < 5816)
-            const unsigned rem = es - __umul24(ag, (unsigned)kObsFloats);
-            const unsigned ch = __umul24(rem, 543u) >> 16;                    // rem / 121  (rem < 363)
-            const int r0 = (int)(rem - __umul24(ch, 121u)) + min(e0, 0);        // (e0 < 0: the first thread of an unaligned tile)
-            const unsigned base = __umul24(ag, (unsigned)kAgentStride) + __umul24(ch, (unsigned)(kPadHW * kPadHW)) + 13u;
-            const unsigned wrapped = base + (ch == 2u ? (unsigned)(kAgentStride - 2 * kPadHW * kPadHW) : (unsigned)(kPadHW * kPadHW));
-            unsigned w1[4], w2[4];
-            const v4u vb = __builtin_bit_cast(v4u, v[k]);
-            const bool inexact = ((vb[0] | vb[1] | vb[2] | vb[3]) & 0xffffu) != 0u;   // some value of this lane is not ONE bf16
-            const bool any_l = __ballot(inexact) != 0ull;               // (wave-uniform)
-            if (!any_l) {
-                // every value IS its h plane (the simulator's {0, 1} observations): no conversions, no l words
-                w1[0] = vb[0] >> 16; w1[1] = vb[1] >> 16; w1[2] = vb[2] >> 16; w1[3] = vb[3] >> 16;
-            } else {
+            for (int k = 0; k < PER; ++k) {
+                const int e0 = (tid + k * kThreads) * 4 - shift;
+                const unsigned es = (unsigned)max(e0, 0);
+                const unsigned ag = __umul24(es, 46223u) >> 24;                   // es / 363   (es < 5816)
+                const unsigned rem = es - __umul24(ag, (unsigned)kObsFloats);
+                const unsigned ch = __umul24(rem, 543u) >> 16;                    // rem / 121  (rem < 363)
+                const int r0 = (int)(rem - __umul24(ch, 121u)) + min(e0, 0);        // (e0 < 0: the first thread of an unaligned tile)
+                const unsigned base = __umul24(ag, AS) + __umul24(ch, CS) + 13u;
+                const unsigned wrapped = base + (ch == 2u ? AS - 2 * CS : CS);
+                unsigned w1[4], w2[4];
+                const v4u vb = __builtin_bit_cast(v4u, v[k]);
+                const bool inexact = ((vb[0] | vb[1] | vb[2] | vb[3]) & 0xffffu) != 0u;   // some value of this lane is not ONE bf16
+                const bool any_l = !PACKED && __ballot(inexact) != 0ull;    // (wave-uniform)
+                if (!any_l) {
+                    // every value IS its h plane: no conversions, no l words
+                    w1[0] = vb[0] >> 16; w1[1] = vb[1] >> 16; w1[2] = vb[2] >> 16; w1[3] = vb[3] >> 16;
+                } else {
 #pragma unroll
-                for (int c2 = 0; c2 < 2; ++c2) {
-                    unsigned h, m, l;
-                    b3_split2(v[k][2 * c2], v[k][2 * c2 + 1], h, m, l);
-                    // (a lane's elements outside the tile are copies of valid ones or other agents' pixels: they can
-                    // only make the flag conservative)
-                    residual |= m | l;
-                    w1[2 * c2] = __builtin_amdgcn_perm(m, h, 0x05040100u);        // (h | m << 16) of the even element
-                    w1[2 * c2 + 1] = __builtin_amdgcn_perm(m, h, 0x07060302u);    // ... of the odd element
-                    w2[2 * c2] = l & 0xffffu;
-                    w2[2 * c2 + 1] = l >> 16;
+                    for (int c2 = 0; c2 < 2; ++c2) {
+                        unsigned h, m, l;
+                        b3_split2(v[k][2 * c2], v[k][2 * c2 + 1], h, m, l);
+                        w1[2 * c2] = __builtin_amdgcn_perm(m, h, 0x05040100u);        // (h | m << 16) of the even element
+                        w1[2 * c2 + 1] = __builtin_amdgcn_perm(m, h, 0x07060302u);    // ... of the odd element
+                        w2[2 * c2] = l & 0xffffu;
+                        w2[2 * c2 + 1] = l >> 16;
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int e = e0 + c;
+                    int r = r0 + c;
+                    const bool wrap = r >= 121;
+                    r = wrap ? r - 121 : r;
+                    const unsigned y = __umul24((unsigned)r & 0xffu, 745u) >> 13;         // r / 11   (0 <= r < 121 where it matters)
+                    const unsigned o = (wrap ? wrapped : base) + (unsigned)r + y;
+                    const bool ok = e >= 0 && e < valid;
+                    if constexpr (PACKED) {
+                        obsh[ok ? o : 2 * dump] = (unsigned short)w1[c];
+                    } else {
+                        obsw[ok ? o : dump] = w1[c];
+                        if (any_l) obsw[ok ? o + kObsFloatsLds : dump] = w2[c];
+                    }
                 }
             }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int e = e0 + c;
-                int r = r0 + c;
-                const bool wrap = r >= 121;
-                r = wrap ? r - 121 : r;
-                const unsigned y = __umul24((unsigned)r & 0xffu, 745u) >> 13;         // r / 11   (0 <= r < 121 where it matters)
-                const unsigned o = (wrap ? wrapped : base) + (unsigned)r + y;
-                const bool ok = e >= 0 && e < valid;
-                obsw[ok ? o : dump] = w1[c];
-                if (any_l) obsw[ok ? o + kObsFloatsLds : dump] = w2[c];
-            }
+        };
+        if (one_plane) {
+            scatter(std::true_type{});
+        } else {
+            for (int i = kPkBytes / 16 + tid; i < 2 * kObsFloatsLds / 4; i += kThreads) R4[i] = vzero();
+            __syncthreads();
+            scatter(std::false_type{});
         }
-        // PLANE SKIPPING: when every pixel of the tile is exactly one bf16 plane (the simulator's observations are
-        // {0, 1}: AgentState.toInputTensor, dataloader/statetransformer.py:82-130) the m and l planes are identically
-        // zero and L0 does not issue their products -- skipping exact zeros, the result is the same to the bit.
-        const bool wave_residual = __ballot(residual != 0) != 0ull;
-        if (lane == 0) planeflag[wave] = wave_residual ? 1u : 0u;
     }
     __syncthreads();
     if (GNNPP_STOP_AT(stop, 1)) return;
@@ -1150,17 +1219,15 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
     // MFMAs of position P are issued, the BatchNorm / ReLU / max epilogue of position P - 1 runs beside them.  The
     // pooled outputs stay in registers until every wave is done with the pixels.
     {
-        const v4u pf = *reinterpret_cast<const v4u*>(planeflag);
-        const bool one_plane = (pf[0] | pf[1] | pf[2] | pf[3]) == 0;     // (workgroup-uniform)
         if (one_plane) {
-            // Window win's output fragments live at R + 3 KiB * win; the h | m pixel words occupy the first 27.1 KiB
-            // of R (the l words behind them are not read on this path): a window beyond them is written as soon as
-            // it is pooled, only a wave's first three windows wait in registers for the barrier.
-            v4f res[3][2];
-            b3_l0_stream<true, CP>(pk, obsw, sstab, gnnpp_smem, geom, res, wave, lane);
+            // Window win's output fragments live at R + 3 KiB * win; the packed pixels occupy the first 14.4 KiB of R: a
+            // window beyond them is written as soon as it is pooled, only a wave's first two windows wait in registers
+            // for the barrier.
+            v4f res[kL0Held][2];
+            b3_l0_stream<CP>(pk, obsw, sstab, gnnpp_smem, geom, res, wave, lane);
             __syncthreads();                                 // every wave has read its last pixel
 #pragma unroll
-            for (int wi = 0; wi < 3; ++wi) {
+            for (int wi = 0; wi < kL0Held; ++wi) {
                 const int win = wave + 4 * wi;
                 v4f pl[3];
                 b3_split8_clamped(res[wi][0], res[wi][1], pl);
@@ -1500,6 +1567,8 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
 }
 
 std::atomic<int> g_policy_column_packing{1};   // GNNPP_TUNE_POLICY_CP: 0 = agents on the MFMA columns for every team size
+std::atomic<int> g_encoder_one_plane{1};       // GNNPP_TUNE_ENCODER_ONE_PLANE: 0 = the three-plane word path for every tile
+static int b3_plane_flag() { return g_encoder_one_plane.load(std::memory_order_relaxed) ? 0 : kB3ForcePlanes; }
 std::atomic<int> g_encoder_cp_tile{0};   // GNNPP_TUNE_ENCODER_CP_TILE: 0 = heuristic, 1 .. 12 = agents per tile, 16 = never
 
 // Few agents (M <= 256 x 8): column-packed tiles of ceil(M / 256) agents, one per CU (latency regime: the per-GPU shards
@@ -1522,14 +1591,14 @@ int encoder_launch_b3(const float* obs, const float* packed, float* feat, int M,
         PolicyTail pt{};
         pt.N = tile;
         hipLaunchKernelGGL((encoder_kernel_b3<false, 3, true>), dim3((M + tile - 1) / tile), dim3(kThreads), kB3Smem, st,
-                           obs, packed, feat, M, GNNPP_ENCODER_STOP_VALUE, pt);
+                           obs, packed, feat, M, GNNPP_ENCODER_STOP_VALUE | b3_plane_flag(), pt);
         return hipGetLastError() == hipSuccess ? 0 : -3;
     }
     static LdsAttrOnce once;
     set_lds_attr_once(once, reinterpret_cast<const void*>(&encoder_kernel_b3<false, 3>), (int)kB3Smem);
     const int grid = (M + kTileAgents - 1) / kTileAgents;
     hipLaunchKernelGGL((encoder_kernel_b3<false, 3>), dim3(grid), dim3(kThreads), kB3Smem, st, obs, packed, feat, M,
-                       GNNPP_ENCODER_STOP_VALUE, PolicyTail{});   // (zero-initialised: unused by <false>)
+                       GNNPP_ENCODER_STOP_VALUE | b3_plane_flag(), PolicyTail{});   // (zero-initialised: unused by <false>)
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1539,7 +1608,7 @@ static int policy_launch_fused_b3_k(const float* obs, const float* packed, const
     static LdsAttrOnce once;
     set_lds_attr_once(once, reinterpret_cast<const void*>(&encoder_kernel_b3<true, KT, CP>), (int)kB3SmemFused);
     hipLaunchKernelGGL((encoder_kernel_b3<true, KT, CP>), dim3(pt.B), dim3(kThreads), kB3SmemFused, st, obs, packed,
-                       static_cast<float*>(nullptr), pt.B * pt.N, 0, pt);
+                       static_cast<float*>(nullptr), pt.B * pt.N, b3_plane_flag(), pt);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -139,6 +139,10 @@ const char* gnnpp_error_string(int code);
                                          its last BatchNorm launch (the workgroups of a channel tile publish their statistics
                                          with an agent-scope release / ticket / acquire hand-off and the last one to arrive
                                          runs the N updates); 0: a launch of its own (r05).  Same statistics to the bit (v330) */
+#define GNNPP_TUNE_ENCODER_ONE_PLANE 20  /* 1 (default): a tile of the bf16x3 encoder / one-launch policy kernel whose pixels are
+                                         all exactly one bf16 (the simulator's {0, 1} observations) stores them packed and
+                                         skips the m and l plane products; 0 (debug): every tile takes the three-plane
+                                         path.  Same results to the bit (the skipped products are exact zeros)         */
 int         gnnpp_set_tuning(int key, int value);
 int         gnnpp_get_tuning(int key);   /* current value of a knob; GNNPP_ERR_ARG for an unknown key */
 

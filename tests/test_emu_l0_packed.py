@@ -1,0 +1,159 @@
+"""CPU (lane emulator): the packed one-plane pixel image and the patch-fed first-layer stream of the bf16x3 encoder
+(csrc/encoder_kernel_b3.hip, kPkChan / b3_l0_stream) against the three-plane word path (b3_l0_generic) of the SAME
+library, which GNNPP_TUNE_ENCODER_ONE_PLANE = 0 routes every tile through.  Both multiply the same non-zero products
+in the same order, so the features and the logits must agree to the bit -- which they only do when every B fragment of
+every position of every window is the word path's (a wrong pixel, half or k-slot changes a product).  Full and ragged
+tiles, every alignment `shift` of the observation pointer, agents-on-columns and column-packed tiles, teams of 1, 10, 12
+and 16 agents, {0, 1} and random one-bf16 pixels; a tile holding one value that is not a bf16 takes the word path."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu'))
+
+pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
+                                reason='host clang++ from ROCm not present')
+
+ONE_PLANE, ENC_CP_TILE, POLICY_CP = 20, 14, 13
+
+
+@pytest.fixture(scope='module')
+def ctx(policy_golden):
+    import emu_lib
+    lib = emu_lib.load()
+    z, _ = policy_golden
+    sd = {k[3:]: z[k] for k in z.files if k.startswith('sd/')}
+    return emu_lib, lib, sd, emu_lib.pack_encoder(lib, sd), emu_lib.pack_filter(lib, z['sd/GFL.0.weight'])
+
+
+def _pixels(kind, M, seed):
+    rng = np.random.default_rng(seed)
+    if kind == 'binary':
+        return (rng.random((M, 3, 11, 11)) < 0.3).astype(np.float32)
+    x = rng.standard_normal((M, 3, 11, 11)).astype(np.float32) * 3.0
+    x = (x.view(np.uint32) & np.uint32(0xffff0000)).view(np.float32)          # exactly one bf16 each, both signs
+    x[rng.random(x.shape) < 0.2] = 0.0
+    return x
+
+
+def _shifted(x, shift):
+    """A copy of x whose first element sits `shift` floats behind a 16-byte boundary."""
+    buf = np.zeros(x.size + 8, np.float32)
+    off = (-(buf.ctypes.data >> 2)) % 4 + shift
+    view = buf[off:off + x.size].reshape(x.shape)
+    view[...] = x
+    assert (view.ctypes.data >> 2) % 4 == shift
+    return view, buf
+
+
+def _encoder_both(el, lib, enc, obs, tile):
+    out = []
+    for knob in (1, 0):
+        assert lib.gnnpp_set_tuning(ONE_PLANE, knob) == 0 and lib.gnnpp_get_tuning(ONE_PLANE) == knob
+        assert lib.gnnpp_set_tuning(ENC_CP_TILE, tile) == 0
+        feat = np.full((obs.shape[0], 128), np.nan, np.float32)
+        try:
+            assert lib.gnnpp_encoder_fwd(el.ptr(obs), el.ptr(enc), el.ptr(feat), obs.shape[0], 0, None, None) == 0
+        finally:
+            lib.gnnpp_set_tuning(ONE_PLANE, 1)
+            lib.gnnpp_set_tuning(ENC_CP_TILE, 0)
+        out.append(feat)
+    return out
+
+
+def _same_bits(a, b):
+    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def test_knob_is_validated(ctx):
+    _, lib, *_ = ctx
+    assert lib.gnnpp_get_tuning(ONE_PLANE) == 1
+    assert lib.gnnpp_set_tuning(ONE_PLANE, 2) == -1 and lib.gnnpp_set_tuning(ONE_PLANE, -1) == -1
+
+
+@pytest.mark.parametrize('kind', ['binary', 'bf16'])
+@pytest.mark.parametrize('M,tile,shift', [
+    (16, 16, 0),          # one full agents-on-columns tile
+    (19, 16, 0),          # + a ragged tile of 3
+    (19, 16, 3),          # both off a 16-byte boundary
+    (10, 16, 1), (10, 16, 2), (10, 16, 3),
+    (1, 16, 0),
+    (24, 12, 0),          # column-packed tiles of 12: the second one at shift 0
+    (21, 10, 1),          # column-packed tiles of 10, 10 and a ragged 1: shifts 1, 3, 1
+    (3, 1, 2),            # one agent per tile: shifts 2, 1, 0
+])
+def test_packed_l0_matches_word_path_encoder(ctx, kind, M, tile, shift):
+    el, lib, _, enc, _ = ctx
+    obs, keep = _shifted(_pixels(kind, M, seed=100 * M + tile + shift), shift)
+    packed, words = _encoder_both(el, lib, enc, obs, tile)
+    assert np.isfinite(packed).all() and np.abs(packed).max() > 0
+    assert _same_bits(packed, words)
+    del keep
+
+
+@pytest.mark.parametrize('kind', ['binary', 'bf16'])
+@pytest.mark.parametrize('N', [1, 10, 12, 16])
+def test_packed_l0_matches_word_path_policy(ctx, kind, N):
+    """The one-launch policy kernel (column-packed for N <= 12, agents on the columns for 16); graph 1 of N = 10 starts
+    at shift 2, of N = 1 at shift 3."""
+    el, lib, sd, enc, filt = ctx
+    B, K = 2, 3
+    obs = _pixels(kind, B * N, seed=7 + N).reshape(B, N, 3, 11, 11)
+    rng = np.random.default_rng(N)
+    S = rng.random((B, N, N)).astype(np.float32) * (rng.random((B, N, N)) < 0.5)
+    S = np.ascontiguousarray((S + S.transpose(0, 2, 1)) * 0.2)
+    gb = el.f32(sd['GFL.0.bias'].reshape(-1))
+    aw, ab = el.f32(sd['actionsMLP.0.weight']), el.f32(sd['actionsMLP.0.bias'])
+    out = []
+    for knob in (1, 0):
+        assert lib.gnnpp_set_tuning(ONE_PLANE, knob) == 0
+        logits = np.full((N, B, 5), np.nan, np.float32)
+        ws = np.zeros((B * N, 128), np.float32)
+        try:
+            assert lib.gnnpp_policy_fwd(el.ptr(obs), el.ptr(S), el.ptr(enc), el.ptr(filt), el.ptr(gb), el.ptr(aw),
+                                        el.ptr(ab), el.ptr(ws), el.ptr(logits), B, N, K, 1, 0, 0, None, None) == 0
+        finally:
+            lib.gnnpp_set_tuning(ONE_PLANE, 1)
+        out.append(logits)
+    assert np.isfinite(out[0]).all()
+    assert _same_bits(out[0], out[1])
+
+
+@pytest.mark.parametrize('tile', [16, 10])
+def test_one_inexact_value_takes_the_word_path(ctx, policy_golden, tile):
+    """One pixel that needs a second plane: the tile must not be packed (it would lose the m plane).  The features then
+    equal the forced word path's, and differ from what the truncated pixel would give."""
+    el, lib, _, enc, _ = ctx
+    obs = _pixels('binary', 10, seed=5)
+    obs[7, 1, 4, 6] = np.float32(1.0) + np.float32(2.0 ** -10)                # h = 1, m = 2^-10
+    packed, words = _encoder_both(el, lib, enc, obs, tile)
+    assert _same_bits(packed, words)
+    trunc = obs.copy()
+    trunc[7, 1, 4, 6] = 1.0
+    t_packed, _ = _encoder_both(el, lib, enc, trunc, tile)
+    assert not _same_bits(packed[7], t_packed[7])
+    others = [i for i in range(10) if i != 7]
+    assert _same_bits(packed[others], t_packed[others])
+
+
+@pytest.mark.parametrize('tile', [16, 10])
+def test_non_finite_one_bf16_pixels_match_word_path(ctx, tile):
+    """+Inf, -Inf and a quiet NaN with clear low bits are each ONE bf16: the tile stays packed.  The five weightless
+    k-slots of the q = 3 lanes then matter (0 x Inf = NaN): they must hold the pixel the word path puts there, or the
+    set of windows / channels that turn NaN -- which L0's ReLU clamp then flushes to 0 (b3_relu_clamp) -- differs.  Same
+    feature bits as the word path."""
+    el, lib, _, enc, _ = ctx
+    obs = _pixels('bf16', 10, seed=11)
+    obs[2, 0, 0, 0] = np.inf                                   # a corner: reached by few windows
+    obs[5, 1, 6, 3] = -np.inf
+    obs[8, 2, 10, 10] = np.float32(np.nan)
+    obs.view(np.uint32)[8, 2, 10, 10] = 0x7fc00000
+    packed, words = _encoder_both(el, lib, enc, obs, tile)
+    assert _same_bits(packed, words)
+    clean = obs.copy()
+    clean[2, 0, 0, 0] = clean[5, 1, 6, 3] = clean[8, 2, 10, 10] = 0.0
+    c_packed, _ = _encoder_both(el, lib, enc, clean, tile)
+    for i in range(10):                                        # the three agents, and only they, see the pixels
+        assert _same_bits(packed[i], c_packed[i]) == (i not in (2, 5, 8))
