@@ -40,7 +40,9 @@ EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get
            'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples', 'gnnpp_mapf_workspace_bytes', 'gnnpp_mapf_solve',
            'gnnpp_mapf_team_workspace_bytes', 'gnnpp_mapf_team_solve', 'gnnpp_schedule_team_workspace_bytes',
            'gnnpp_schedule_team_samples', 'gnnpp_lsigf_team_workspace_bytes', 'gnnpp_lsigf_team_fwd',
-           'gnnpp_filter_head_team_fwd', 'gnnpp_policy_team_fwd')
+           'gnnpp_filter_head_team_fwd', 'gnnpp_policy_team_fwd', 'gnnpp_team_lists_bytes',
+           'gnnpp_team_lists_from_dense', 'gnnpp_rollout_lists', 'gnnpp_lsigf_team_lists_fwd',
+           'gnnpp_filter_head_team_lists_fwd', 'gnnpp_policy_team_lists_fwd')
 
 
 class GnnppError(RuntimeError):
@@ -292,6 +294,18 @@ def _bind(path):
     L.gnnpp_filter_head_team_fwd.restype = ci
     L.gnnpp_policy_team_fwd.argtypes = [vp] * 9 + [ci] * 6 + [vp, vp, vp, cs]
     L.gnnpp_policy_team_fwd.restype = ci
+    L.gnnpp_team_lists_bytes.argtypes = [ci, ci]
+    L.gnnpp_team_lists_bytes.restype = cs
+    L.gnnpp_team_lists_from_dense.argtypes = [vp, vp, cs, ci, ci, ci, vp]
+    L.gnnpp_team_lists_from_dense.restype = ci
+    L.gnnpp_rollout_lists.argtypes = [ctypes.POINTER(RolloutStruct), vp, cs, vp]
+    L.gnnpp_rollout_lists.restype = ci
+    L.gnnpp_lsigf_team_lists_fwd.argtypes = [vp] * 6 + [cs] + [ci] * 10 + [vp]
+    L.gnnpp_lsigf_team_lists_fwd.restype = ci
+    L.gnnpp_filter_head_team_lists_fwd.argtypes = [vp] * 8 + [cs] + [ci] * 7 + [vp]
+    L.gnnpp_filter_head_team_lists_fwd.restype = ci
+    L.gnnpp_policy_team_lists_fwd.argtypes = [vp] * 9 + [ci] * 5 + [vp, vp, vp, cs]
+    L.gnnpp_policy_team_lists_fwd.restype = ci
     L.gnnpp_filter_head_mode.argtypes = [ci, ci, ci, ci]
     L.gnnpp_filter_head_mode.restype = ci
     for f in ('gnnpp_rollout_observe', 'gnnpp_rollout_gso', 'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe',

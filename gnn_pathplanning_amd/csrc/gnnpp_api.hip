@@ -20,6 +20,7 @@
 #include "policy_filter_kernel.hip"
 #include "lsigf_small_kernel.hip"
 #include "lsigf_team_kernel.hip"   // forward filter / head / policy step for graphs of up to 1024 nodes, spread over workgroups
+#include "rollout_team_lists_kernel.hip"   // the rollout's communication graph as the team filter's neighbour lists
 #include "train_encoder.hip"
 #include "train_ops.hip"
 
@@ -279,6 +280,80 @@ int gnnpp_policy_team_fwd(const float* obs, const void* S, const float* enc_pack
     a.B = B; a.N = N; a.G = GNNPP_FEAT; a.F = GNNPP_FEAT; a.K = K; a.E = E;
     a.s_is_f64 = s_is_f64; a.s_batched = 1; a.relu = 1;
     return team_launch(a, workspace, precision, st);
+}
+
+size_t gnnpp_team_lists_bytes(int graphs, int N) {
+    if (graphs <= 0 || N <= 0 || N > GNNPP_ROLLOUT_MAX_TEAM) return 0;
+    return team_lists_bytes(graphs, N);
+}
+
+// a lists block handed in by the caller: present, 16-byte aligned and large enough for `graphs` graphs of N nodes
+static bool team_lists_block_ok(const void* lists, size_t lists_bytes, int graphs, int N) {
+    return lists && graphs > 0 && N > 0 && N <= GNNPP_ROLLOUT_MAX_TEAM && !(reinterpret_cast<uintptr_t>(lists) & 15) &&
+           lists_bytes >= team_lists_bytes(graphs, N);
+}
+
+int gnnpp_team_lists_from_dense(const void* S, void* lists, size_t lists_bytes, int graphs, int N, int s_is_f64,
+                                void* stream) {
+    if (!S || !team_lists_block_ok(lists, lists_bytes, graphs, N)) return GNNPP_ERR_ARG;
+    TeamArgs a = {};
+    a.S = S; a.N = N; a.s_is_f64 = s_is_f64;
+    return team_lists_launch(a, lists, graphs, static_cast<hipStream_t>(stream));
+}
+
+// The three team calls on the caller's lists: team_check with the lists in the place of S (NULL allowed at K = 1), then
+// the block's alignment.  Its size is the caller's contract (include/gnnpp.h).
+static int team_lists_check(const void* x, const void* lists, const void* packed, const void* workspace,
+                            size_t workspace_bytes, int B, int N, int G, int F, int K, int E, int s_batched,
+                            int precision) {
+    const int rc = team_check(x, lists, packed, workspace, workspace_bytes, B, N, G, F, K, E, s_batched, precision);
+    if (rc) return rc;
+    return (reinterpret_cast<uintptr_t>(lists) & 15) ? GNNPP_ERR_ARG : GNNPP_OK;
+}
+
+int gnnpp_lsigf_team_lists_fwd(const float* x, const void* lists, const float* packed, const float* bias, float* y,
+                               void* workspace, size_t workspace_bytes, int B, int N, int G, int F, int K, int E,
+                               int s_batched, int relu, int bias_per_node, int precision, void* stream) {
+    if (!y) return GNNPP_ERR_ARG;
+    const int rc = team_lists_check(x, lists, packed, workspace, workspace_bytes, B, N, G, F, K, E, s_batched, precision);
+    if (rc) return rc;
+    TeamArgs a = {};
+    a.x = x; a.wpk = packed; a.bias = bias; a.y = y;
+    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
+    a.s_batched = s_batched != 0; a.relu = relu; a.bias_per_node = bias && bias_per_node;
+    return team_launch(a, workspace, precision, static_cast<hipStream_t>(stream), K > 1 ? lists : nullptr);
+}
+
+int gnnpp_filter_head_team_lists_fwd(const float* x, const void* lists, const float* packed, const float* bias,
+                                     const float* act_w, const float* act_b, float* logits, void* workspace,
+                                     size_t workspace_bytes, int B, int N, int G, int F, int K, int E, int precision,
+                                     void* stream) {
+    if (!act_w || !act_b || !logits) return GNNPP_ERR_ARG;
+    const int rc = team_lists_check(x, lists, packed, workspace, workspace_bytes, B, N, G, F, K, E, 1, precision);
+    if (rc) return rc;
+    TeamArgs a = {};
+    a.x = x; a.wpk = packed; a.bias = bias; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
+    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
+    a.s_batched = 1; a.relu = 1;
+    return team_launch(a, workspace, precision, static_cast<hipStream_t>(stream), K > 1 ? lists : nullptr);
+}
+
+int gnnpp_policy_team_lists_fwd(const float* obs, const void* lists, const float* enc_packed, const float* filt_packed,
+                                const float* gf_bias, const float* act_w, const float* act_b, float* feat_ws,
+                                float* logits, int B, int N, int K, int E, int precision, int* range_flag, void* stream,
+                                void* workspace, size_t workspace_bytes) {
+    if (!obs || !enc_packed || !act_w || !act_b || !logits) return GNNPP_ERR_ARG;
+    int rc = team_lists_check(feat_ws, lists, filt_packed, workspace, workspace_bytes, B, N, GNNPP_FEAT, GNNPP_FEAT, K,
+                              E, 1, precision);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = encoder_launch(obs, enc_packed, feat_ws, B * N, range_flag, precision, st);
+    if (rc) return rc;
+    TeamArgs a = {};
+    a.x = feat_ws; a.wpk = filt_packed; a.bias = gf_bias; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
+    a.B = B; a.N = N; a.G = GNNPP_FEAT; a.F = GNNPP_FEAT; a.K = K; a.E = E;
+    a.s_batched = 1; a.relu = 1;
+    return team_launch(a, workspace, precision, st, K > 1 ? lists : nullptr);
 }
 
 int gnnpp_filter_head_mode(int B, int N, int K, int precision) {
@@ -582,6 +657,11 @@ int gnnpp_rollout_gso(const gnnpp_rollout* r, void* stream) {
     if (!rollout_common_ok(r) || !r->radius || !r->S) return GNNPP_ERR_ARG;
     if (rollout_team(r)) return rollout_team_gso_launch(*r, r->grow != 0, static_cast<hipStream_t>(stream));
     return rollout_gso_launch(*r, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_rollout_lists(const gnnpp_rollout* r, void* lists, size_t lists_bytes, void* stream) {
+    if (!rollout_common_ok(r) || !r->radius || !team_lists_block_ok(lists, lists_bytes, r->B, r->N)) return GNNPP_ERR_ARG;
+    return rollout_team_lists_launch(*r, r->grow != 0, lists, static_cast<hipStream_t>(stream));
 }
 
 int gnnpp_rollout_gso_observe(const gnnpp_rollout* r, void* stream) {

@@ -405,21 +405,37 @@ static hipError_t team_tail_launch(const TeamArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// team_lists_kernel on its own (gnnpp_team_lists_from_dense): `a` carries S, s_is_f64 and N; the lists of `graphs`
+// slabs go to `lists` (the head of team_layout for that many graphs).
+int team_lists_launch(TeamArgs a, void* lists, int graphs, hipStream_t st) {
+    const TeamLayout L = team_layout(graphs, a.N, 1, 2, 1, 1);
+    char* base = static_cast<char*>(lists);
+    a.cnt = reinterpret_cast<int*>(base + L.cnt);
+    a.idx = reinterpret_cast<unsigned short*>(base + L.idx);
+    a.val = reinterpret_cast<float*>(base + L.val);
+    a.Np = L.Np;
+    hipLaunchKernelGGL(team_lists_kernel, dim3(graphs * ((a.N + 15) / 16)), dim3(256), 4 * 16 * sizeof(int), st, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 // `a` carries the call's pointers, sizes and flags; fills in the derived fields and enqueues lists, shifts and tail.
 // The caller has validated everything (nothing here can fail but a launch).
-int team_launch(TeamArgs a, void* workspace, int precision, hipStream_t st) {
+// lists != nullptr: the caller's neighbour lists (the same layout as the head of the workspace, which then goes unused)
+// stand in for S and no list launch is made.
+int team_launch(TeamArgs a, void* workspace, int precision, hipStream_t st, const void* lists = nullptr) {
     const TeamLayout L = team_layout(a.B, a.N, a.G, a.K, a.E, a.s_batched);
     char* ws = static_cast<char*>(workspace);
-    a.cnt = reinterpret_cast<int*>(ws + L.cnt);
-    a.idx = reinterpret_cast<unsigned short*>(ws + L.idx);
-    a.val = reinterpret_cast<float*>(ws + L.val);
+    char* lb = lists ? static_cast<char*>(const_cast<void*>(lists)) : ws;       // (read only when it is the caller's)
+    a.cnt = reinterpret_cast<int*>(lb + L.cnt);
+    a.idx = reinterpret_cast<unsigned short*>(lb + L.idx);
+    a.val = reinterpret_cast<float*>(lb + L.val);
     a.z = reinterpret_cast<float*>(ws + L.z);
     a.Np = L.Np; a.Gz = L.Gz;
     a.NG = (a.G + 15) / 16; a.KB = (a.G + 31) / 32; a.MT = (a.F + 15) / 16;
     a.wpk_b = a.wpk + filter_packed_b3_offset(a.G, a.F, a.K, a.E);
     a.x_vec = (a.G & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
     a.y_vec = a.y && (a.F & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & 15) == 0;
-    if (a.K > 1) {
+    if (a.K > 1 && !lists) {
         const int graphs = (a.s_batched ? a.B : 1) * a.E, strips = (a.N + 15) / 16;
         hipLaunchKernelGGL(team_lists_kernel, dim3(graphs * strips), dim3(256), 4 * 16 * sizeof(int), st, a);
         if (hipGetLastError() != hipSuccess) return -3;

@@ -738,6 +738,86 @@ class DecentralPlannerNet(nn.Module):
                 _native.check(rc, 'gnnpp_filter_head_team_fwd')
                 return logits[:N] if Ns != N else logits
 
+    def lists_refusal(self, N=None):
+        """Why forward_logits_lists cannot serve this planner (and a team of N agents) -- None when it can."""
+        if self.training:
+            return 'forward_logits_lists is the eval-mode forward (call model.eval()); training takes the dense GSO'
+        if self.largeGraphFilter != 'lists':
+            return "the planner was built with largeGraphFilter=%r; neighbour lists need 'lists'" % self.largeGraphFilter
+        if self._prec() == _native.PREC_SPLIT_F16:
+            return "precision 'split_f16' has no team kernels; neighbour lists need 'fp32' or 'fp32_mfma'"
+        if self.numAgents > gml.TEAM_MAX_NODES or any(w > 128 for w in self.F):
+            return ('neighbour lists serve teams of up to %d agents and layers of up to 128 features (this planner: %d '
+                    'agents, widths %s)' % (gml.TEAM_MAX_NODES, self.numAgents, self.F))
+        if N is not None and N != self.numAgents:
+            return 'the planner serves teams of %d agents, the lists describe %d' % (self.numAgents, N)
+        return None
+
+    def forward_logits_lists(self, inputTensor, lists):
+        """forward_logits with the communication graph given as NEIGHBOUR LISTS instead of addGSO's dense matrix: `lists`
+        is a block of B * E graphs of numAgents nodes (graphML.team_lists_from_dense(S [B,E,N,N]), or
+        BatchedRollout(graph='lists').gso()).  The team kernels at any team size; bit-identical to addGSO(S) + forward_logits
+        under largeGraphFilter='lists' wherever that route runs them (teams of more than graphML.MAX_NODES agents).
+        The reference's planner (one layer, 128 features) is ONE gnnpp_policy_team_lists_fwd call; several layers or
+        edge features run the encoder, gnnpp_lsigf_team_lists_fwd per layer and gnnpp_filter_head_team_lists_fwd.
+        Needs eval mode, no gradient wanted (the result carries no graph), largeGraphFilter='lists' and not split-f16
+        (GnnppError otherwise).  Lists are built for
+        the team: a graph of more nodes than numAgents (which addGSO accepts) is refused -- a block that is not the
+        size of B * E graphs of numAgents nodes raises."""
+        why = self.lists_refusal()
+        if why is None and torch.is_grad_enabled() and inputTensor.requires_grad:
+            why = 'forward_logits_lists has no backward pass: detach the observations or call it under torch.no_grad()'
+        if why:
+            raise _native.GnnppError(why)
+        B, N = inputTensor.shape[0], self.numAgents
+        assert inputTensor.shape[1] >= N
+        obs = inputTensor.detach()
+        if obs.shape[1] != N:
+            obs = obs[:, :N]
+        if obs.dtype is not torch.float32 or not obs.is_contiguous():
+            obs = obs.contiguous().float()
+        enc = self.packed_encoder()                        # (also refreshes self._mods)
+        gfs, act = self._mods
+        dev = _native.require_gpu(obs, lists, gfs[0].weight, act.weight)
+        need = gml.team_lists_bytes(B * self.E, N)
+        if lists.dtype is not torch.uint8 or lists.dim() != 1 or lists.numel() != need or lists.data_ptr() % 16:
+            raise _native.GnnppError('forward_logits_lists: the lists must be a 16-byte aligned uint8 block of %d bytes '
+                                     '(%d x %d graphs of the team\'s %d nodes; got %s of %d elements): lists are built for '
+                                     'the team, a GSO larger than the team goes through addGSO'
+                                     % (need, B, self.E, N, lists.dtype, lists.numel()))
+        prec = self._prec()
+        L = _native.lib()
+        gl = gfs[-1]
+        gb_p, aw_p, ab_p, _keep = self._head_cache.get(
+            (gl.bias, act.weight, act.bias) if gl.bias is not None else (act.weight, act.bias),
+            lambda: self._head_pointers(gl, act))
+        with _native.device_guard(dev):
+            st = _native.stream_ptr(dev)
+            if self.L == 1 and gl.F == 128:
+                feat = self._feat_workspace(B * N, st, dev)
+                ws = gml.team_workspace(B, N, 128, gl.K, self.E, True, dev, st.value)
+                logits = torch.empty(N, B, 5, dtype=torch.float32, device=dev)
+                rc = L.gnnpp_policy_team_lists_fwd(obs.data_ptr(), lists.data_ptr(), enc.data_ptr(),
+                                                   gl.packed_taps().data_ptr(), gb_p, aw_p, ab_p, feat.data_ptr(),
+                                                   logits.data_ptr(), B, N, gl.K, self.E, prec, None, st, ws.data_ptr(),
+                                                   ws.numel())
+                _native.check(rc, 'gnnpp_policy_team_lists_fwd')
+                return logits
+            x = self.encode(obs, prec)
+            for l, gf in enumerate(gfs):
+                if l < self.L - 1:
+                    x = gml.lsigf_team(gf.weight, None, x, gf.bias, relu=True, precision=prec, packed=gf.packed_taps(),
+                                       lists=lists, batched=True)
+                    continue
+                bias = gf.bias.detach().reshape(-1).contiguous().float() if gf.bias is not None else None
+                ws = gml.team_workspace(B, N, gf.G, gf.K, self.E, True, dev, st.value)
+                logits = torch.empty(N, B, 5, dtype=torch.float32, device=dev)
+                rc = L.gnnpp_filter_head_team_lists_fwd(_ptr(x), _ptr(lists), _ptr(gf.packed_taps()), _ptr(bias), aw_p,
+                                                        ab_p, _ptr(logits), _ptr(ws), ws.numel(), B, N, gf.G, gf.F,
+                                                        gf.K, self.E, prec, st)
+                _native.check(rc, 'gnnpp_filter_head_team_lists_fwd')
+                return logits
+
     def _forward_train(self, inputTensor):
         """Differentiable train-mode forward with the reference's semantics (decentralplanner.py:278-318).
         Hand-written HIP: the per-agent ConvLayers calls (BatchNorm with THAT call's batch statistics, N

@@ -110,25 +110,100 @@ def team_workspace(B, N, G, K, E, batched, dev, stream):
     return ws
 
 
-def lsigf_team(h, S, x, b, relu=False, precision=None, workspace=None, packed=None):
+def team_lists_bytes(graphs, N):
+    """Size in bytes of a neighbour-lists block for `graphs` graphs of N nodes (gnnpp_team_lists_bytes; 0 out of range).
+    Layout (include/gnnpp.h), every region 16-byte aligned, Np = N rounded up to 4:
+    int32 cnt [graphs][N] | uint16 idx [graphs][N][Np] | fp32 val [graphs][N][Np]."""
+    return int(_native.lib().gnnpp_team_lists_bytes(int(graphs), int(N)))
+
+
+def _team_lists_offsets(graphs, N):
+    Np = (N + 3) & ~3
+    up = lambda v: (v + 15) & ~15                                              # noqa: E731
+    idx = up(graphs * N * 4)
+    val = idx + up(graphs * N * Np * 2)
+    return idx, val, val + up(graphs * N * Np * 4), Np
+
+
+def team_lists_from_dense(S, out=None):
+    """The neighbour lists of the non-zeros of S [..., N, N] (fp32, or fp64 rounded like S.float()), one graph per
+    leading index, as a uint8 device block (gnnpp_team_lists_from_dense): what lsigf_team(lists=...) and
+    DecentralPlannerNet.forward_logits_lists take."""
+    dev = _native.require_gpu(S)
+    N = int(S.shape[-1])
+    assert S.dim() >= 2 and S.shape[-2] == N
+    Sc = S.detach().contiguous()
+    if Sc.dtype not in (torch.float32, torch.float64):
+        Sc = Sc.float()
+    graphs = Sc.numel() // (N * N)
+    nbytes = team_lists_bytes(graphs, N)
+    if nbytes == 0:
+        raise _native.GnnppError('neighbour lists serve graphs of 1 .. %d nodes (got %d graphs of %d)'
+                                 % (TEAM_MAX_NODES, graphs, N))
+    block = out if out is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _native.device_guard(dev):
+        rc = _native.lib().gnnpp_team_lists_from_dense(_ptr(Sc), _ptr(block), block.numel(), graphs, N,
+                                                       int(Sc.dtype == torch.float64), _native.stream_ptr(dev))
+    _native.check(rc, 'gnnpp_team_lists_from_dense')
+    return block
+
+
+def team_lists_views(block, graphs, N):
+    """(cnt [graphs,N] int32, idx [graphs,N,Np] uint16, val [graphs,N,Np] float32): tensor views of a lists block."""
+    idx_o, val_o, total, Np = _team_lists_offsets(graphs, N)
+    if block.dtype is not torch.uint8 or block.dim() != 1 or block.numel() < total or block.data_ptr() % 16:
+        raise _native.GnnppError('a lists block for %d graphs of %d nodes is a 16-byte aligned uint8 tensor of at least '
+                                 '%d bytes' % (graphs, N, total))
+    return (block[:graphs * N * 4].view(torch.int32).view(graphs, N),
+            block[idx_o:idx_o + graphs * N * Np * 2].view(torch.uint16).view(graphs, N, Np),
+            block[val_o:val_o + graphs * N * Np * 4].view(torch.float32).view(graphs, N, Np))
+
+
+def team_lists_to_dense(block, graphs, N):
+    """S [graphs,N,N] float32 with S[g, idx[g,n,j], n] = val[g,n,j] for j < cnt[g,n] -- torch ops, for debugging (it
+    synchronises).  A count outside 0 .. N or a listed index >= N raises GnnppError."""
+    cnt, idx, val = team_lists_views(block, graphs, N)
+    if bool(((cnt < 0) | (cnt > N)).any()):
+        raise _native.GnnppError('lists block: a count outside 0 .. %d' % N)
+    live = torch.arange(idx.shape[2], device=block.device)[None, None, :] < cnt[:, :, None]
+    g, n, j = live.nonzero(as_tuple=True)
+    rows = idx.view(torch.int16)[g, n, j].long() & 0xffff
+    if bool((rows >= N).any()):
+        raise _native.GnnppError('lists block: a row index >= %d' % N)
+    S = torch.zeros(graphs, N, N, dtype=torch.float32, device=block.device)
+    S[g, rows, n] = val[g, n, j]
+    return S
+
+
+def lsigf_team(h, S, x, b, relu=False, precision=None, workspace=None, packed=None, lists=None, batched=None):
     """The forward filter on neighbour lists for graphs of up to TEAM_MAX_NODES nodes (gnnpp_lsigf_team_fwd), node-major:
     h [F,E,K,G], S [B,E,N,N] | [E,N,N] (fp32 or fp64), x [B,N,G], b [F,1] | [F,N] | None -> [B,N,F].  No autograd.
     workspace: a uint8 device tensor of gnnpp_lsigf_team_workspace_bytes (None: cached per shape and stream).
+    lists: instead of S (pass S=None), a lists block of (B if batched else 1) * E graphs -- team_lists_from_dense(S), or
+    BatchedRollout(graph='lists').gso() -- handed to gnnpp_lsigf_team_lists_fwd: no list launch, the same bytes out.
+    batched (with lists only; default True): one graph per sample.  Its validity is the caller's contract.
     G or F > 128 and precision='split_f16' raise GnnppError: there is no fallback behind this call."""
-    dev = _native.require_gpu(h, S, x, b)
+    if (S is None) == (lists is None):
+        raise _native.GnnppError('lsigf_team takes either S or lists')
+    dev = _native.require_gpu(h, S, x, b, lists)
     L = _native.lib()
     precision = _native.precision_code(DEFAULT_PRECISION if precision is None else precision)
     F_out, E, K, G = h.shape
     B, N = x.shape[0], x.shape[1]
-    batched = S.dim() == 4
-    assert x.shape[2] == G and S.shape[-1] == N and S.shape[-2] == N and S.shape[-3] == E
-    assert not batched or S.shape[0] == B
+    assert x.shape[2] == G
+    if lists is None:
+        batched = S.dim() == 4
+        assert S.shape[-1] == N and S.shape[-2] == N and S.shape[-3] == E
+        assert not batched or S.shape[0] == B
+        Sc = S.detach().contiguous()
+        if Sc.dtype not in (torch.float32, torch.float64):
+            Sc = Sc.float()
+    else:
+        batched = True if batched is None else bool(batched)
+        team_lists_views(lists, (B if batched else 1) * E, N)          # (size, dtype, alignment)
     xc = x.detach().contiguous()
     if xc.dtype != torch.float32:
         xc = xc.float()
-    Sc = S.detach().contiguous()
-    if Sc.dtype not in (torch.float32, torch.float64):
-        Sc = Sc.float()
     if packed is None:
         packed = pack_filter_taps(h)
     bias, per_node = _bias_arg(b, F_out, N)
@@ -136,6 +211,12 @@ def lsigf_team(h, S, x, b, relu=False, precision=None, workspace=None, packed=No
     with _native.device_guard(dev):
         st = _native.stream_ptr(dev)
         ws = workspace if workspace is not None else team_workspace(B, N, G, K, E, batched, dev, st.value)
+        if lists is not None:
+            rc = L.gnnpp_lsigf_team_lists_fwd(_ptr(xc), _ptr(lists), _ptr(packed), _ptr(bias), _ptr(y), _ptr(ws),
+                                              ws.numel(), B, N, G, F_out, K, E, int(batched), int(relu), per_node,
+                                              int(precision), st)
+            _native.check(rc, 'gnnpp_lsigf_team_lists_fwd')
+            return y
         rc = L.gnnpp_lsigf_team_fwd(_ptr(xc), _ptr(Sc), _ptr(packed), _ptr(bias), _ptr(y), _ptr(ws), ws.numel(), B, N,
                                     G, F_out, K, E, int(Sc.dtype == torch.float64), int(batched), int(relu), per_node,
                                     int(precision), st)

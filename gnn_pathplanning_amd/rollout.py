@@ -27,6 +27,7 @@ _TIE = {'lowest': 0, 'hashed': 1, 'replay': 2, 'mt19937': 3}
 MAX_AGENTS = 128            # GNNPP_ROLLOUT_MAX_AGENTS: the one-wave simulator kernels
 MAX_TEAM = 1024             # GNNPP_ROLLOUT_MAX_TEAM
 MAX_TEAM_CELLS = 65536      # GNNPP_ROLLOUT_TEAM_MAX_CELLS: map limit of the large-team kernels
+GRAPHS = ('dense', 'lists')  # how a BatchedRollout hands the communication graph to the policy
 
 
 def _p(t):
@@ -35,14 +36,21 @@ def _p(t):
 
 class BatchedRollout:
     def __init__(self, grid, starts, goals, maxstep, device, commR=6.0, tie_mode='lowest', seed=0,
-                 rng_words=None):
+                 rng_words=None, graph='dense'):
         """grid [B,H,W] or [H,W] (1 = obstacle); starts, goals [B,N,2]; maxstep int or [B].  Teams of up to
         MAX_TEAM agents; beyond MAX_AGENTS the simulator runs the large-team kernels, which need H * W <=
         MAX_TEAM_CELLS.  rng_words (tie_mode 'mt19937'): words of each episode's random stream, by default 2048,
-        and 64 per agent for teams of more than MAX_AGENTS agents."""
+        and 64 per agent for teams of more than MAX_AGENTS agents.
+        graph: 'dense' (default) -- the communication graph is the GSO S [B,N,N] -- or 'lists': it is the team filter's
+        neighbour lists (gnnpp_rollout_lists; `self.lists`, a uint8 block of B graphs, see graphML.team_lists_views), no
+        S is ever allocated, and step(model) needs a planner that takes lists (DecentralPlannerNet with
+        largeGraphFilter='lists', its forward_logits_lists).  Same episodes, step for step."""
         dev = torch.device(device)
         if dev.type != 'cuda':
             raise _native.GnnppError('BatchedRollout needs a HIP device (no CPU fallback)')
+        if graph not in GRAPHS:
+            raise _native.GnnppError('unknown graph %r (one of %s)' % (graph, list(GRAPHS)))
+        self.graph = graph
         _native.lib()
         self.device = dev
         g = torch.as_tensor(grid)
@@ -66,7 +74,12 @@ class BatchedRollout:
         B, N = self.B, self.N
         self.obs = torch.empty(B, N, 3, 11, 11, dtype=torch.float32, device=dev)
         self.radius = torch.full((B,), float(commR), dtype=torch.float64, device=dev)
-        self.S = torch.empty(B, N, N, dtype=torch.float32, device=dev)
+        # 'lists': no dense GSO, the lists block instead (sized for the dense worst case, touched only where the
+        # graph has neighbours)
+        self.S = torch.empty(B, N, N, dtype=torch.float32, device=dev) if graph == 'dense' else None
+        self.lists = None
+        if graph == 'lists':
+            self.lists = torch.empty(_native.lib().gnnpp_team_lists_bytes(B, N), dtype=torch.uint8, device=dev)
         self.connected = torch.zeros(B, dtype=torch.int32, device=dev)
         self.reached = torch.zeros(B, N, dtype=torch.int32, device=dev)
         self.start_step = torch.full((B, N), -1, dtype=torch.int32, device=dev)
@@ -120,17 +133,32 @@ class BatchedRollout:
         self._call(_native.lib().gnnpp_rollout_observe, 'gnnpp_rollout_observe')
         return self.obs
 
+    def _lists_call(self):
+        with _native.device_guard(self.device):
+            _native.check(_native.lib().gnnpp_rollout_lists(ctypes.byref(self._r), _p(self.lists), self.lists.numel(),
+                                                            _native.stream_ptr(self.device)), 'gnnpp_rollout_lists')
+
     def gso(self, step=None):
-        """[B,N,N] float32 GSO of the current positions.  step 0 grows the radius until connected."""
+        """[B,N,N] float32 GSO of the current positions (graph='lists': the lists block of the same graph).  step 0
+        grows the radius until connected."""
         step = self.t if step is None else step
         self._r.grow = int(step == 0)
+        if self.graph == 'lists':
+            self._lists_call()
+            return self.lists
         self._call(_native.lib().gnnpp_rollout_gso, 'gnnpp_rollout_gso')
         return self.S
 
     def gso_observe(self):
         """gso() (no radius growth: not for step 0) and observe() of the current positions as ONE launch
-        (gnnpp_rollout_gso_observe): the two are independent given the positions."""
+        (gnnpp_rollout_gso_observe): the two are independent given the positions.  graph='lists': the lists launch,
+        then the observations (separate launches, as large teams already use); returns (obs, lists)."""
         self._r.grow = 0
+        if self.graph == 'lists':
+            self._lists_call()
+            self._call(_native.lib().gnnpp_rollout_observe, 'gnnpp_rollout_observe')
+            self._state_step = self.t
+            return self.obs, self.lists
         self._call(_native.lib().gnnpp_rollout_gso_observe, 'gnnpp_rollout_gso_observe')
         self._state_step = self.t
         return self.obs, self.S
@@ -170,7 +198,12 @@ class BatchedRollout:
         (gnnpp_rollout_step).  Same results as the three calls in sequence."""
         self._prepare_move(logits, actions, choices, currentstep)
         self._r.grow = 0
-        self._call(_native.lib().gnnpp_rollout_step, 'gnnpp_rollout_step')
+        if self.graph == 'lists':                          # move -> lists -> observations: three launches
+            self._call(_native.lib().gnnpp_rollout_move, 'gnnpp_rollout_move')
+            self._lists_call()
+            self._call(_native.lib().gnnpp_rollout_observe, 'gnnpp_rollout_observe')
+        else:
+            self._call(_native.lib().gnnpp_rollout_step, 'gnnpp_rollout_step')
         self._state_step = self.t                          # obs / S describe the positions after step t
         return self.flags
 
@@ -178,7 +211,7 @@ class BatchedRollout:
         """gnnpp_rollout_policy_step(s): policy forward + move + next gso/observe in ONE kernel per step, when
         the model and the team qualify (eval mode, N = model.numAgents <= 16, K = 2..4, not 'replay'); nsteps
         launches are enqueued by one C call."""
-        if (self.N > 16 or self.tie_mode == 2 or getattr(model, 'training', True)
+        if (self.graph != 'dense' or self.N > 16 or self.tie_mode == 2 or getattr(model, 'training', True)
                 or getattr(model, 'numAgents', -1) != self.N or not hasattr(model, 'policy_pointers')):
             return False
         ptrs = model.policy_pointers()
@@ -207,11 +240,16 @@ class BatchedRollout:
         """One rollout step of all episodes: observe -> gso -> policy forward -> move.  From the
         second step on the observation and the GSO were already produced by the previous step's
         fused move kernel."""
+        if self.graph == 'lists':
+            self._check_lists_model(model)
         if self.t == 0:                                      # step 0 may grow the radius
             self.observe()
             self.gso()
         elif self._state_step != self.t:                     # stale state: graph and observations side by side
             self.gso_observe()
+        if self.graph == 'lists':
+            logits = model.forward_logits_lists(self.obs, self.lists)
+            return self.move_and_observe(logits=logits) if self.N <= self.fused_sim_max_agents else self.move(logits=logits)
         if self._policy_step(model):                         # small teams: the whole step is one launch
             return self.flags
         model.addGSO(self.S)
@@ -219,6 +257,19 @@ class BatchedRollout:
         # one launch for move -> graph -> observations (see fused_sim_max_agents); beyond it: move now, the
         # graph and the observations side by side at the start of the next step
         return self.move_and_observe(logits=logits) if self.N <= self.fused_sim_max_agents else self.move(logits=logits)
+
+    def _check_lists_model(self, model):
+        """graph='lists': the planner must take lists, for this team -- refused with the reason, before anything runs."""
+        if not hasattr(model, 'forward_logits_lists'):
+            raise _native.GnnppError("BatchedRollout(graph='lists') needs a planner with forward_logits_lists "
+                                     "(DecentralPlannerNet with largeGraphFilter='lists'); %s has none"
+                                     % type(model).__name__)
+        why = model.lists_refusal(self.N)
+        if why is None and self.N <= 16 and model.policy_pointers() is not None and 2 <= model.policy_pointers()[5] <= 4:
+            why = ('this planner and team run the one-launch step (N <= 16, K = 2..4), which reads the dense GSO: use '
+                   "graph='dense'")
+        if why:
+            raise _native.GnnppError("BatchedRollout(graph='lists'): " + why)
 
     def steps(self, model, n):
         """n rollout steps.  Small teams (the one-launch step): the launches of all n steps are enqueued by ONE

@@ -452,6 +452,42 @@ int gnnpp_policy_team_fwd(const float* obs, const void* S, const float* enc_pack
                           float* logits, int B, int N, int K, int E, int s_is_f64, int precision,
                           int* range_flag, void* stream, void* workspace, size_t workspace_bytes);
 
+/* Neighbour lists as an INPUT format of the team filter (the symbols below were added without a version change, like
+ * the team calls above).  A lists block is the head of the team workspace: team_layout with graphs = (s_batched ? B : 1)
+ * * E, every region 16-byte aligned, Np = N rounded up to 4:
+ *     int32 cnt [graphs][N] | uint16 idx [graphs][N][Np] | fp32 val [graphs][N][Np]
+ * Column n of graph g (g = b * E + e, or e for a shared graph) holds cnt entries (row index, weight) in ASCENDING row
+ * order, padded with (0, 0.0f) up to the next multiple of four entries; entries behind the padding are unspecified and
+ * never read.  Node n gathers z[n] = sum_j val[n][j] * z_prev[idx[n][j]] as an fmaf chain in list order.
+ * Validity is the CALLER's contract -- the filter calls do not inspect a block: 0 <= cnt <= N, every index < N, the
+ * padding present, the block at least gnnpp_team_lists_bytes(graphs, N) bytes.
+ *   gnnpp_team_lists_bytes        size of the block; 0 for graphs <= 0 or N outside 1 .. GNNPP_ROLLOUT_MAX_TEAM.
+ *   gnnpp_team_lists_from_dense   the lists of the non-zeros of S [graphs][N][N] (fp32, or fp64 rounded like
+ *                                 `S.float()`): the launch the dense-S team calls make on every call, as a call of
+ *                                 its own.  One launch.
+ *   gnnpp_lsigf_team_lists_fwd / gnnpp_filter_head_team_lists_fwd / gnnpp_policy_team_lists_fwd
+ *                                 the three team calls with `const void* S, int s_is_f64` replaced by `const void* lists`:
+ *                                 no list launch, bit-identical outputs to the dense-S call on the S the lists were made
+ *                                 from.  `workspace` keeps its size (gnnpp_lsigf_team_workspace_bytes) and holds the tap
+ *                                 signals z; its lists region goes unused.  lists may be NULL at K = 1.
+ * Errors (checked before any HIP call, nothing enqueued or written): a NULL pointer, a size out of range, a block or
+ * workspace that is misaligned or too small: GNNPP_ERR_ARG; G or F > 128, split-f16: GNNPP_ERR_UNSUPPORTED.
+ * No atomics, one writer per element (two calls give the same bytes), capturable in a HIP graph. */
+size_t gnnpp_team_lists_bytes(int graphs, int N);
+int gnnpp_team_lists_from_dense(const void* S, void* lists, size_t lists_bytes, int graphs, int N, int s_is_f64,
+                                void* stream);
+int gnnpp_lsigf_team_lists_fwd(const float* x, const void* lists, const float* packed, const float* bias, float* y,
+                               void* workspace, size_t workspace_bytes, int B, int N, int G, int F, int K, int E,
+                               int s_batched, int relu, int bias_per_node, int precision, void* stream);
+int gnnpp_filter_head_team_lists_fwd(const float* x, const void* lists, const float* packed, const float* bias,
+                                     const float* act_w, const float* act_b, float* logits, void* workspace,
+                                     size_t workspace_bytes, int B, int N, int G, int F, int K, int E, int precision,
+                                     void* stream);
+int gnnpp_policy_team_lists_fwd(const float* obs, const void* lists, const float* enc_packed, const float* filt_packed,
+                                const float* gf_bias, const float* act_w, const float* act_b, float* feat_ws,
+                                float* logits, int B, int N, int K, int E, int precision, int* range_flag, void* stream,
+                                void* workspace, size_t workspace_bytes);
+
 /* ------------------------------------------------------------------------------------------
  * Batched rollout step around the forward (B independent episodes resident on the device):
  *   gnnpp_rollout_observe  AgentState.toInputTensor             dataloader/statetransformer.py:82-130
@@ -527,6 +563,15 @@ int gnnpp_rollout_move(const gnnpp_rollout* r, void* stream);
  * on the positions, so their workgroups run side by side (large teams, where one workgroup per episode is too
  * little for gnnpp_rollout_step).  Same results as the two calls. */
 int gnnpp_rollout_gso_observe(const gnnpp_rollout* r, void* stream);
+/* gnnpp_rollout_gso with the graph delivered as the team filter's neighbour lists (see "Neighbour lists as an INPUT
+ * format" above; graphs = B) instead of a dense S: the block equals, over cnt and the first roundup4(cnt) entries of
+ * every column, what gnnpp_team_lists_from_dense makes of gnnpp_rollout_gso's S on the same state (every weight is at
+ * least 1 / 1023, so no edge is lost as a zero); radius and connected are the same to the bit.  r->S is ignored and may
+ * be NULL; radius, connected and grow as for gnnpp_rollout_gso; the map is not used.  Any 1 <= N <=
+ * GNNPP_ROLLOUT_MAX_TEAM (one workgroup per episode, one thread per agent: csrc/rollout_team_lists_kernel.hip).
+ * lists: gnnpp_team_lists_bytes(B, N) bytes, 16-byte aligned; NULL, misaligned or too small: GNNPP_ERR_ARG, nothing
+ * enqueued.  One launch, no atomics, two calls give the same bytes, capturable. */
+int gnnpp_rollout_lists(const gnnpp_rollout* r, void* lists, size_t lists_bytes, void* stream);
 /* move -> gso (grow = 0) -> observe of the new positions in ONE launch: the simulator work between
  * two policy forwards of a rollout (the loop agents/decentralplannerlocal.py:560-599 runs move,
  * then getCurrentState + getGSO of the next iteration).  Same results as the three calls in
