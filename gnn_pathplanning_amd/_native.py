@@ -42,7 +42,8 @@ EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get
            'gnnpp_schedule_team_samples', 'gnnpp_lsigf_team_workspace_bytes', 'gnnpp_lsigf_team_fwd',
            'gnnpp_filter_head_team_fwd', 'gnnpp_policy_team_fwd', 'gnnpp_team_lists_bytes',
            'gnnpp_team_lists_from_dense', 'gnnpp_rollout_lists', 'gnnpp_lsigf_team_lists_fwd',
-           'gnnpp_filter_head_team_lists_fwd', 'gnnpp_policy_team_lists_fwd')
+           'gnnpp_filter_head_team_lists_fwd', 'gnnpp_policy_team_lists_fwd', 'gnnpp_team_lists_transpose',
+           'gnnpp_lsigf_team_lists_fwd_save', 'gnnpp_lsigf_team_lists_input_grad')
 
 
 class GnnppError(RuntimeError):
@@ -306,6 +307,12 @@ def _bind(path):
     L.gnnpp_filter_head_team_lists_fwd.restype = ci
     L.gnnpp_policy_team_lists_fwd.argtypes = [vp] * 9 + [ci] * 5 + [vp, vp, vp, cs]
     L.gnnpp_policy_team_lists_fwd.restype = ci
+    L.gnnpp_team_lists_transpose.argtypes = [vp, vp, cs, ci, ci, vp]
+    L.gnnpp_team_lists_transpose.restype = ci
+    L.gnnpp_lsigf_team_lists_fwd_save.argtypes = [vp] * 7 + [cs] + [ci] * 10 + [vp]
+    L.gnnpp_lsigf_team_lists_fwd_save.restype = ci
+    L.gnnpp_lsigf_team_lists_input_grad.argtypes = [vp] * 5 + [cs] + [ci] * 7 + [vp]
+    L.gnnpp_lsigf_team_lists_input_grad.restype = ci
     L.gnnpp_filter_head_mode.argtypes = [ci, ci, ci, ci]
     L.gnnpp_filter_head_mode.restype = ci
     for f in ('gnnpp_rollout_observe', 'gnnpp_rollout_gso', 'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe',

@@ -20,6 +20,7 @@
 #include "policy_filter_kernel.hip"
 #include "lsigf_small_kernel.hip"
 #include "lsigf_team_kernel.hip"   // forward filter / head / policy step for graphs of up to 1024 nodes, spread over workgroups
+#include "lsigf_team_train_kernel.hip"   // ... its training calls: lists of S^T, the forward that keeps the tap signals
 #include "rollout_team_lists_kernel.hip"   // the rollout's communication graph as the team filter's neighbour lists
 #include "train_encoder.hip"
 #include "train_ops.hip"
@@ -354,6 +355,35 @@ int gnnpp_policy_team_lists_fwd(const float* obs, const void* lists, const float
     a.B = B; a.N = N; a.G = GNNPP_FEAT; a.F = GNNPP_FEAT; a.K = K; a.E = E;
     a.s_batched = 1; a.relu = 1;
     return team_launch(a, workspace, precision, st, K > 1 ? lists : nullptr);
+}
+
+int gnnpp_team_lists_transpose(const void* lists, void* lists_t, size_t lists_bytes, int graphs, int N, void* stream) {
+    if (lists == lists_t || !team_lists_block_ok(lists, lists_bytes, graphs, N) ||
+        !team_lists_block_ok(lists_t, lists_bytes, graphs, N))
+        return GNNPP_ERR_ARG;
+    return team_transpose_launch(lists, lists_t, graphs, N, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_lsigf_team_lists_fwd_save(const float* x, const void* lists, const float* packed, const float* bias, float* y,
+                                    float* zs, void* workspace, size_t workspace_bytes, int B, int N, int G, int F,
+                                    int K, int E, int s_batched, int relu, int bias_per_node, int precision,
+                                    void* stream) {
+    if (!y || !zs) return GNNPP_ERR_ARG;
+    const int rc = team_lists_check(x, lists, packed, workspace, workspace_bytes, B, N, G, F, K, E, s_batched, precision);
+    if (rc) return rc;
+    TeamArgs a = {};
+    a.x = x; a.wpk = packed; a.bias = bias; a.y = y;
+    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
+    a.s_batched = s_batched != 0; a.relu = relu; a.bias_per_node = bias && bias_per_node;
+    return team_save_launch(a, K > 1 ? lists : nullptr, zs, precision, static_cast<hipStream_t>(stream));
+}
+
+// the team forward on (dy [B,N,F], lists of S^T, taps of h.permute(3,1,2,0)) -> dx [B,N,G], exact fp32 MFMA
+int gnnpp_lsigf_team_lists_input_grad(const float* dy, const void* lists_t, const float* packed_t, float* dx,
+                                      void* workspace, size_t workspace_bytes, int B, int N, int G, int F, int K,
+                                      int E, int s_batched, void* stream) {
+    return gnnpp_lsigf_team_lists_fwd(dy, lists_t, packed_t, nullptr, dx, workspace, workspace_bytes, B, N, F, G, K, E,
+                                      s_batched, 0, 0, GNNPP_PREC_FP32_MFMA, stream);
 }
 
 int gnnpp_filter_head_mode(int B, int N, int K, int precision) {

@@ -224,8 +224,10 @@ __global__ __launch_bounds__(256) void team_shift_kernel(const TeamArgs p, int k
 // ---- 3. last shift + contraction + epilogue -------------------------------------------------------------------------
 // RT = 16-row MFMA tiles per workgroup; MODE 2 = bf16x3 planes (GNNPP_PREC_FP32), 1 = exact fp32 MFMA.
 // Wave w owns the 16-feature output tiles mt = w and w + 4 for all RT row tiles.
-template <int RT, int MODE>
-__global__ __launch_bounds__(256) void team_tail_kernel(const TeamArgs p) {
+// SAVED (lsigf_team_train_kernel.hip): every tap signal, the last one included, is a copy from p.z laid out as
+// zs [E*K][B*N][G] with row stride G -- no gather here; p.x_vec then says whether THOSE rows can be read 16 bytes at a time.
+template <int RT, int MODE, bool SAVED>
+__device__ __forceinline__ void team_tail_body(const TeamArgs& p) {
     extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
     constexpr int R = 16 * RT;
     constexpr int kBuf = MODE == 2 ? R * kTeamPRow : R * kTeamZs * 4;       // bytes of one tap's tile
@@ -263,8 +265,13 @@ __global__ __launch_bounds__(256) void team_tail_kernel(const TeamArgs p) {
             }
             // the workgroup's rows of z_{e,k}: a half wave per row, four features per lane
             char* const buf = gnnpp_smem + (tap & 1) * kBuf;
-            const bool last_shift = K > 1 && k == K - 1;
-            const TeamSrc src = team_signal(p, e, last_shift ? k - 1 : k, b);
+            const bool last_shift = !SAVED && K > 1 && k == K - 1;
+            TeamSrc src;
+            if (SAVED) {
+                src.rows = p.z + ((size_t)tap * p.B + b) * N * p.G; src.stride = p.G; src.G = p.G; src.vec = p.x_vec != 0;
+            } else {
+                src = team_signal(p, e, last_shift ? k - 1 : k, b);
+            }
             const size_t lbase = ((size_t)(p.s_batched ? b : 0) * p.E + e) * N;
             for (int i = tid >> 5; i < R; i += 8) {
                 const int row = r0 + i;
@@ -394,6 +401,11 @@ __global__ __launch_bounds__(256) void team_tail_kernel(const TeamArgs p) {
             }
         }
     }
+}
+
+template <int RT, int MODE>
+__global__ __launch_bounds__(256) void team_tail_kernel(const TeamArgs p) {
+    team_tail_body<RT, MODE, false>(p);
 }
 
 template <int RT, int MODE>

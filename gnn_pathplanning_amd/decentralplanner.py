@@ -326,10 +326,16 @@ class DecentralPlannerNet(nn.Module):
         # kernels: neighbour lists, the graph spread over workgroups; _forward_eval).  Training, inputs that require
         # grad and precision='split_f16' keep the dense form under either value.
         self.largeGraphFilter = gml.large_graph_filter(getattr(self.config, 'largeGraphFilter', None))
+        # Optional config field `largeGraphTraining`: how the TRAIN-mode forward treats a GSO of more than graphML.MAX_NODES
+        # nodes -- 'dense' (default: exact fp32 GEMMs over the dense GSO, forward and backward) or 'lists' (neighbour
+        # lists of S and S^T built once per addGSO, every filter layer on graphML.lsigf_team_train; _forward_train).
+        self.largeGraphTraining = gml.large_graph_training(getattr(self.config, 'largeGraphTraining', None))
+        self._train_lists = None                   # (GSO, its version, lists, lists of the transpose) of 'lists' training
         gfl = []
         for l in range(self.L):
             gfl += [gml.GraphFilterBatch(self.F[l], self.F[l + 1], self.K[l], self.E, self.bias,
-                                         largeGraphFilter=self.largeGraphFilter),
+                                         largeGraphFilter=self.largeGraphFilter,
+                                         largeGraphTraining=self.largeGraphTraining),
                     nn.ReLU(inplace=True)]
         self.GFL = nn.Sequential(*gfl)
         self.actionsMLP = nn.Sequential(nn.Linear(self.F[-1], _ACTIONS, bias=True))
@@ -364,6 +370,7 @@ class DecentralPlannerNet(nn.Module):
             assert len(S.shape) == 4
             assert S.shape[1] == self.E
             self.__dict__['S'] = S
+        self.__dict__['_train_lists'] = None       # (largeGraphTraining='lists': rebuilt by the next train-mode forward)
 
     def _encoder_tensors(self):
         """The 32 tensors the packed encoder depends on.  Walking nn.Sequential / __getattr__ costs
@@ -818,6 +825,26 @@ class DecentralPlannerNet(nn.Module):
                 _native.check(rc, 'gnnpp_filter_head_team_lists_fwd')
                 return logits
 
+    def _train_encoder(self, inputTensor, with_packs=False):
+        """The train-mode encoder over all agents (_EncoderTrainFunction): features [B,N,128] (and the step's packs)."""
+        _native.require_gpu(inputTensor, self.compressMLP[0].weight)
+        B, N = inputTensor.shape[0], self.numAgents
+        obs = inputTensor.detach()
+        if obs.shape[1] != N:
+            obs = obs[:, :N]
+        obs = obs.contiguous().float()
+        tensors, buffers = [], []
+        eps, momentum, track = self._bn_settings(True)
+        for ci, bi in zip(_CONV_IDX, _BN_IDX):
+            conv, bn = self.ConvLayers[ci], self.ConvLayers[bi]
+            tensors += [conv.weight, conv.bias, bn.weight, bn.bias]
+            buffers += [bn.running_mean, bn.running_var]
+        counters = [self.ConvLayers[bi].num_batches_tracked for bi in _BN_IDX] if track else None   # += N each
+        packs = self._train_packs(tensors)                                              # one launch per weight version
+        feat = _EncoderTrainFunction.apply(obs, buffers if track else None, counters, float(momentum or 0.0),
+                                           float(eps), packs[0] if packs else None, *tensors)   # [B,N,128]
+        return (feat, packs) if with_packs else feat
+
     def _forward_train(self, inputTensor):
         """Differentiable train-mode forward with the reference's semantics (decentralplanner.py:278-318).
         Hand-written HIP: the per-agent ConvLayers calls (BatchNorm with THAT call's batch statistics, N
@@ -834,20 +861,7 @@ class DecentralPlannerNet(nn.Module):
             raise TypeError('addGSO() must be called before forward()')
         _native.require_gpu(inputTensor, self.S, self.compressMLP[0].weight)
         B, N = inputTensor.shape[0], self.numAgents
-        obs = inputTensor.detach()
-        if obs.shape[1] != N:
-            obs = obs[:, :N]
-        obs = obs.contiguous().float()
-        tensors, buffers = [], []
-        eps, momentum, track = self._bn_settings(True)
-        for ci, bi in zip(_CONV_IDX, _BN_IDX):
-            conv, bn = self.ConvLayers[ci], self.ConvLayers[bi]
-            tensors += [conv.weight, conv.bias, bn.weight, bn.bias]
-            buffers += [bn.running_mean, bn.running_var]
-        counters = [self.ConvLayers[bi].num_batches_tracked for bi in _BN_IDX] if track else None   # += N each
-        packs = self._train_packs(tensors)                                              # one launch per weight version
-        feat = _EncoderTrainFunction.apply(obs, buffers if track else None, counters, float(momentum or 0.0),
-                                           float(eps), packs[0] if packs else None, *tensors)   # [B,N,128]
+        feat, packs = self._train_encoder(inputTensor, True)
         fc = self.compressMLP[0]
         if self.S.shape[0] != B:
             raise _native.GnnppError('addGSO() was given %d graphs, the input has %d samples' % (self.S.shape[0], B))
@@ -859,6 +873,13 @@ class DecentralPlannerNet(nn.Module):
         # filter's own into the action head's dx product (`fold` bit 0 <-> mask_dx) -- when the filter's input / output
         # ARE those tensors (no zero-padded nodes in between) and the filter runs on the LDS-resident kernels.
         direct = Ns == N and Ns <= gml.MAX_NODES
+        if Ns > gml.MAX_NODES and self.largeGraphTraining == 'lists':
+            ent = self._train_lists                # the lists of S and of S^T: two launches, once per addGSO
+            if ent is None or ent[0] is not self.S or ent[1] != self.S._version:
+                lists = gml.team_lists_from_dense(self.S)
+                ent = (self.S, self.S._version, lists, gml.team_lists_transpose(lists, B * self.E, Ns))
+                self.__dict__['_train_lists'] = ent
+            return self._train_tail_lists(feat, ent[2], ent[3], B, N, Ns)
         # (`direct`: the head's and the filter's parameter-gradient products wait for the compress layer's backward launch)
         x = _LinearFunction.apply(feat, fc.weight, fc.bias, 2 if direct else 1, False, 2 if direct else 0)   # [B,N,F]
         # every activation stays node-major [B,N,*] (the layout the filter kernel keeps in LDS): no transposing
@@ -875,6 +896,49 @@ class DecentralPlannerNet(nn.Module):
                 x = x[:, :N]                       # an activation nor a cotangent passes them from layer to layer
         act = self.actionsMLP[0]
         return _LinearFunction.apply(x, act.weight, act.bias, 0, direct, 1 if direct else 0).permute(1, 0, 2)   # [N,B,5]
+
+    def _train_tail_lists(self, feat, lists, lists_t, B, N, Ns):
+        """compressMLP, the filter layers on graphML.lsigf_team_train and the action head for encoder features feat
+        [B,N,128] and the neighbour lists of a graph of Ns >= N nodes: largeGraphTraining='lists'.  The per-layer zero
+        padding of the dense route is kept; no ReLU backward is folded (large teams never run `direct`)."""
+        if self._prec() == _native.PREC_SPLIT_F16:
+            raise _native.GnnppError("largeGraphTraining='lists': precision 'split_f16' has no team kernels; use "
+                                     "largeGraphTraining='dense'")
+        fc, act = self.compressMLP[0], self.actionsMLP[0]
+        x = _LinearFunction.apply(feat, fc.weight, fc.bias, 1, False, 0)                  # [B,N,F]
+        for l in range(self.L):
+            gf = self.GFL[2 * l]
+            if Ns != N:                            # every layer zero-pads its input again (graphML.py:2464-2476) ...
+                x = torch.cat([x, x.new_zeros(B, Ns - N, x.shape[2])], 1)
+            x = gf.forward_node_major_lists(x, lists, lists_t, relu=True)                 # [B,Ns,F_l]
+            if Ns != N:                            # ... and drops its outputs there
+                x = x[:, :N]
+        return _LinearFunction.apply(x, act.weight, act.bias, 0, False, 0).permute(1, 0, 2)   # [N,B,5]
+
+    def forward_train_lists(self, inputTensor, lists, lists_t=None, symmetric=False):
+        """The train-mode forward with the communication graph given as NEIGHBOUR LISTS instead of addGSO's dense matrix:
+        `lists` is a block of B * E graphs of numAgents nodes (graphML.team_lists_from_dense, or
+        BatchedRollout(graph='lists').gso()), lists_t the block of the transposed graphs (None: one
+        graphML.team_lists_transpose launch here; symmetric=True: the caller's promise that S = S^T bit for bit, `lists`
+        serves both directions).  The route of largeGraphTraining='lists' without the dense GSO, at any team size;
+        returns what forward() returns in train mode.  Needs train mode, layers of up to 128 features and not split-f16
+        (GnnppError otherwise)."""
+        if not self.training:
+            raise _native.GnnppError('forward_train_lists is the train-mode forward (call model.train()); '
+                                     'forward_logits_lists is the eval-mode one')
+        B, N = inputTensor.shape[0], self.numAgents
+        need = gml.team_lists_bytes(B * self.E, N)
+        for blk in (lists, lists_t):
+            if blk is not None and (blk.dtype is not torch.uint8 or blk.dim() != 1 or blk.numel() != need
+                                    or blk.data_ptr() % 16):
+                raise _native.GnnppError('forward_train_lists: the lists must be a 16-byte aligned uint8 block of %d '
+                                         'bytes (%d x %d graphs of the team\'s %d nodes)' % (need, B, self.E, N))
+        if symmetric:
+            lists_t = lists
+        elif lists_t is None:
+            lists_t = gml.team_lists_transpose(lists, B * self.E, N)
+        feat = self._train_encoder(inputTensor)
+        return LogitList(self._train_tail_lists(feat, lists, lists_t, B, N, N))
 
     def _train_packs(self, conv_tensors):
         """(encoder train pack, filter taps forward, filter taps transposed) of the CURRENT weights by ONE

@@ -79,7 +79,8 @@ def _bias_arg(b, F_out, N):
 
 # How an eval-mode, no-grad filter call treats graphs of more than MAX_NODES nodes: 'dense' (default) = _lsigf_large
 # (exact fp32 GEMMs over the dense S), 'lists' = lsigf_team (neighbour lists, the graph spread over workgroups; G, F <=
-# 128, not split-f16).  The two round differently, which is why the default stays.  Training always takes the dense form.
+# 128, not split-f16).  The two round differently, which is why the default stays.  Training has a field of its own
+# (LARGE_GRAPH_TRAININGS below).
 LARGE_GRAPH_FILTERS = ('dense', 'lists')
 TEAM_MAX_NODES = 1024   # GNNPP_ROLLOUT_MAX_TEAM
 
@@ -222,6 +223,146 @@ def lsigf_team(h, S, x, b, relu=False, precision=None, workspace=None, packed=No
                                     int(precision), st)
     _native.check(rc, 'gnnpp_lsigf_team_fwd')
     return y
+
+
+# How a TRAIN-mode filter call treats graphs of more than MAX_NODES nodes: 'dense' (default) = _lsigf_large /
+# _lsigf_large_backward (exact fp32 GEMMs over the dense S), 'lists' = lsigf_team_train (neighbour lists of S and S^T; G,
+# F <= 128, N <= TEAM_MAX_NODES, not split-f16 -- GnnppError otherwise, no fallback).  A field of its own: largeGraphFilter
+# alone leaves training on the dense route, bit for bit.
+LARGE_GRAPH_TRAININGS = ('dense', 'lists')
+
+
+def large_graph_training(name):
+    name = 'dense' if name is None else name
+    if name not in LARGE_GRAPH_TRAININGS:
+        raise _native.GnnppError('unknown largeGraphTraining %r (one of %s)' % (name, list(LARGE_GRAPH_TRAININGS)))
+    return name
+
+
+def team_lists_transpose(block, graphs, N, out=None):
+    """The lists block of S^T for the lists block of S (`graphs` graphs of N nodes; gnnpp_team_lists_transpose): column m
+    of the result holds every n with m in column n of `block`, in ascending n, with the same weight.  One launch, no
+    dense matrix.  out: a block of the same size to write into (not `block` itself)."""
+    dev = _native.require_gpu(block, out)
+    team_lists_views(block, graphs, N)                                 # (size, dtype, alignment)
+    if out is None:
+        out = torch.empty(team_lists_bytes(graphs, N), dtype=torch.uint8, device=dev)
+    else:
+        team_lists_views(out, graphs, N)
+    with _native.device_guard(dev):
+        rc = _native.lib().gnnpp_team_lists_transpose(_ptr(block), _ptr(out), min(block.numel(), out.numel()),
+                                                      int(graphs), int(N), _native.stream_ptr(dev))
+    _native.check(rc, 'gnnpp_team_lists_transpose')
+    team_train_calls['transpose'] += 1
+    return out
+
+
+# launches of the team training calls made through this module since import (tests and tools read the differences)
+team_train_calls = {'transpose': 0, 'fwd_save': 0, 'input_grad': 0}
+
+
+def _team_train_refusal(N, G, F_out, precision):
+    """Why lsigf_team_train cannot serve a layer -- None when it can."""
+    if _native.precision_code(DEFAULT_PRECISION if precision is None else precision) == _native.PREC_SPLIT_F16:
+        return "precision 'split_f16' has no team kernels"
+    if N > TEAM_MAX_NODES or G > 128 or F_out > 128:
+        return ('the team kernels serve graphs of up to %d nodes and layers of up to 128 features (got %d nodes, %d -> %d '
+                'features)' % (TEAM_MAX_NODES, N, G, F_out))
+    return None
+
+
+class _TeamTrainFunction(torch.autograd.Function):
+    """lsigf_team_train: forward = gnnpp_lsigf_team_lists_fwd_save, backward = gnnpp_lsigf_team_lists_input_grad on the
+    lists of S^T (dx) and one gnnpp_gemm_kmajor_multi launch over the saved tap signals (dh, db)."""
+
+    @staticmethod
+    def forward(ctx, h, x, b, lists, lists_t, relu, precision, batched):
+        dev = _native.require_gpu(h, x, b, lists, lists_t)
+        L = _native.lib()
+        F_out, E, K, G = h.shape
+        B, N = x.shape[0], x.shape[1]
+        xc = x.detach().contiguous()
+        if xc.dtype != torch.float32:
+            xc = xc.float()
+        bias, per_node = _bias_arg(b, F_out, N)
+        y = torch.empty(B, N, F_out, dtype=torch.float32, device=dev)
+        zs = torch.empty(E * K, B * N, G, dtype=torch.float32, device=dev)
+        with _native.device_guard(dev):
+            st = _native.stream_ptr(dev)
+            ws = team_workspace(B, N, G, K, E, batched, dev, st.value)
+            rc = L.gnnpp_lsigf_team_lists_fwd_save(_ptr(xc), _ptr(lists) if K > 1 else None, _ptr(_cached_pack(h, False)),
+                                                   _ptr(bias), _ptr(y), _ptr(zs), _ptr(ws), ws.numel(), B, N, G, F_out,
+                                                   K, E, int(batched), int(relu), per_node, int(precision), st)
+        _native.check(rc, 'gnnpp_lsigf_team_lists_fwd_save')
+        team_train_calls['fwd_save'] += 1
+        ctx.save_for_backward(h, zs, y if relu else None, lists_t)
+        ctx.relu, ctx.batched = bool(relu), bool(batched)
+        ctx.bias_ref, ctx.bias_shape = b, None if b is None else tuple(b.shape)
+        ctx.param_ptrs = (h.data_ptr(), b.data_ptr() if b is not None else 0)    # (_native.grad_out: gradient sinks)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, zs, yrelu, lists_t = ctx.saved_tensors
+        F_out, E, K, G = h.shape
+        B, N = dy.shape[0], dy.shape[1]
+        dev = dy.device
+        dy = dy.contiguous().float()
+        if ctx.relu:
+            dy = torch.ops.aten.threshold_backward(dy, yrelu, 0)          # dy where y > 0, else 0
+        dh = dx = db = None
+        if ctx.needs_input_grad[1]:
+            dx = torch.empty(B, N, G, dtype=torch.float32, device=dev)
+            with _native.device_guard(dev):
+                st = _native.stream_ptr(dev)
+                ws = team_workspace(B, N, F_out, K, E, ctx.batched, dev, st.value)
+                rc = _native.lib().gnnpp_lsigf_team_lists_input_grad(
+                    _ptr(dy), _ptr(lists_t) if K > 1 else None, _ptr(_packed_transposed_taps(h)), _ptr(dx), _ptr(ws),
+                    ws.numel(), B, N, G, F_out, K, E, int(ctx.batched), st)
+            _native.check(rc, 'gnnpp_lsigf_team_lists_input_grad')
+            team_train_calls['input_grad'] += 1
+        specs = []
+        if ctx.needs_input_grad[0]:                                       # (the specs of _LSIGFFunction._backward_node_major)
+            dh = _native.grad_out(ctx.param_ptrs[0], (F_out, E, K, G), dev)
+            specs.append((dy, (0, 1, F_out), zs, (B * N * G, G), dh, (G, E * K * G), E * K, F_out, G, B * N))
+        if ctx.bias_ref is not None and ctx.needs_input_grad[2]:
+            if ctx.bias_shape[-1] == 1 or len(ctx.bias_shape) == 1:
+                db = _native.grad_out(ctx.param_ptrs[1], ctx.bias_shape, dev)                # sum over (b, n)
+                specs.append((_ones(B * N, dev), (0, 0, 1), dy, (0, F_out), db, (0, F_out), 1, 1, F_out, B * N))
+            else:                                                         # per-node bias [F,N]: sum over b
+                db = dy.sum(dim=0).t().contiguous().reshape(ctx.bias_shape)
+        if specs:
+            _native.gemm_kmajor_multi(specs)
+        return dh, dx, db, None, None, None, None, None
+
+
+def lsigf_team_train(h, lists, x, b, relu=False, precision=None, lists_t=None, symmetric=False, batched=True):
+    """The DIFFERENTIABLE filter on neighbour lists for graphs of up to TEAM_MAX_NODES nodes, node-major:
+    h [F,E,K,G], lists (a block of (B if batched else 1) * E graphs of N nodes), x [B,N,G], b [F,1] | [F,N] | None ->
+    [B,N,F], with gradients for h, x and b (none for the lists).  The forward keeps the tap signals
+    (gnnpp_lsigf_team_lists_fwd_save: E K B N G floats); the input gradient is the same filter on the lists of S^T
+    (gnnpp_lsigf_team_lists_input_grad, exact fp32), the tap and bias gradients one multi-product GEMM launch.
+    lists_t: the block of S^T (team_lists_transpose); None builds it here, once, and saves it for the backward pass.
+    symmetric: the caller's promise that S = S^T bit for bit (D^-1/2 A D^-1/2 of the simulator and the expert): `lists`
+    serves both directions.  G or F > 128 and precision='split_f16' raise GnnppError: there is no fallback behind this
+    call."""
+    _native.require_gpu(h, lists, x, b, lists_t)
+    F_out, E, K, G = h.shape
+    B, N = x.shape[0], x.shape[1]
+    assert x.shape[2] == G
+    why = _team_train_refusal(N, G, F_out, precision)
+    if why:
+        raise _native.GnnppError('lsigf_team_train: ' + why)
+    graphs = (B if batched else 1) * E
+    team_lists_views(lists, graphs, N)
+    if symmetric:
+        lists_t = lists
+    elif lists_t is None:
+        lists_t = team_lists_transpose(lists, graphs, N) if K > 1 and _wants_grad(x) else lists
+    else:
+        team_lists_views(lists_t, graphs, N)
+    prec = _native.precision_code(DEFAULT_PRECISION if precision is None else precision)
+    return _TeamTrainFunction.apply(h, x, b, lists, lists_t, bool(relu), prec, bool(batched))
 
 
 def _large_tap_signals(h, S, x, batched):
@@ -603,10 +744,12 @@ def BatchLSIGF(h, S, x, b=None, precision=None):
 class _GraphFilterBase(nn.Module):
     _batched = False
 
-    def __init__(self, G, F, K, E=1, bias=True, precision=None, largeGraphFilter=None):
+    def __init__(self, G, F, K, E=1, bias=True, precision=None, largeGraphFilter=None, largeGraphTraining=None):
         super().__init__()
         # eval-mode, no-grad calls on graphs of more than MAX_NODES nodes: 'dense' (default) | 'lists' (LARGE_GRAPH_FILTERS)
         self.largeGraphFilter = large_graph_filter(largeGraphFilter)
+        # train-mode calls on such graphs: 'dense' (default) | 'lists' (LARGE_GRAPH_TRAININGS; forward_node_major_lists)
+        self.largeGraphTraining = large_graph_training(largeGraphTraining)
         self.G = G
         self.F = F
         self.K = K
@@ -670,6 +813,17 @@ class _GraphFilterBase(nn.Module):
         return _LSIGFFunction.apply(self.weight, self.S, x, self.bias, self._batched,
                                     packed if packed is not None else self.packed_taps(), True,
                                     bool(relu), self.precision, packed_T, fold)
+
+    def forward_node_major_lists(self, x, lists, lists_t, relu=False, batched=True):
+        """forward_node_major with the graph as neighbour lists of S (`lists`) and S^T (`lists_t`) instead of addGSO's
+        dense matrix: lsigf_team_train, the route of largeGraphTraining='lists'.  A layer it does not serve raises."""
+        N, dev = x.shape[1], x.device
+        why = _team_train_refusal(N, self.G, self.F, self.precision)
+        if why:
+            raise _native.GnnppError("largeGraphTraining='lists': %s; use largeGraphTraining='dense'" % why)
+        assert x.shape[2] == self.G and dev == self.weight.device
+        return lsigf_team_train(self.weight, lists, x, self.bias, relu=relu, precision=self.precision, lists_t=lists_t,
+                                batched=batched)
 
     def extra_repr(self):
         s = 'in_features=%d, out_features=%d, ' % (self.G, self.F)

@@ -488,6 +488,39 @@ int gnnpp_policy_team_lists_fwd(const float* obs, const void* lists, const float
                                 float* logits, int B, int N, int K, int E, int precision, int* range_flag, void* stream,
                                 void* workspace, size_t workspace_bytes);
 
+/* TRAINING the team filter on neighbour lists (added without a version change, like the lists calls above;
+ * csrc/lsigf_team_train_kernel.hip).  The input gradient of the filter is the filter on S^T with the taps of
+ * h.permute(3,1,2,0): dx = sum_k W_k^T . dy . (S^T)^k.
+ *   gnnpp_team_lists_transpose    lists_t := the block of S^T for the block `lists` of S (graphs graphs of N nodes, both
+ *                                 of lists_bytes >= gnnpp_team_lists_bytes(graphs, N) bytes): column m of lists_t holds
+ *                                 every n with m in column n of lists, in ascending n, with the same weight, then
+ *                                 (0, 0.0f) up to a multiple of four entries.  No dense matrix, one launch.  The
+ *                                 validity of `lists` is the caller's contract (ascending indices, 0 <= cnt <= N); an
+ *                                 invalid block gives unspecified lists but never a write outside lists_t.
+ *                                 lists == lists_t, NULL, a misaligned pointer or a block too small: GNNPP_ERR_ARG.
+ *   gnnpp_lsigf_team_lists_fwd_save
+ *                                 gnnpp_lsigf_team_lists_fwd that also writes every tap signal to zs [E*K][B*N][G]
+ *                                 (node-major, row stride G: the layout of gnnpp_lsigf_fwd_save; tap (e, 0) is a copy of
+ *                                 x).  One shift launch per k = 1 .. K-1 and the tail, which stages all K taps from zs.
+ *                                 y is BYTE-IDENTICAL to gnnpp_lsigf_team_lists_fwd on the same arguments, in both
+ *                                 precisions.  `workspace` is validated like that call's and not written.
+ *   gnnpp_lsigf_team_lists_input_grad
+ *                                 dx [B,N,G] for dy [B,N,F]: gnnpp_lsigf_team_lists_fwd(dy, lists_t, packed_t, no bias,
+ *                                 dx, ..., G := F, F := G, no ReLU, GNNPP_PREC_FP32_MFMA), byte for byte.  packed_t:
+ *                                 gnnpp_filter_pack of h.permute(3,1,2,0) [G,E,K,F]; workspace:
+ *                                 gnnpp_lsigf_team_workspace_bytes(B, N, F, K, E, s_batched).
+ * The tap and bias gradients are gnnpp_gemm_kmajor_multi products over zs.  Limits and errors as the lists calls: 1 <=
+ * G, F <= 128 (any value), N <= GNNPP_ROLLOUT_MAX_TEAM, split-f16 GNNPP_ERR_UNSUPPORTED; nothing enqueued on failure;
+ * no atomics, one writer per element, capturable. */
+int gnnpp_team_lists_transpose(const void* lists, void* lists_t, size_t lists_bytes, int graphs, int N, void* stream);
+int gnnpp_lsigf_team_lists_fwd_save(const float* x, const void* lists, const float* packed, const float* bias, float* y,
+                                    float* zs, void* workspace, size_t workspace_bytes, int B, int N, int G, int F,
+                                    int K, int E, int s_batched, int relu, int bias_per_node, int precision,
+                                    void* stream);
+int gnnpp_lsigf_team_lists_input_grad(const float* dy, const void* lists_t, const float* packed_t, float* dx,
+                                      void* workspace, size_t workspace_bytes, int B, int N, int G, int F, int K,
+                                      int E, int s_batched, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Batched rollout step around the forward (B independent episodes resident on the device):
  *   gnnpp_rollout_observe  AgentState.toInputTensor             dataloader/statetransformer.py:82-130
