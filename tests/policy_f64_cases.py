@@ -79,10 +79,12 @@ def encoder_statement(sd, obs, dt, acts=None):
     return t
 
 
-def filter_stack(h, S4, p, N):
+def filter_stack(h, S4, p, N, relu=None):
     """The L graph-filter layers with their ReLUs (decentralplanner.py:293-301): h [B,F,N] -> [B,F',N].  S4
     [B,E,Ns,Ns] in h's dtype (a GSO with more nodes than agents zero-pads the signal); p holds GFL.{2l}.weight
-    [F',E,K,F] and .bias [F',1].  Also the training step's statement (tests/test_gpu_training_f64.py)."""
+    [F',E,K,F] and .bias [F',1].  Also the training step's statement (tests/test_gpu_training_f64.py).
+    relu(name, pre-activation), name = 'GFL.<2l>': the activation, for the tests that look at a layer's pre-activation
+    or state a defect of its backward pass (tests/train_freeze_cases.py); None = ReLU."""
     B, Ns = h.shape[0], S4.shape[-1]
     l = 0
     while 'GFL.%d.weight' % (2 * l) in p:
@@ -97,7 +99,7 @@ def filter_stack(h, S4, p, N):
                 y = y + torch.einsum('fg,bgn->bfn', w[:, e, k], z)
         if b is not None:
             y = y + b
-        h = tF.relu(y[:, :, :N])
+        h = tF.relu(y[:, :, :N]) if relu is None else relu('GFL.%d' % (2 * l), y[:, :, :N])
         l += 1
     return h
 

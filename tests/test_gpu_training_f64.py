@@ -43,13 +43,16 @@ def dev():
 
 
 # ---- the float64 statement -----------------------------------------------------------------------------------------
-def statement(sd, S, obs, tgt, N, dtype):
+def statement(sd, S, obs, tgt, N, dtype, frozen=None, relu=None):
     """One training step's forward and backward in `dtype` on the CPU, after the reference (agents/
     decentralplannerlocal.py:287-317 over graphs/models/decentralplanner.py:278-318): per-agent train-mode encoder calls
     (BatchNorm over that call's batch, N sequential running-statistics updates), compressMLP, the L graph-filter layers
     with their ReLUs (a GSO with more nodes than agents zero-pads the signal), the action head, the loss = mean over
-    agents of CrossEntropy against the first arg-max of the target, every gradient by autograd."""
-    p = {k: v.to(dtype).clone().requires_grad_(True) for k, v in sd.items()
+    agents of CrossEntropy against the first arg-max of the target, every gradient by autograd.
+    frozen(name): the parameters that take no gradient (requires_grad_(False) and nothing else: train-mode BatchNorm of a
+    frozen encoder still uses batch statistics and updates the running ones) -- they are absent from 'grads'.
+    relu(name, pre-activation), name = 'compress' | 'GFL.<2l>': as policy_f64_cases.filter_stack."""
+    p = {k: v.to(dtype).clone().requires_grad_(not (frozen is not None and frozen(k))) for k, v in sd.items()
          if v.dtype.is_floating_point and 'running' not in k}
     run = {k: v.to(dtype).clone() for k, v in sd.items() if 'running' in k}
     nbt = {k: int(v) for k, v in sd.items() if 'num_batches' in k}
@@ -68,17 +71,19 @@ def statement(sd, S, obs, tgt, N, dtype):
             if orc.POOL_AFTER[li]:
                 t = tF.max_pool2d(t, 2)
         enc.append(t.reshape(B, 128))
-        comp.append(tF.relu(tF.linear(enc[-1], p['compressMLP.0.weight'], p['compressMLP.0.bias'])))
+        pre = tF.linear(enc[-1], p['compressMLP.0.weight'], p['compressMLP.0.bias'])
+        comp.append(tF.relu(pre) if relu is None else relu('compress', pre))
     h = torch.stack(comp, 2)                                             # [B,F,N]
     S4 = (S.unsqueeze(1) if S.dim() == 3 else S).to(dtype)               # [B,E,Ns,Ns]
-    h = filter_stack(h, S4, p, N)
+    h = filter_stack(h, S4, p, N, relu)
     logits = torch.stack([tF.linear(h[:, :, n], p['actionsMLP.0.weight'], p['actionsMLP.0.bias'])
                           for n in range(N)], 1)                          # [B,N,5]
     labels = tgt.argmax(-1)                                              # first maximum
     loss = sum(tF.cross_entropy(logits[:, n], labels[:, n]) for n in range(N)) / N
-    loss.backward()
+    if loss.requires_grad:
+        loss.backward()
     return dict(loss=loss.detach(), logits=logits.detach(), feat=torch.stack(enc, 1).detach(),
-                grads={k: v.grad for k, v in p.items()}, running=run, nbt=nbt)
+                grads={k: v.grad for k, v in p.items() if v.requires_grad}, running=run, nbt=nbt)
 
 
 def without_pool_near_ties(sd, obs, draw, tau=(1e-5, 0, 2e-6, 0, 2e-6), rounds=50):
@@ -285,6 +290,19 @@ def _step(dev, dp, sd, obs, S, tgt, N, K, L, E, via_step, adam, widths=None):
     return res
 
 
+def grad_scale(k, g64, B, N):
+    """The scale the yardstick's floor is taken of for the gradient of parameter k (None: the gradient's own largest
+    entry); g64: the float64 gradients by name."""
+    li = CONV.index(int(k.split('.')[1])) if k.startswith('ConvLayers.') and int(k.split('.')[1]) in CONV else None
+    if li is not None and k.endswith('.bias'):
+        return g64['ConvLayers.%d.weight' % CONV[li]].abs().max().item() * np.sqrt(B * POS[li])
+    if k.endswith('.bias') and not k.startswith('ConvLayers.'):
+        # a sum over all N x B rows of terms that nearly cancel (softmax - one-hot): its roundoff grows with the
+        # square root of the row count, in units of the result's own scale
+        return g64[k].abs().max().item() * np.sqrt(B * N)
+    return None
+
+
 def check_against_f64(got, w64, w32, B, N):
     bad = []
 
@@ -301,16 +319,7 @@ def check_against_f64(got, w64, w32, B, N):
         bad.append(('loss', rep, 'max |d logit| %.3g' % dlog))
     cmp('feat', got['feat'], w64['feat'], w32['feat'])
     for k, g in got['grads'].items():
-        li = CONV.index(int(k.split('.')[1])) if k.startswith('ConvLayers.') and int(k.split('.')[1]) in CONV else None
-        if li is not None and k.endswith('.bias'):
-            wscale = w64['grads']['ConvLayers.%d.weight' % CONV[li]].abs().max().item()
-            cmp(k, g, w64['grads'][k], w32['grads'][k], wscale * np.sqrt(B * POS[li]))
-        elif k.endswith('.bias') and not k.startswith('ConvLayers.'):
-            # a sum over all N x B rows of terms that nearly cancel (softmax - one-hot): its roundoff grows with the
-            # square root of the row count, in units of the result's own scale
-            cmp(k, g, w64['grads'][k], w32['grads'][k], w64['grads'][k].abs().max().item() * np.sqrt(B * N))
-        else:
-            cmp(k, g, w64['grads'][k], w32['grads'][k])
+        cmp(k, g, w64['grads'][k], w32['grads'][k], grad_scale(k, w64['grads'], B, N))
     for k, r in got['running'].items():
         cmp(k, r, w64['running'][k], w32['running'][k])
     for k, c in got['nbt'].items():
