@@ -447,9 +447,10 @@ _defer_depth = 0
 class allow_deferred_gemms:
     """Deferral is OPT-IN per backward pass: training.train_step (and with it GraphedTrainStep) runs its backward inside
     this context.  A plain `loss.backward()` of a caller of the reference API computes every gradient inside the node
-    that returns it, as autograd's contract says -- a tensor hook on a parameter, or the post-accumulate hooks
-    torch.nn.parallel.DistributedDataParallel hangs on every parameter's AccumulateGrad node, READ the gradient the
-    moment the node has returned it and would see a queued product's still-uncomputed buffer."""
+    that returns it, as autograd's contract says.  Inside the context hooks are honoured too: a tensor hook or a
+    post-accumulate-grad hook on a parameter READS the gradient the moment the node has returned it (and a tensor hook
+    may replace it), so a node whose parameters carry one -- or have a `.grad` already, or run under anomaly detection --
+    computes its products at once (may_defer, decided per node); only the other nodes' products wait."""
 
     def __enter__(self):
         global _defer_depth
@@ -468,6 +469,25 @@ class allow_deferred_gemms:
 
 def deferral_allowed():
     return _defer_depth > 0
+
+
+def may_defer(*params):
+    """May the products that yield the gradients of `params` (None entries are skipped) wait in the queue?  Only inside
+    allow_deferred_gemms, and only when nothing can read or replace the gradient before the flush: every parameter is a
+    leaf without a `.grad` (autograd then only stores the tensor it is handed) and without tensor hooks or
+    post-accumulate-grad hooks (both run the moment the node returns, on a buffer the queue has not filled yet, and a
+    hook's returned gradient would be overwritten at flush time); anomaly detection reads every gradient for NaNs as
+    well.  Decided per backward node: a hook on one layer costs that layer's deferral only."""
+    import torch
+    if _defer_depth <= 0 or torch.is_anomaly_enabled():
+        return False
+    for p in params:
+        if p is None:
+            continue
+        if (not p.is_leaf or p.grad is not None or p._backward_hooks
+                or getattr(p, '_post_accumulate_grad_hooks', None)):
+            return False
+    return True
 
 
 def defer_gemms(specs, params):

@@ -514,6 +514,8 @@ int gnnpp_linear_fwd(const float* x, const float* W, const float* bias, float* y
                      void* stream) {
     if (!x || !W || !y || R <= 0 || I <= 0 || O <= 0) return GNNPP_ERR_ARG;
     if (I % 64 != 0 || ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(W)) & 15)) return GNNPP_ERR_UNSUPPORTED;
+    // (O % 4 == 0: every row of y is stored as 16-byte vectors)
+    if ((O & 3) == 0 && (reinterpret_cast<size_t>(y) & 15)) return GNNPP_ERR_UNSUPPORTED;
     const int tiles = ((O + 15) / 16) * ((R + 15) / 16);
     hipLaunchKernelGGL(linear_fwd_kernel, dim3((tiles + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), x, W,
                        bias, y, R, I, O, relu);

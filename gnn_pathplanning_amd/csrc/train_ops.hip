@@ -212,12 +212,23 @@ __global__ __launch_bounds__(1024) void policy_loss_kernel(const float* __restri
             mx = fmaxf(mx, lg[c]);
         }
         float se = 0.f;
-        for (int c = 0; c < C; ++c) se += expf(lg[c] - mx);
+        double sd = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const float ec = expf(lg[c] - mx);
+            se += ec;
+            sd += (double)ec;
+        }
         const float lse = mx + logf(se);
         part += (double)(lse - lg[label]);
-        if (dlogits)
+        // softmax = exp(x - max) / sum with the sum of the SAME terms taken in double, NOT exp(x - lse): lse is rounded at
+        // the size of the largest logit (half a unit in the last place of 80 is 2^-18 of every probability of the row)
+        // and an fp32 sum of 64 terms carries several units itself -- the row would no longer sum to 1 (nor the
+        // gradient row to 0) to fp32 accuracy
+        if (dlogits) {
+            const float sf = (float)sd;
             for (int c = 0; c < C; ++c)
-                dlogits[row * C + c] = (expf(lg[c] - lse) - (c == label ? 1.f : 0.f)) * inv;
+                dlogits[row * C + c] = (expf(lg[c] - mx) / sf - (c == label ? 1.f : 0.f)) * inv;
+        }
     }
     red[threadIdx.x] = part;
     __syncthreads();

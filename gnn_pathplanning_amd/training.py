@@ -167,8 +167,9 @@ def train_step(model, optimizer, batch_input, batch_target, batch_GSO, dp=None):
         # loss and d loss / d logits from one launch; backward starts at the logits (what loss.backward() does,
         # minus the ones_like fill and the multiplication by it)
         loss, dlogits = _policy_loss_and_grad(stacked, batch_target)
-        # (this step owns its backward pass -- no hooks read a gradient before the pass has ended --, so the products that
-        # only yield parameter gradients may wait for one later launch of the pass: _native.allow_deferred_gemms)
+        # (this step owns its backward pass, so the products that only yield parameter gradients may wait for one later
+        # launch of the pass: _native.allow_deferred_gemms.  A parameter with a tensor hook or a post-accumulate-grad hook
+        # is read before the pass has ended: its node computes at once -- _native.may_defer decides per node)
         with _native.allow_deferred_gemms():
             stacked.backward(dlogits)
     else:

@@ -312,7 +312,8 @@ int gnnpp_lsigf_input_grad(const float* dy, const void* S, const float* packed_t
 /* y = x W^T + bias (+ ReLU): forward of compressMLP (Linear 128 -> 128 + ReLU, decentralplanner.py:187-195, :289-290)
  * and of actionsMLP (Linear 128 -> 5, :232-243, :304-315) in the training step.  x [R,I], W [O,I] (nn.Linear's layout),
  * bias [O] or NULL, y [R,O].  Exact fp32 MFMA, fixed summation order.  I must be a multiple of 64 and x, W 16-byte
- * aligned (GNNPP_ERR_UNSUPPORTED otherwise).  (v330; r05 ran these as library GEMMs + an aten ReLU.) */
+ * aligned; where O is a multiple of 4 the rows of y are stored as 16-byte vectors and y must be 16-byte aligned too
+ * (GNNPP_ERR_UNSUPPORTED otherwise).  (v330; r05 ran these as library GEMMs + an aten ReLU.) */
 int gnnpp_linear_fwd(const float* x, const float* W, const float* bias, float* y, int R, int I, int O, int relu,
                      void* stream);
 
@@ -348,7 +349,9 @@ int gnnpp_gemm_kmajor_multi(const gnnpp_gemm_desc* d, int count, float* workspac
 /* The training loop's loss (agents/decentralplannerlocal.py:296-312), forward and backward in one launch:
  *   logits [N,B,C] (agent-major: the list forward() returns, stacked), target [B,N,C] one-hot expert actions;
  *   loss[0] = (1/N) sum_n CrossEntropyLoss(logits[n], argmax_c target[:, n])   (first maximum, like torch.max);
- *   dlogits [N,B,C] = d loss / d logits, or NULL.  C <= 64.
+ *   dlogits [N,B,C] = d loss / d logits, or NULL.  C <= 64.  The softmax in it is exp(x - max) / sum with the sum of
+ *   those terms taken in double (not exp(x - logsumexp), which is rounded at the size of the largest logit): every
+ *   gradient row sums to 0 within a few units in the last place of 1 / (N B), whatever the size of the logits.
  *   logits_sample_major != 0: logits and dlogits are [B,N,C] (the layout the train-mode forward computes). */
 int gnnpp_policy_loss(const float* logits, const float* target, float* loss, float* dlogits, int B, int N,
                       int C, int logits_sample_major, void* stream);

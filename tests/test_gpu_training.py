@@ -580,6 +580,137 @@ def test_deferred_parameter_gradient_products(dev):
     assert not _native._deferred_gemms and torch.equal(gh, once['GFL.0.weight'])
 
 
+class _DeferralSetup:
+    """The planner of test_deferred_parameter_gradient_products (B, N, K = 16, 10, 3), the reference gradients of a plain
+    backward pass WITHOUT deferral -- of policy_loss(...) ('plain') and of policy_loss_fused(...) ('fused': the loss
+    launch train_step() starts its backward from, whose d loss / d logits has other last bits than aten's) --, and a
+    counter of what _native.defer_gemms is handed."""
+    B, N, K = 16, 10, 3
+    HOOKED = ('actionsMLP.0.weight', 'actionsMLP.0.bias', 'GFL.0.weight', 'GFL.0.bias')
+
+    def __init__(self, dev):
+        from gnn_pathplanning_amd.training import policy_loss, policy_loss_fused
+        B, N = self.B, self.N
+        self.dev = dev
+        self.sd0 = orc.init_state_dict(self.K, seed=21)
+        self.obs = orc.synth_obs(B, N, seed=21).to(dev)
+        self.S = torch.from_numpy(orc.synth_gso_geometric(B, N, 20, seed=21)).float().to(dev)
+        gen = torch.Generator().manual_seed(1)
+        self.tgt = torch.nn.functional.one_hot(torch.randint(0, 5, (B, N), generator=gen), 5).float().to(dev)
+        self.ref = {}
+        for kind, lossf in (('plain', policy_loss), ('fused', policy_loss_fused)):
+            net = self.fresh()
+            lossf(net(self.obs), self.tgt).backward()
+            self.ref[kind] = {k: p.grad.clone() for k, p in net.named_parameters()}
+
+    def fresh(self):
+        from gnn_pathplanning_amd.decentralplanner import DecentralPlannerNet
+
+        class C:
+            num_agents, nGraphFilterTaps, device = self.N, self.K, self.dev
+        net = DecentralPlannerNet(C()).to(self.dev)
+        net.load_state_dict(self.sd0)
+        net.train()
+        net.addGSO(self.S)
+        return net
+
+    def run(self, net, how):
+        """'step': training.train_step (reference 'fused'); 'backward': loss.backward() inside allow_deferred_gemms
+        (reference 'plain').  Returns (reference gradients, the number of products of every defer_gemms call)."""
+        from gnn_pathplanning_amd import _native
+        from gnn_pathplanning_amd.training import policy_loss, train_step
+        queued = []
+        orig_defer = _native.defer_gemms
+        _native.defer_gemms = lambda specs, prms: (queued.append(len(specs)), orig_defer(specs, prms))[1]
+        try:
+            if how == 'step':
+                train_step(net, torch.optim.SGD(net.parameters(), lr=0.0), self.obs, self.tgt, self.S)
+            else:
+                with _native.allow_deferred_gemms():
+                    policy_loss(net(self.obs), self.tgt).backward()
+        finally:
+            _native.defer_gemms = orig_defer
+        assert not _native._deferred_gemms
+        return self.ref['fused' if how == 'step' else 'plain'], queued
+
+    def same(self, net, ref, scaled=()):
+        for k, p in net.named_parameters():
+            assert torch.equal(p.grad, 2 * ref[k] if k in scaled else ref[k]), k
+
+
+@pytest.fixture(scope='module')
+def deferral(dev):
+    return _DeferralSetup(dev)
+
+
+@pytest.mark.parametrize('how', ['step', 'backward'])
+def test_deferral_tensor_hooks_see_the_computed_gradient(deferral, how):
+    """Tensor hooks that clone what they receive, on the head's and the filter's weight and bias, inside a pass that
+    allows deferral: every hook saw the reference gradient (not a buffer the queue had yet to fill), and so is .grad."""
+    net = deferral.fresh()
+    prm = dict(net.named_parameters())
+    seen = {}
+    for k in deferral.HOOKED:
+        prm[k].register_hook(lambda g, k=k: seen.__setitem__(k, g.clone()))
+    ref, queued = deferral.run(net, how)
+    assert queued == [] and set(seen) == set(deferral.HOOKED)
+    for k in deferral.HOOKED:
+        assert torch.equal(seen[k], ref[k]), k
+    deferral.same(net, ref)
+
+
+@pytest.mark.parametrize('how', ['step', 'backward'])
+def test_deferral_keeps_the_gradient_a_hook_returns(deferral, how):
+    """A hook that returns 2 g: .grad is twice the reference (the flush must not write over what the hook returned)."""
+    net = deferral.fresh()
+    prm = dict(net.named_parameters())
+    for k in deferral.HOOKED:
+        prm[k].register_hook(lambda g: 2 * g)
+    ref, _ = deferral.run(net, how)
+    deferral.same(net, ref, scaled=deferral.HOOKED)
+
+
+@pytest.mark.parametrize('how', ['step', 'backward'])
+def test_deferral_post_accumulate_hook_sees_the_computed_gradient(deferral, how):
+    """register_post_accumulate_grad_hook on the head's weight copies p.grad: it saw the reference."""
+    net = deferral.fresh()
+    seen = {}
+    net.actionsMLP[0].weight.register_post_accumulate_grad_hook(lambda p: seen.__setitem__('w', p.grad.clone()))
+    ref, queued = deferral.run(net, how)
+    assert torch.equal(seen['w'], ref['actionsMLP.0.weight'])
+    assert queued == [2]                                     # (the filter's node carries no hook)
+    deferral.same(net, ref)
+
+
+@pytest.mark.parametrize('how', ['step', 'backward'])
+def test_deferral_is_decided_per_node(deferral, how):
+    """Hooks on the head only: the head's products run at once, the filter's two still wait (one defer_gemms call of two
+    products, not two), and nothing is left in the queue."""
+    net = deferral.fresh()
+    seen = {}
+    net.actionsMLP[0].weight.register_hook(lambda g: seen.__setitem__('w', g.clone()))
+    ref, queued = deferral.run(net, how)
+    assert queued == [2]
+    assert torch.equal(seen['w'], ref['actionsMLP.0.weight'])
+    deferral.same(net, ref)
+    net2 = deferral.fresh()                                  # a removed hook costs nothing: both nodes defer again
+    net2.actionsMLP[0].weight.register_hook(lambda g: g).remove()
+    ref, queued = deferral.run(net2, how)
+    assert queued == [2, 2]
+    deferral.same(net2, ref)
+
+
+@pytest.mark.parametrize('how', ['step', 'backward'])
+def test_deferral_is_off_under_anomaly_detection(deferral, how):
+    """torch.autograd.set_detect_anomaly(True) reads every gradient a node returns: nothing is queued, the pass
+    completes, the gradients are the reference."""
+    net = deferral.fresh()
+    with torch.autograd.set_detect_anomaly(True):
+        ref, queued = deferral.run(net, how)
+    assert queued == []
+    deferral.same(net, ref)
+
+
 def test_fused_adam_and_loss_match_torch(dev):
     """The one-launch pieces of the optimisation step against stock torch on the same model and batches:
     policy_loss_fused == policy_loss (value and gradient of every parameter), and FusedAdam (gnnpp_adam_step)
