@@ -56,30 +56,11 @@ int gnnpp_filter_pack(const float* h, float* packed, int G, int F, int K, int E,
 
 // One launch covers F <= 128 output features; wider filters run as several launches over
 // output-feature chunks inside lsigf_launch (each chunk recomputes the cheap shifts).
-int gnnpp_lsigf_fwd(const float* x, const void* S, const float* packed, const float* bias,
-                    float* y, int B, int N, int Nin, int G, int F, int K, int E, int s_is_f64,
-                    int s_batched, int x_node_major, int y_node_major, int relu, int bias_per_node,
-                    int precision, int* range_flag, void* stream) {
-    if (!x || !packed || !y || B <= 0 || N <= 0 || Nin <= 0 || Nin > N || G <= 0 || F <= 0 ||
-        K <= 0 || E <= 0 || precision < 0 || precision > 2)
-        return GNNPP_ERR_ARG;
-    if (K > 1 && !S) return GNNPP_ERR_ARG;
-    if ((x_node_major || y_node_major) && Nin != N) return GNNPP_ERR_ARG;
-    if (N > GNNPP_MAX_ROWS) return GNNPP_ERR_UNSUPPORTED;
-    LsigfArgs a = {};
-    a.x = x; a.S = S; a.wpk = packed; a.bias = bias; a.y = y;
-    a.B = B; a.N = N; a.Nin = Nin; a.G = G; a.F = F; a.K = K; a.E = E;
-    a.s_is_f64 = s_is_f64; a.s_batched = s_batched;
-    a.x_node_major = x_node_major; a.y_node_major = y_node_major; a.relu = relu;
-    a.bias_per_node = bias && bias_per_node; a.range_flag = range_flag; a.prec = precision;
-    return lsigf_launch(a, static_cast<hipStream_t>(stream));
-}
-
-int gnnpp_lsigf_fwd_save(const float* x, const void* S, const float* packed, const float* bias,
-                         float* y, float* zs, int B, int N, int Nin, int G, int F, int K, int E,
-                         int s_is_f64, int s_batched, int s_transposed, int x_node_major,
-                         int y_node_major, int relu, int bias_per_node, int precision, int* range_flag,
-                         void* stream) {
+// gnnpp_lsigf_fwd is this body without the tap signals (zs) and on S itself (s_transposed = 0).
+static int lsigf_fwd_body(const float* x, const void* S, const float* packed, const float* bias, float* y, float* zs,
+                          int B, int N, int Nin, int G, int F, int K, int E, int s_is_f64, int s_batched,
+                          int s_transposed, int x_node_major, int y_node_major, int relu, int bias_per_node,
+                          int precision, int* range_flag, void* stream) {
     if (!x || !packed || !y || B <= 0 || N <= 0 || Nin <= 0 || Nin > N || G <= 0 || F <= 0 ||
         K <= 0 || E <= 0 || precision < 0 || precision > 2)
         return GNNPP_ERR_ARG;
@@ -93,6 +74,23 @@ int gnnpp_lsigf_fwd_save(const float* x, const void* S, const float* packed, con
     a.x_node_major = x_node_major; a.y_node_major = y_node_major; a.relu = relu;
     a.bias_per_node = bias && bias_per_node; a.range_flag = range_flag; a.prec = precision;
     return lsigf_launch(a, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_lsigf_fwd(const float* x, const void* S, const float* packed, const float* bias,
+                    float* y, int B, int N, int Nin, int G, int F, int K, int E, int s_is_f64,
+                    int s_batched, int x_node_major, int y_node_major, int relu, int bias_per_node,
+                    int precision, int* range_flag, void* stream) {
+    return lsigf_fwd_body(x, S, packed, bias, y, nullptr, B, N, Nin, G, F, K, E, s_is_f64, s_batched, 0, x_node_major,
+                          y_node_major, relu, bias_per_node, precision, range_flag, stream);
+}
+
+int gnnpp_lsigf_fwd_save(const float* x, const void* S, const float* packed, const float* bias,
+                         float* y, float* zs, int B, int N, int Nin, int G, int F, int K, int E,
+                         int s_is_f64, int s_batched, int s_transposed, int x_node_major,
+                         int y_node_major, int relu, int bias_per_node, int precision, int* range_flag,
+                         void* stream) {
+    return lsigf_fwd_body(x, S, packed, bias, y, zs, B, N, Nin, G, F, K, E, s_is_f64, s_batched, s_transposed,
+                          x_node_major, y_node_major, relu, bias_per_node, precision, range_flag, stream);
 }
 
 int gnnpp_lsigf_input_grad(const float* dy, const void* S, const float* packed_t, const float* mask, float* dx,
@@ -238,17 +236,27 @@ static int team_check(const void* x, const void* S, const void* packed, const vo
     return GNNPP_OK;
 }
 
+// The TeamArgs of a team call from its arguments.  S = nullptr: the caller's lists take its place (team_launch's last
+// argument); the filter calls pass y, the head calls act_w / act_b / logits.
+static TeamArgs team_args(const float* x, const void* S, int s_is_f64, const float* packed, const float* bias, float* y,
+                          const float* act_w, const float* act_b, float* logits, int B, int N, int G, int F, int K,
+                          int E, int s_batched, int relu, int bias_per_node) {
+    TeamArgs a = {};
+    a.x = x; a.S = S; a.wpk = packed; a.bias = bias; a.y = y; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
+    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
+    a.s_is_f64 = s_is_f64; a.s_batched = s_batched != 0; a.relu = relu; a.bias_per_node = bias && bias_per_node;
+    return a;
+}
+
 int gnnpp_lsigf_team_fwd(const float* x, const void* S, const float* packed, const float* bias, float* y,
                          void* workspace, size_t workspace_bytes, int B, int N, int G, int F, int K, int E,
                          int s_is_f64, int s_batched, int relu, int bias_per_node, int precision, void* stream) {
     if (!y) return GNNPP_ERR_ARG;
     const int rc = team_check(x, S, packed, workspace, workspace_bytes, B, N, G, F, K, E, s_batched, precision);
     if (rc) return rc;
-    TeamArgs a = {};
-    a.x = x; a.S = S; a.wpk = packed; a.bias = bias; a.y = y;
-    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
-    a.s_is_f64 = s_is_f64; a.s_batched = s_batched != 0; a.relu = relu; a.bias_per_node = bias && bias_per_node;
-    return team_launch(a, workspace, precision, static_cast<hipStream_t>(stream));
+    return team_launch(team_args(x, S, s_is_f64, packed, bias, y, nullptr, nullptr, nullptr, B, N, G, F, K, E,
+                                 s_batched, relu, bias_per_node),
+                       workspace, precision, static_cast<hipStream_t>(stream));
 }
 
 int gnnpp_filter_head_team_fwd(const float* x, const void* S, const float* packed, const float* bias,
@@ -258,29 +266,8 @@ int gnnpp_filter_head_team_fwd(const float* x, const void* S, const float* packe
     if (!act_w || !act_b || !logits) return GNNPP_ERR_ARG;
     const int rc = team_check(x, S, packed, workspace, workspace_bytes, B, N, G, F, K, E, 1, precision);
     if (rc) return rc;
-    TeamArgs a = {};
-    a.x = x; a.S = S; a.wpk = packed; a.bias = bias; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
-    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
-    a.s_is_f64 = s_is_f64; a.s_batched = 1; a.relu = 1;
-    return team_launch(a, workspace, precision, static_cast<hipStream_t>(stream));
-}
-
-int gnnpp_policy_team_fwd(const float* obs, const void* S, const float* enc_packed, const float* filt_packed,
-                          const float* gf_bias, const float* act_w, const float* act_b, float* feat_ws,
-                          float* logits, int B, int N, int K, int E, int s_is_f64, int precision,
-                          int* range_flag, void* stream, void* workspace, size_t workspace_bytes) {
-    if (!obs || !enc_packed || !act_w || !act_b || !logits) return GNNPP_ERR_ARG;
-    int rc = team_check(feat_ws, S, filt_packed, workspace, workspace_bytes, B, N, GNNPP_FEAT, GNNPP_FEAT, K, E, 1,
-                        precision);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = encoder_launch(obs, enc_packed, feat_ws, B * N, range_flag, precision, st);
-    if (rc) return rc;
-    TeamArgs a = {};
-    a.x = feat_ws; a.S = S; a.wpk = filt_packed; a.bias = gf_bias; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
-    a.B = B; a.N = N; a.G = GNNPP_FEAT; a.F = GNNPP_FEAT; a.K = K; a.E = E;
-    a.s_is_f64 = s_is_f64; a.s_batched = 1; a.relu = 1;
-    return team_launch(a, workspace, precision, st);
+    return team_launch(team_args(x, S, s_is_f64, packed, bias, nullptr, act_w, act_b, logits, B, N, G, F, K, E, 1, 1, 0),
+                       workspace, precision, static_cast<hipStream_t>(stream));
 }
 
 size_t gnnpp_team_lists_bytes(int graphs, int N) {
@@ -302,7 +289,7 @@ int gnnpp_team_lists_from_dense(const void* S, void* lists, size_t lists_bytes, 
     return team_lists_launch(a, lists, graphs, static_cast<hipStream_t>(stream));
 }
 
-// The three team calls on the caller's lists: team_check with the lists in the place of S (NULL allowed at K = 1), then
+// The team calls on the caller's lists: team_check with the lists in the place of S (NULL allowed at K = 1), then
 // the block's alignment.  Its size is the caller's contract (include/gnnpp.h).
 static int team_lists_check(const void* x, const void* lists, const void* packed, const void* workspace,
                             size_t workspace_bytes, int B, int N, int G, int F, int K, int E, int s_batched,
@@ -318,11 +305,9 @@ int gnnpp_lsigf_team_lists_fwd(const float* x, const void* lists, const float* p
     if (!y) return GNNPP_ERR_ARG;
     const int rc = team_lists_check(x, lists, packed, workspace, workspace_bytes, B, N, G, F, K, E, s_batched, precision);
     if (rc) return rc;
-    TeamArgs a = {};
-    a.x = x; a.wpk = packed; a.bias = bias; a.y = y;
-    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
-    a.s_batched = s_batched != 0; a.relu = relu; a.bias_per_node = bias && bias_per_node;
-    return team_launch(a, workspace, precision, static_cast<hipStream_t>(stream), K > 1 ? lists : nullptr);
+    return team_launch(team_args(x, nullptr, 0, packed, bias, y, nullptr, nullptr, nullptr, B, N, G, F, K, E, s_batched,
+                                 relu, bias_per_node),
+                       workspace, precision, static_cast<hipStream_t>(stream), K > 1 ? lists : nullptr);
 }
 
 int gnnpp_filter_head_team_lists_fwd(const float* x, const void* lists, const float* packed, const float* bias,
@@ -332,29 +317,42 @@ int gnnpp_filter_head_team_lists_fwd(const float* x, const void* lists, const fl
     if (!act_w || !act_b || !logits) return GNNPP_ERR_ARG;
     const int rc = team_lists_check(x, lists, packed, workspace, workspace_bytes, B, N, G, F, K, E, 1, precision);
     if (rc) return rc;
-    TeamArgs a = {};
-    a.x = x; a.wpk = packed; a.bias = bias; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
-    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
-    a.s_batched = 1; a.relu = 1;
-    return team_launch(a, workspace, precision, static_cast<hipStream_t>(stream), K > 1 ? lists : nullptr);
+    return team_launch(team_args(x, nullptr, 0, packed, bias, nullptr, act_w, act_b, logits, B, N, G, F, K, E, 1, 1, 0),
+                       workspace, precision, static_cast<hipStream_t>(stream), K > 1 ? lists : nullptr);
+}
+
+// gnnpp_policy_team_fwd and _lists_fwd: the encoder into feat_ws, then the filter + head on it.  `graph` is the dense S,
+// or with from_lists the caller's lists block.
+static int policy_team(const float* obs, const void* graph, bool from_lists, int s_is_f64, const float* enc_packed,
+                       const float* filt_packed, const float* gf_bias, const float* act_w, const float* act_b,
+                       float* feat_ws, float* logits, int B, int N, int K, int E, int precision, int* range_flag,
+                       void* stream, void* workspace, size_t workspace_bytes) {
+    if (!obs || !enc_packed || !act_w || !act_b || !logits) return GNNPP_ERR_ARG;
+    int rc = (from_lists ? team_lists_check : team_check)(feat_ws, graph, filt_packed, workspace, workspace_bytes, B, N,
+                                                          GNNPP_FEAT, GNNPP_FEAT, K, E, 1, precision);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = encoder_launch(obs, enc_packed, feat_ws, B * N, range_flag, precision, st);
+    if (rc) return rc;
+    return team_launch(team_args(feat_ws, from_lists ? nullptr : graph, s_is_f64, filt_packed, gf_bias, nullptr, act_w,
+                                 act_b, logits, B, N, GNNPP_FEAT, GNNPP_FEAT, K, E, 1, 1, 0),
+                       workspace, precision, st, from_lists && K > 1 ? graph : nullptr);
+}
+
+int gnnpp_policy_team_fwd(const float* obs, const void* S, const float* enc_packed, const float* filt_packed,
+                          const float* gf_bias, const float* act_w, const float* act_b, float* feat_ws,
+                          float* logits, int B, int N, int K, int E, int s_is_f64, int precision,
+                          int* range_flag, void* stream, void* workspace, size_t workspace_bytes) {
+    return policy_team(obs, S, false, s_is_f64, enc_packed, filt_packed, gf_bias, act_w, act_b, feat_ws, logits, B, N, K,
+                       E, precision, range_flag, stream, workspace, workspace_bytes);
 }
 
 int gnnpp_policy_team_lists_fwd(const float* obs, const void* lists, const float* enc_packed, const float* filt_packed,
                                 const float* gf_bias, const float* act_w, const float* act_b, float* feat_ws,
                                 float* logits, int B, int N, int K, int E, int precision, int* range_flag, void* stream,
                                 void* workspace, size_t workspace_bytes) {
-    if (!obs || !enc_packed || !act_w || !act_b || !logits) return GNNPP_ERR_ARG;
-    int rc = team_lists_check(feat_ws, lists, filt_packed, workspace, workspace_bytes, B, N, GNNPP_FEAT, GNNPP_FEAT, K,
-                              E, 1, precision);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = encoder_launch(obs, enc_packed, feat_ws, B * N, range_flag, precision, st);
-    if (rc) return rc;
-    TeamArgs a = {};
-    a.x = feat_ws; a.wpk = filt_packed; a.bias = gf_bias; a.act_w = act_w; a.act_b = act_b; a.logits = logits;
-    a.B = B; a.N = N; a.G = GNNPP_FEAT; a.F = GNNPP_FEAT; a.K = K; a.E = E;
-    a.s_batched = 1; a.relu = 1;
-    return team_launch(a, workspace, precision, st, K > 1 ? lists : nullptr);
+    return policy_team(obs, lists, true, 0, enc_packed, filt_packed, gf_bias, act_w, act_b, feat_ws, logits, B, N, K, E,
+                       precision, range_flag, stream, workspace, workspace_bytes);
 }
 
 int gnnpp_team_lists_transpose(const void* lists, void* lists_t, size_t lists_bytes, int graphs, int N, void* stream) {
@@ -371,11 +369,9 @@ int gnnpp_lsigf_team_lists_fwd_save(const float* x, const void* lists, const flo
     if (!y || !zs) return GNNPP_ERR_ARG;
     const int rc = team_lists_check(x, lists, packed, workspace, workspace_bytes, B, N, G, F, K, E, s_batched, precision);
     if (rc) return rc;
-    TeamArgs a = {};
-    a.x = x; a.wpk = packed; a.bias = bias; a.y = y;
-    a.B = B; a.N = N; a.G = G; a.F = F; a.K = K; a.E = E;
-    a.s_batched = s_batched != 0; a.relu = relu; a.bias_per_node = bias && bias_per_node;
-    return team_save_launch(a, K > 1 ? lists : nullptr, zs, precision, static_cast<hipStream_t>(stream));
+    return team_save_launch(team_args(x, nullptr, 0, packed, bias, y, nullptr, nullptr, nullptr, B, N, G, F, K, E,
+                                      s_batched, relu, bias_per_node),
+                            K > 1 ? lists : nullptr, zs, precision, static_cast<hipStream_t>(stream));
 }
 
 // the team forward on (dy [B,N,F], lists of S^T, taps of h.permute(3,1,2,0)) -> dx [B,N,G], exact fp32 MFMA
@@ -703,26 +699,26 @@ int gnnpp_rollout_gso_observe(const gnnpp_rollout* r, void* stream) {
     return rollout_gso_observe_launch(*r, static_cast<hipStream_t>(stream));
 }
 
-int gnnpp_rollout_move(const gnnpp_rollout* r, void* stream) {
-    if (!rollout_common_ok(r) || !r->grid || !r->goal || (!r->logits && !r->actions) ||
+// what gnnpp_rollout_move, _step and _policy_step share: the map, the actions' source, the episode's bookkeeping and a
+// tie mode with the inputs it reads
+static bool rollout_move_ok(const gnnpp_rollout* r, int max_agents = GNNPP_ROLLOUT_MAX_TEAM) {
+    if (!rollout_common_ok(r, max_agents) || !r->grid || !r->goal || (!r->logits && !r->actions) ||
         !r->reached || !r->start_step || !r->end_step || !r->maxstep || !r->flags || !r->stats ||
         r->H <= 0 || r->W <= 0)
-        return GNNPP_ERR_ARG;
-    if (r->tie_mode == GNNPP_TIE_REPLAY && (!r->choices || r->max_choices <= 0)) return GNNPP_ERR_ARG;
-    if (r->tie_mode < 0 || r->tie_mode > 3) return GNNPP_ERR_ARG;
-    if (r->tie_mode == GNNPP_TIE_MT19937 && (!r->rng_words || !r->rng_cursor || r->rng_max <= 0)) return GNNPP_ERR_ARG;
+        return false;
+    if (r->tie_mode == GNNPP_TIE_REPLAY && (!r->choices || r->max_choices <= 0)) return false;
+    if (r->tie_mode < 0 || r->tie_mode > 3) return false;
+    return !(r->tie_mode == GNNPP_TIE_MT19937 && (!r->rng_words || !r->rng_cursor || r->rng_max <= 0));
+}
+
+int gnnpp_rollout_move(const gnnpp_rollout* r, void* stream) {
+    if (!rollout_move_ok(r)) return GNNPP_ERR_ARG;
     if (rollout_team(r)) return rollout_team_move_launch(*r, static_cast<hipStream_t>(stream));
     return rollout_move_launch(*r, static_cast<hipStream_t>(stream));
 }
 
 int gnnpp_rollout_step(const gnnpp_rollout* r, void* stream) {
-    if (!rollout_common_ok(r) || !r->grid || !r->goal || !r->obs || !r->radius || !r->S ||
-        (!r->logits && !r->actions) || !r->reached || !r->start_step || !r->end_step || !r->maxstep ||
-        !r->flags || !r->stats || r->H <= 0 || r->W <= 0)
-        return GNNPP_ERR_ARG;
-    if (r->tie_mode == GNNPP_TIE_REPLAY && (!r->choices || r->max_choices <= 0)) return GNNPP_ERR_ARG;
-    if (r->tie_mode < 0 || r->tie_mode > 3) return GNNPP_ERR_ARG;
-    if (r->tie_mode == GNNPP_TIE_MT19937 && (!r->rng_words || !r->rng_cursor || r->rng_max <= 0)) return GNNPP_ERR_ARG;
+    if (!rollout_move_ok(r) || !r->obs || !r->radius || !r->S) return GNNPP_ERR_ARG;
     if (rollout_team(r)) return rollout_team_step_launch(*r, static_cast<hipStream_t>(stream));
     return rollout_step_launch(*r, static_cast<hipStream_t>(stream));
 }
@@ -730,15 +726,9 @@ int gnnpp_rollout_step(const gnnpp_rollout* r, void* stream) {
 int gnnpp_rollout_policy_step(const gnnpp_rollout* r, const float* enc_packed, const float* filt_packed,
                               const float* gf_bias, const float* act_w, const float* act_b, int K,
                               int precision, void* stream) {
-    if (!rollout_common_ok(r, GNNPP_ROLLOUT_MAX_AGENTS) || !r->grid || !r->goal || !r->obs || !r->radius || !r->S ||
-        !r->logits ||
-        !r->reached || !r->start_step || !r->end_step || !r->maxstep || !r->flags || !r->stats ||
-        r->H <= 0 || r->W <= 0 || !enc_packed || !filt_packed || !act_w || !act_b)
+    if (!rollout_move_ok(r, GNNPP_ROLLOUT_MAX_AGENTS) || !r->obs || !r->radius || !r->S || !r->logits ||
+        !enc_packed || !filt_packed || !act_w || !act_b || precision < 0 || precision > 2)
         return GNNPP_ERR_ARG;
-    if (r->tie_mode == GNNPP_TIE_REPLAY && (!r->choices || r->max_choices <= 0)) return GNNPP_ERR_ARG;
-    if (r->tie_mode < 0 || r->tie_mode > 3) return GNNPP_ERR_ARG;
-    if (r->tie_mode == GNNPP_TIE_MT19937 && (!r->rng_words || !r->rng_cursor || r->rng_max <= 0)) return GNNPP_ERR_ARG;
-    if (precision < 0 || precision > 2) return GNNPP_ERR_ARG;
     // same conditions as the fused policy kernel of gnnpp_policy_fwd, plus room for the occupancy grid
     const size_t occ_room = precision == kPrecFp32 ? policy_sim_occ_bytes_b3() : policy_sim_occ_bytes(K);
     if (!(fused_policy_applies(r->B, r->N, K, precision) && (size_t)r->H * r->W <= occ_room))
@@ -772,12 +762,16 @@ int gnnpp_rollout_policy_steps(const gnnpp_rollout* r, const float* enc_packed, 
     return GNNPP_OK;
 }
 
-// pointers and sizes first (GNNPP_ERR_ARG), then the supported range: nothing is enqueued on an error
+// pointers and sizes first (GNNPP_ERR_ARG; the team call's workspace among them), then the supported range: nothing is
+// enqueued on an error
+static bool schedules_ok(const gnnpp_schedules* s, int max_agents) {
+    return s && s->grid && s->goal && s->pos && s->case_start && s->obs && s->S && s->target && s->radius &&
+           s->growth && s->status && s->step_info && s->C > 0 && s->T_total > 0 && s->C <= s->T_total && s->N > 0 &&
+           s->N <= max_agents && s->H > 0 && s->W > 0 && s->radius0 > 0.0 && s->radius0 < 1e300;
+}
+
 int gnnpp_schedule_samples(const gnnpp_schedules* s, void* stream) {
-    if (!s || !s->grid || !s->goal || !s->pos || !s->case_start || !s->obs || !s->S || !s->target || !s->radius ||
-        !s->growth || !s->status || !s->step_info || s->C <= 0 || s->T_total <= 0 || s->C > s->T_total || s->N <= 0 ||
-        s->N > GNNPP_ROLLOUT_MAX_AGENTS || s->H <= 0 || s->W <= 0 || !(s->radius0 > 0.0) || !(s->radius0 < 1e300))
-        return GNNPP_ERR_ARG;
+    if (!schedules_ok(s, GNNPP_ROLLOUT_MAX_AGENTS)) return GNNPP_ERR_ARG;
     if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;          // a graph of one node: deg = 0, the reference divides by it
     return schedule_samples_launch(*s, static_cast<hipStream_t>(stream));
 }
@@ -787,15 +781,11 @@ size_t gnnpp_schedule_team_workspace_bytes(int N, int T_total) {
     return schedule_team_workspace_bytes(N, T_total);
 }
 
-// the order of gnnpp_schedule_samples' checks, with the workspace among the arguments
 int gnnpp_schedule_team_samples(const gnnpp_schedules* s, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!s || !s->grid || !s->goal || !s->pos || !s->case_start || !s->obs || !s->S || !s->target || !s->radius ||
-        !s->growth || !s->status || !s->step_info || s->C <= 0 || s->T_total <= 0 || s->C > s->T_total || s->N <= 0 ||
-        s->N > GNNPP_ROLLOUT_MAX_TEAM || s->H <= 0 || s->W <= 0 || !(s->radius0 > 0.0) || !(s->radius0 < 1e300) ||
-        !workspace || (reinterpret_cast<size_t>(workspace) & 7) != 0 ||
+    if (!schedules_ok(s, GNNPP_ROLLOUT_MAX_TEAM) || !workspace || (reinterpret_cast<size_t>(workspace) & 7) != 0 ||
         workspace_bytes < schedule_team_workspace_bytes(s->N, s->T_total))
         return GNNPP_ERR_ARG;
-    if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;          // a graph of one node: deg = 0, the reference divides by it
+    if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;
     return schedule_team_samples_launch(*s, static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
 }
 
@@ -808,12 +798,15 @@ size_t gnnpp_mapf_workspace_bytes(int C, int R, int H, int T_max) {
 
 // pointers and sizes first (GNNPP_ERR_ARG), then the supported map size, then the workspace: nothing is enqueued on
 // an error
+static bool mapf_ok(const gnnpp_mapf* m, int max_agents, int max_steps) {
+    return m && m->grid && m->start && m->goal && m->schedule && m->arrival && m->makespan && m->flowtime &&
+           m->status && m->failing && m->restart && m->workspace && m->C > 0 && m->N > 0 && m->N <= max_agents &&
+           m->H > 0 && m->W > 0 && m->R > 0 && (m->order || m->R == 1) && m->T_max >= 0 && m->T_max <= max_steps &&
+           (long long)m->C * m->R <= 0x7fffffffLL;
+}
+
 int gnnpp_mapf_solve(const gnnpp_mapf* m, void* stream) {
-    if (!m || !m->grid || !m->start || !m->goal || !m->schedule || !m->arrival || !m->makespan || !m->flowtime ||
-        !m->status || !m->failing || !m->restart || !m->workspace || m->C <= 0 || m->N <= 0 ||
-        m->N > GNNPP_ROLLOUT_MAX_AGENTS || m->H <= 0 || m->W <= 0 || m->R <= 0 || (!m->order && m->R != 1) ||
-        m->T_max < 0 || m->T_max > GNNPP_MAPF_MAX_STEPS || (long long)m->C * m->R > 0x7fffffffLL)
-        return GNNPP_ERR_ARG;
+    if (!mapf_ok(m, GNNPP_ROLLOUT_MAX_AGENTS, GNNPP_MAPF_MAX_STEPS)) return GNNPP_ERR_ARG;
     if (m->H > GNNPP_MAPF_MAX_SIDE || m->W > GNNPP_MAPF_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
     if (m->workspace_bytes < mapf_workspace_bytes(m->C, m->R, m->H, m->T_max)) return GNNPP_ERR_ARG;
     return mapf_launch(*m, static_cast<hipStream_t>(stream));
@@ -826,13 +819,9 @@ size_t gnnpp_mapf_team_workspace_bytes(int C, int R, int H, int W, int T_max) {
     return mapf_team_workspace_bytes(C, R, H, W, T_max);
 }
 
-// the order of gnnpp_mapf_solve's checks; the workspace must hold the summary and at least one slot
+// the workspace must hold the summary and at least one slot
 int gnnpp_mapf_team_solve(const gnnpp_mapf* m, void* stream) {
-    if (!m || !m->grid || !m->start || !m->goal || !m->schedule || !m->arrival || !m->makespan || !m->flowtime ||
-        !m->status || !m->failing || !m->restart || !m->workspace || m->C <= 0 || m->N <= 0 ||
-        m->N > GNNPP_ROLLOUT_MAX_TEAM || m->H <= 0 || m->W <= 0 || m->R <= 0 || (!m->order && m->R != 1) ||
-        m->T_max < 0 || m->T_max > GNNPP_MAPF_TEAM_MAX_STEPS || (long long)m->C * m->R > 0x7fffffffLL)
-        return GNNPP_ERR_ARG;
+    if (!mapf_ok(m, GNNPP_ROLLOUT_MAX_TEAM, GNNPP_MAPF_TEAM_MAX_STEPS)) return GNNPP_ERR_ARG;
     if (m->H > GNNPP_MAPF_TEAM_MAX_SIDE || m->W > GNNPP_MAPF_TEAM_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
     const int slots = mapf_team_slots((long long)m->C * m->R, m->R, m->C, m->H, m->W, m->T_max, m->workspace_bytes);
     if (slots < 1) return GNNPP_ERR_ARG;

@@ -35,6 +35,7 @@ import torch.nn as nn
 
 from . import _native
 from . import graphML as gml
+from .graphML import _ones
 from .weights_initializer import weights_init
 
 # The architecture the kernels implement (graphs/models/decentralplanner.py:93-197: 3 -> 32 -> 32 -> 64 -> 64 -> 128
@@ -202,16 +203,6 @@ class _LinearFunction(torch.autograd.Function):
         return (dx.reshape(x.shape) if dx is not None else None), dW, db, None, None, None
 
 
-_ones_cache = {}
-
-
-def _ones(n, device):
-    key = (str(device), n)
-    if key not in _ones_cache:
-        _ones_cache[key] = torch.ones(n, dtype=torch.float32, device=device)
-    return _ones_cache[key]
-
-
 class LogitList(list):
     """The reference's return value -- a python list of N tensors [B,5] -- built as the N views of ONE
     tensor [N,B,5], which stays reachable as .stacked.  Autograd sees one unbind (its backward is one
@@ -285,6 +276,55 @@ class _OutputSlot:
         self.views = views
         self.fresh += 1
         return stacked
+
+
+def planner_route(training, N, Ns, L, E, widths, precision='fp32', largeGraphFilter='dense',
+                  largeGraphTraining='dense'):
+    """The route a forward of a planner takes, by name -- the ONE place that decides it; pure (no device, no module):
+    N agents, a GSO of Ns >= N nodes, L filter layers of output `widths`, E edge features (which never change the
+    route), the precision by name or code.
+      policy_fwd               one gnnpp_policy_fwd call: one layer of 128 features, Ns == N <= graphML.MAX_NODES
+      small_general            encoder, gnnpp_lsigf_fwd per inner layer, gnnpp_filter_head_fwd (Ns <= MAX_NODES)
+      small_general+gemm_head  the same with a last layer wider than 128: gnnpp_lsigf_fwd for it, the head as a GEMM
+      dense                    Ns > MAX_NODES: encoder, graphML._lsigf_large per layer (and split_f16 always)
+      lists / lists_one_call   Ns > MAX_NODES under largeGraphFilter='lists': the team kernels per layer / the one
+                               gnnpp_policy_team_fwd call (one layer of 128 features, Ns == N)
+      train_direct             train mode, Ns == N <= MAX_NODES: the LDS-resident kernels with the ReLU folds
+      train_padded             train mode, N < Ns <= MAX_NODES: the same kernels on the zero-padded signal
+      train_dense / _lists     train mode, Ns > MAX_NODES: graphML._LSIGFFunction's dense form / under
+                               largeGraphTraining='lists' graphML.lsigf_team_train"""
+    large = Ns > gml.MAX_NODES
+    if training:
+        if large:
+            return 'train_lists' if largeGraphTraining == 'lists' else 'train_dense'
+        return 'train_direct' if Ns == N else 'train_padded'
+    one_call = L == 1 and Ns == N and widths[-1] == _FEATURES
+    if large:
+        if largeGraphFilter == 'lists' and precision not in ('split_f16', _native.PREC_SPLIT_F16):
+            return 'lists_one_call' if one_call else 'lists'
+        return 'dense'
+    if one_call:
+        return 'policy_fwd'
+    return 'small_general+gemm_head' if widths[-1] > _FEATURES else 'small_general'
+
+
+def _pad_nodes(x, Ns):
+    """The padding rule, first half: EVERY filter layer zero-pads its input x [B,N,G] to the GSO's Ns nodes and drops its
+    outputs on the extra ones (graphML.py:2464-2476), so neither an activation nor a cotangent passes them from layer
+    to layer.  By concatenation: autograd cuts the gradient back.  The second half is the caller's: train mode cuts
+    the output to [:, :N] and pads again, eval mode zeroes the rows in place (_zero_extra_nodes)."""
+    N = x.shape[1]
+    return x if N == Ns else torch.cat([x, x.new_zeros(x.shape[0], Ns - N, x.shape[2])], 1)
+
+
+def _zero_extra_nodes(y, N):
+    if y.shape[1] != N:
+        y[:, N:].zero_()
+    return y
+
+
+def _flat_bias(gf):
+    return gf.bias.detach().reshape(-1).contiguous().float() if gf.bias is not None else None
 
 
 class DecentralPlannerNet(nn.Module):
@@ -529,9 +569,18 @@ class DecentralPlannerNet(nn.Module):
     def _head_pointers(gf, act):
         # fp32 kernels read these through raw pointers: cast (a no-op for fp32 modules) and keep
         # the casted tensors alive in the cache entry
-        gb = gf.bias.detach().reshape(-1).contiguous().float() if gf.bias is not None else None
+        gb = _flat_bias(gf)
         aw, ab = act.weight.detach().contiguous().float(), act.bias.detach().contiguous().float()
         return (gb.data_ptr() if gb is not None else None, aw.data_ptr(), ab.data_ptr(), (gb, aw, ab))
+
+    @staticmethod
+    def _head_key(gl, act):
+        return (gl.bias, act.weight, act.bias) if gl.bias is not None else (act.weight, act.bias)
+
+    def _head(self, gl, act):
+        """(GFL bias, head weight, head bias) raw pointers of the last filter layer and the action head, and the tensors
+        behind them: cached until one of the parameters changes."""
+        return self._head_cache.get(self._head_key(gl, act), lambda: self._head_pointers(gl, act))
 
     def policy_pointers(self):
         """(encoder pack, filter taps, GFL bias, head weight, head bias) raw pointers + K for the
@@ -543,9 +592,7 @@ class DecentralPlannerNet(nn.Module):
         enc = self.packed_encoder()                        # (also refreshes self._mods)
         (gf,), act = self._mods
         taps = gf.packed_taps()
-        gb_p, aw_p, ab_p, _keep = self._head_cache.get(
-            (gf.bias, act.weight, act.bias) if gf.bias is not None else (act.weight, act.bias),
-            lambda: self._head_pointers(gf, act))
+        gb_p, aw_p, ab_p, _keep = self._head(gf, act)
         return enc.data_ptr(), taps.data_ptr(), gb_p, aw_p, ab_p, gf.K
 
     def materialize_packs(self):
@@ -557,9 +604,7 @@ class DecentralPlannerNet(nn.Module):
         gfs, act = self._mods
         for gf in gfs:
             gf.packed_taps()
-        gl = gfs[-1]
-        self._head_cache.get((gl.bias, act.weight, act.bias) if gl.bias is not None else (act.weight, act.bias),
-                             lambda: self._head_pointers(gl, act))
+        self._head(gfs[-1], act)
         after = (self._enc_cache.key, self._head_cache.key) + tuple(gf._packed.key for gf in gfs)
         return before != after
 
@@ -570,10 +615,8 @@ class DecentralPlannerNet(nn.Module):
         it keeps `buffers` alive and compares `keys` before every replay."""
         enc_t = self._encoder_tensors()                    # (also refreshes self._mods)
         gfs, act = self._mods
-        gl = gfs[-1]
-        head = (gl.bias, act.weight, act.bias) if gl.bias is not None else (act.weight, act.bias)
         K = _native.PackCache.key_of
-        keys = (K(enc_t), K(head)) + tuple(K((gf.weight,)) for gf in gfs)
+        keys = (K(enc_t), K(self._head_key(gfs[-1], act))) + tuple(K((gf.weight,)) for gf in gfs)
         bufs = (self._enc_cache.buf, self._head_cache.buf) + tuple(gf._packed.buf for gf in gfs)
         if self.largeGraphFilter == 'lists':               # the team calls' workspaces are baked into a graph like the packs
             bufs += tuple(gml._team_ws.values())
@@ -595,19 +638,26 @@ class DecentralPlannerNet(nn.Module):
             logits = self._forward_eval(inputTensor, _native.PREC_FP32, _slot)
         return logits
 
-    def _forward_eval(self, inputTensor, prec=_native.PREC_FP32, slot=None):
-        B = inputTensor.shape[0]
+    def _observations(self, inputTensor):
+        """The observations the kernels read: those of the first numAgents agents (the reference only visits them),
+        detached, contiguous fp32."""
         N = self.numAgents
         assert inputTensor.shape[1] >= N
         obs = inputTensor.detach()
         if obs.shape[1] != N:
-            obs = obs[:, :N]                      # the reference only visits the first numAgents
+            obs = obs[:, :N]
         if obs.dtype is not torch.float32 or not obs.is_contiguous():
             obs = obs.contiguous().float()
+        return obs
+
+    def _forward_eval(self, inputTensor, prec=_native.PREC_FP32, slot=None):
+        B = inputTensor.shape[0]
+        N = self.numAgents
+        obs = self._observations(inputTensor)
         S = self.S.detach()                       # [B,E,N,N]
         assert S.shape[0] == B
         Ns = S.shape[2]
-        assert Ns >= N                            # Nin <= N zero padding (graphML.py:2464-2469)
+        assert Ns >= N
         if not S.is_contiguous():
             S = S.contiguous()
         if S.dtype not in (torch.float32, torch.float64):
@@ -615,80 +665,74 @@ class DecentralPlannerNet(nn.Module):
         enc = self.packed_encoder()
         gfs, act = self._mods
         dev = _native.require_gpu(obs, S, gfs[0].weight, act.weight)
-        if Ns > gml.MAX_NODES and self.largeGraphFilter == 'lists' and prec != _native.PREC_SPLIT_F16:
-            return self._forward_eval_team(obs, S, B, N, Ns, prec, slot, enc, gfs, act, dev)
-        if Ns > gml.MAX_NODES:
-            # larger graphs than one workgroup's LDS holds: encoder kernel, then every filter layer as dense
-            # exact-fp32 GEMMs (graphML._lsigf_large) and the head as one small library GEMM
-            x = self.encode(obs, prec)
-            if Ns != N:
-                x = torch.cat([x, x.new_zeros(B, Ns - N, x.shape[2])], 1)
-            for l, gf in enumerate(gfs):
-                if l and Ns != N:                          # every layer zero-pads its input again (graphML.py:2464-2476)
-                    x[:, N:].zero_()
-                x = gml._lsigf_large(gf.weight, S, x, gf.bias, True, relu=True)
-            out = torch.nn.functional.linear(x[:, :N], act.weight.detach().float(), act.bias.detach().float())
-            return out.permute(1, 0, 2).contiguous()
+        gl = gfs[-1]                               # last graph-filter layer: fused with the head
+        # planner_route's condition for 'policy_fwd', spelled out: the reference's configs reach their one C call after
+        # the integer comparisons they have always cost, without the route function's call
+        if self.L == 1 and Ns == N and Ns <= gml.MAX_NODES and gl.F == 128:
+            route = 'policy_fwd'
+        else:
+            route = planner_route(False, N, Ns, self.L, self.E, self.F[1:], prec, self.largeGraphFilter)
+        if route == 'dense':
+            # larger graphs than one workgroup's LDS holds: every filter layer as dense exact-fp32 GEMMs
+            return self._eval_layers(obs, N, Ns, prec,
+                                     lambda gf, x: gml._lsigf_large(gf.weight, S, x, gf.bias, True, relu=True))
+        if route in ('lists', 'lists_one_call'):
+            return self._forward_eval_team(obs, S, None, B, N, Ns, prec, slot, enc, gfs, act, dev,
+                                           route == 'lists_one_call')
         L = _native.lib()
         s64 = int(S.dtype is torch.float64)
         flag = self._flag(dev).data_ptr() if prec == _native.PREC_SPLIT_F16 else None
-        gl = gfs[-1]                               # last graph-filter layer: fused with the head
-        gb_p, aw_p, ab_p, _keep = self._head_cache.get(
-            (gl.bias, act.weight, act.bias) if gl.bias is not None else (act.weight, act.bias),
-            lambda: self._head_pointers(gl, act))
+        gb_p, aw_p, ab_p, _keep = self._head(gl, act)
         with _native.device_guard(dev):
             st = _native.stream_ptr(dev)
-            if self.L == 1 and Ns == N and gl.F == 128:
-                # the planner of the reference's configs: ONE C call (one or two kernels)
-                # feature workspace between the two kernels: one per (size, stream) -- several batches of a rollout
-                # may be in flight on different streams (rollout.GroupedRollout)
-                wkey = (B * N, st.value)
-                if self._ws is None or self._ws_key != wkey or self._ws.device != dev:
-                    if wkey not in self._ws_all or self._ws_all[wkey].device != dev:
-                        if len(self._ws_all) > 16:
-                            self._ws_all.clear()
-                        self._ws_all[wkey] = torch.empty(B * N, 128, dtype=torch.float32, device=dev)
-                    self._ws, self._ws_key = self._ws_all[wkey], wkey
+            if route == 'policy_fwd':
+                # ONE C call (one or two kernels), the feature workspace between the two kernels
+                ws = self._feat_workspace(B * N, st, dev)
                 logits = (torch.empty(N, B, 5, dtype=torch.float32, device=dev) if slot is None
                           else slot.acquire(N, B, dev, st.value))
                 rc = L.gnnpp_policy_fwd(obs.data_ptr(), S.data_ptr(), enc.data_ptr(),
                                         gl.packed_taps().data_ptr(), gb_p, aw_p, ab_p,
-                                        self._ws.data_ptr(), logits.data_ptr(), B, N, gl.K, self.E,
+                                        ws.data_ptr(), logits.data_ptr(), B, N, gl.K, self.E,
                                         s64, prec, flag, st)
                 _native.check(rc, 'gnnpp_policy_fwd')
                 return logits
-            # general form: encoder kernel, then one filter kernel per layer (node-major in / out, bias
-            # + ReLU fused), the last one with the action head.  A GSO larger than numAgents carries
-            # zero features on the extra nodes into EVERY layer, whose outputs there are dropped.
-            x = torch.zeros(B, Ns, 128, dtype=torch.float32, device=dev) if Ns != N else None
-            feat = self.encode(obs, prec)
-            if x is not None:
-                x[:, :N] = feat
-            else:
-                x = feat
-            for l, gf in enumerate(gfs):
-                last = l == self.L - 1
-                bias = gf.bias.detach().reshape(-1).contiguous().float() if gf.bias is not None else None
-                if last and gf.F <= 128:
-                    logits = torch.empty(Ns, B, 5, dtype=torch.float32, device=dev)
-                    rc = L.gnnpp_filter_head_fwd(_ptr(x), _ptr(S), _ptr(gf.packed_taps()), _ptr(bias),
-                                                 aw_p, ab_p, _ptr(logits), B, Ns, gf.G, gf.F, gf.K,
-                                                 self.E, s64, prec, flag, st)
-                    _native.check(rc, 'gnnpp_filter_head_fwd')
-                    return logits[:N] if Ns != N else logits
+
+            # general form: one filter kernel per layer (node-major in / out, bias + ReLU fused), the last one with
+            # the action head unless it is wider than 128 features
+            def layer(gf, x):
                 y = torch.empty(B, Ns, gf.F, dtype=torch.float32, device=dev)
-                rc = L.gnnpp_lsigf_fwd(_ptr(x), _ptr(S), _ptr(gf.packed_taps()), _ptr(bias), _ptr(y),
+                rc = L.gnnpp_lsigf_fwd(_ptr(x), _ptr(S), _ptr(gf.packed_taps()), _ptr(_flat_bias(gf)), _ptr(y),
                                        B, Ns, Ns, gf.G, gf.F, gf.K, self.E, s64, 1, 1, 1, 1, 0, prec, flag, st)
                 _native.check(rc, 'gnnpp_lsigf_fwd')
-                if Ns != N and not last:                   # every layer zero-pads its input again (graphML.py:2464-2476)
-                    y[:, N:].zero_()
-                x = y
-        # last layer wider than 128 features: the 5-row head is one small library GEMM
+                return y
+
+            def head(gf, x):
+                logits = torch.empty(Ns, B, 5, dtype=torch.float32, device=dev)
+                rc = L.gnnpp_filter_head_fwd(_ptr(x), _ptr(S), _ptr(gf.packed_taps()), _ptr(_flat_bias(gf)),
+                                             aw_p, ab_p, _ptr(logits), B, Ns, gf.G, gf.F, gf.K,
+                                             self.E, s64, prec, flag, st)
+                _native.check(rc, 'gnnpp_filter_head_fwd')
+                return logits
+            return self._eval_layers(obs, N, Ns, prec, layer, head if route == 'small_general' else None)
+
+    def _eval_layers(self, obs, N, Ns, prec, layer, head=None):
+        """The layer-by-layer eval form of every route: the encoder, each filter layer as layer(gf, x [B,Ns,G]) ->
+        [B,Ns,F] under the padding rule (_pad_nodes), the last one as head(gf, x) -> logits [Ns,B,5] where a kernel
+        fuses it with the action head; without one the 5-row head is one small library GEMM."""
+        gfs, act = self._mods
+        x = _pad_nodes(self.encode(obs, prec), Ns)
+        for gf in gfs[:-1]:
+            x = _zero_extra_nodes(layer(gf, x), N)
+        if head is not None:
+            logits = head(gfs[-1], x)
+            return logits[:N] if Ns != N else logits
+        x = layer(gfs[-1], x)
         out = torch.nn.functional.linear(x[:, :N], act.weight.detach().float(), act.bias.detach().float())
         return out.permute(1, 0, 2).contiguous()
 
     def _feat_workspace(self, rows, st, dev):
-        """Feature workspace between the encoder and the filter kernels: one per (rows, stream)."""
+        """Feature workspace between the encoder and the filter kernels: one per (rows, stream) -- several batches of a
+        rollout may be in flight on different streams (rollout.GroupedRollout)."""
         wkey = (rows, st.value)
         if self._ws is None or self._ws_key != wkey or self._ws.device != dev:
             if wkey not in self._ws_all or self._ws_all[wkey].device != dev:
@@ -698,52 +742,50 @@ class DecentralPlannerNet(nn.Module):
             self._ws, self._ws_key = self._ws_all[wkey], wkey
         return self._ws
 
-    def _forward_eval_team(self, obs, S, B, N, Ns, prec, slot, enc, gfs, act, dev):
-        """largeGraphFilter='lists' on a team of more than graphML.MAX_NODES agents: the team kernels
-        (csrc/lsigf_team_kernel.hip).  The reference's planner (one layer, 128 features, GSO of numAgents nodes) is ONE
-        gnnpp_policy_team_fwd call; anything else runs the encoder, one gnnpp_lsigf_team_fwd per layer and
-        gnnpp_filter_head_team_fwd for the last.  What those calls do not serve raises GnnppError: nothing falls back."""
+    def _forward_eval_team(self, obs, S, lists, B, N, Ns, prec, slot, enc, gfs, act, dev, one_call):
+        """The team kernels (csrc/lsigf_team_kernel.hip) on the dense GSO S [B,E,Ns,Ns] -- largeGraphFilter='lists' on a
+        team of more than graphML.MAX_NODES agents -- or, with S = None, on a lists block of the team's N = Ns nodes
+        (forward_logits_lists).  one_call: the reference's planner (one layer, 128 features, GSO of numAgents nodes) is
+        ONE gnnpp_policy_team[_lists]_fwd call; anything else runs the encoder, one gnnpp_lsigf_team[_lists]_fwd per
+        layer and gnnpp_filter_head_team[_lists]_fwd for the last.  What those calls do not serve raises GnnppError:
+        nothing falls back.  slot: where the one call takes its logits buffer from (None: a fresh one)."""
         if Ns > gml.TEAM_MAX_NODES or any(gf.G > 128 or gf.F > 128 for gf in gfs):
             raise _native.GnnppError("largeGraphFilter='lists' serves graphs of up to %d nodes and layers of up to 128 "
                                      "features (this planner: %d nodes, widths %s); use largeGraphFilter='dense'"
                                      % (gml.TEAM_MAX_NODES, Ns, self.F))
         L = _native.lib()
-        s64 = int(S.dtype is torch.float64)
+        if lists is None:                          # (the dense entry points take s_is_f64 after E, their twins do not)
+            graph, s64, policy_team, head_team = S, (int(S.dtype is torch.float64),), 'gnnpp_policy_team_fwd', \
+                'gnnpp_filter_head_team_fwd'
+        else:
+            graph, s64, policy_team, head_team = lists, (), 'gnnpp_policy_team_lists_fwd', \
+                'gnnpp_filter_head_team_lists_fwd'
         gl = gfs[-1]
-        gb_p, aw_p, ab_p, _keep = self._head_cache.get(
-            (gl.bias, act.weight, act.bias) if gl.bias is not None else (act.weight, act.bias),
-            lambda: self._head_pointers(gl, act))
+        gb_p, aw_p, ab_p, _keep = self._head(gl, act)
         with _native.device_guard(dev):
             st = _native.stream_ptr(dev)
-            if self.L == 1 and Ns == N and gl.F == 128:
+            if one_call:
                 feat = self._feat_workspace(B * N, st, dev)
                 ws = gml.team_workspace(B, N, 128, gl.K, self.E, True, dev, st.value)
                 logits = (torch.empty(N, B, 5, dtype=torch.float32, device=dev) if slot is None
                           else slot.acquire(N, B, dev, st.value))
-                rc = L.gnnpp_policy_team_fwd(obs.data_ptr(), S.data_ptr(), enc.data_ptr(), gl.packed_taps().data_ptr(),
-                                             gb_p, aw_p, ab_p, feat.data_ptr(), logits.data_ptr(), B, N, gl.K, self.E,
-                                             s64, prec, None, st, ws.data_ptr(), ws.numel())
-                _native.check(rc, 'gnnpp_policy_team_fwd')
+                rc = getattr(L, policy_team)(obs.data_ptr(), graph.data_ptr(), enc.data_ptr(),
+                                             gl.packed_taps().data_ptr(), gb_p, aw_p, ab_p, feat.data_ptr(),
+                                             logits.data_ptr(), B, N, gl.K, self.E, *s64, prec, None, st, ws.data_ptr(),
+                                             ws.numel())
+                _native.check(rc, policy_team)
                 return logits
-            x = self.encode(obs, prec)
-            if Ns != N:                                    # zero features on the GSO's extra nodes, outputs dropped
-                xp = torch.zeros(B, Ns, 128, dtype=torch.float32, device=dev)
-                xp[:, :N] = x
-                x = xp
-            for l, gf in enumerate(gfs):
-                if l < self.L - 1:
-                    x = gml.lsigf_team(gf.weight, S, x, gf.bias, relu=True, precision=prec, packed=gf.packed_taps())
-                    if Ns != N:                            # every layer zero-pads its input again (graphML.py:2464-2476)
-                        x[:, N:].zero_()
-                    continue
-                bias = gf.bias.detach().reshape(-1).contiguous().float() if gf.bias is not None else None
+
+            def head(gf, x):
                 ws = gml.team_workspace(B, Ns, gf.G, gf.K, self.E, True, dev, st.value)
                 logits = torch.empty(Ns, B, 5, dtype=torch.float32, device=dev)
-                rc = L.gnnpp_filter_head_team_fwd(_ptr(x), _ptr(S), _ptr(gf.packed_taps()), _ptr(bias), aw_p, ab_p,
-                                                  _ptr(logits), _ptr(ws), ws.numel(), B, Ns, gf.G, gf.F, gf.K, self.E,
-                                                  s64, prec, st)
-                _native.check(rc, 'gnnpp_filter_head_team_fwd')
-                return logits[:N] if Ns != N else logits
+                rc = getattr(L, head_team)(_ptr(x), _ptr(graph), _ptr(gf.packed_taps()), _ptr(_flat_bias(gf)), aw_p, ab_p,
+                                           _ptr(logits), _ptr(ws), ws.numel(), B, Ns, gf.G, gf.F, gf.K, self.E, *s64,
+                                           prec, st)
+                _native.check(rc, head_team)
+                return logits
+            return self._eval_layers(obs, N, Ns, prec, lambda gf, x: gml.lsigf_team(
+                gf.weight, S, x, gf.bias, relu=True, precision=prec, packed=gf.packed_taps(), lists=lists), head)
 
     def lists_refusal(self, N=None):
         """Why forward_logits_lists cannot serve this planner (and a team of N agents) -- None when it can."""
@@ -763,10 +805,9 @@ class DecentralPlannerNet(nn.Module):
     def forward_logits_lists(self, inputTensor, lists):
         """forward_logits with the communication graph given as NEIGHBOUR LISTS instead of addGSO's dense matrix: `lists`
         is a block of B * E graphs of numAgents nodes (graphML.team_lists_from_dense(S [B,E,N,N]), or
-        BatchedRollout(graph='lists').gso()).  The team kernels at any team size; bit-identical to addGSO(S) + forward_logits
-        under largeGraphFilter='lists' wherever that route runs them (teams of more than graphML.MAX_NODES agents).
-        The reference's planner (one layer, 128 features) is ONE gnnpp_policy_team_lists_fwd call; several layers or
-        edge features run the encoder, gnnpp_lsigf_team_lists_fwd per layer and gnnpp_filter_head_team_lists_fwd.
+        BatchedRollout(graph='lists').gso()).  The team kernels at any team size (_forward_eval_team); bit-identical to
+        addGSO(S) + forward_logits under largeGraphFilter='lists' wherever that route runs them (teams of more than
+        graphML.MAX_NODES agents).
         Needs eval mode, no gradient wanted (the result carries no graph), largeGraphFilter='lists' and not split-f16
         (GnnppError otherwise).  Lists are built for
         the team: a graph of more nodes than numAgents (which addGSO accepts) is refused -- a block that is not the
@@ -777,62 +818,19 @@ class DecentralPlannerNet(nn.Module):
         if why:
             raise _native.GnnppError(why)
         B, N = inputTensor.shape[0], self.numAgents
-        assert inputTensor.shape[1] >= N
-        obs = inputTensor.detach()
-        if obs.shape[1] != N:
-            obs = obs[:, :N]
-        if obs.dtype is not torch.float32 or not obs.is_contiguous():
-            obs = obs.contiguous().float()
+        obs = self._observations(inputTensor)
         enc = self.packed_encoder()                        # (also refreshes self._mods)
         gfs, act = self._mods
         dev = _native.require_gpu(obs, lists, gfs[0].weight, act.weight)
-        need = gml.team_lists_bytes(B * self.E, N)
-        if lists.dtype is not torch.uint8 or lists.dim() != 1 or lists.numel() != need or lists.data_ptr() % 16:
-            raise _native.GnnppError('forward_logits_lists: the lists must be a 16-byte aligned uint8 block of %d bytes '
-                                     '(%d x %d graphs of the team\'s %d nodes; got %s of %d elements): lists are built for '
-                                     'the team, a GSO larger than the team goes through addGSO'
-                                     % (need, B, self.E, N, lists.dtype, lists.numel()))
-        prec = self._prec()
-        L = _native.lib()
-        gl = gfs[-1]
-        gb_p, aw_p, ab_p, _keep = self._head_cache.get(
-            (gl.bias, act.weight, act.bias) if gl.bias is not None else (act.weight, act.bias),
-            lambda: self._head_pointers(gl, act))
-        with _native.device_guard(dev):
-            st = _native.stream_ptr(dev)
-            if self.L == 1 and gl.F == 128:
-                feat = self._feat_workspace(B * N, st, dev)
-                ws = gml.team_workspace(B, N, 128, gl.K, self.E, True, dev, st.value)
-                logits = torch.empty(N, B, 5, dtype=torch.float32, device=dev)
-                rc = L.gnnpp_policy_team_lists_fwd(obs.data_ptr(), lists.data_ptr(), enc.data_ptr(),
-                                                   gl.packed_taps().data_ptr(), gb_p, aw_p, ab_p, feat.data_ptr(),
-                                                   logits.data_ptr(), B, N, gl.K, self.E, prec, None, st, ws.data_ptr(),
-                                                   ws.numel())
-                _native.check(rc, 'gnnpp_policy_team_lists_fwd')
-                return logits
-            x = self.encode(obs, prec)
-            for l, gf in enumerate(gfs):
-                if l < self.L - 1:
-                    x = gml.lsigf_team(gf.weight, None, x, gf.bias, relu=True, precision=prec, packed=gf.packed_taps(),
-                                       lists=lists, batched=True)
-                    continue
-                bias = gf.bias.detach().reshape(-1).contiguous().float() if gf.bias is not None else None
-                ws = gml.team_workspace(B, N, gf.G, gf.K, self.E, True, dev, st.value)
-                logits = torch.empty(N, B, 5, dtype=torch.float32, device=dev)
-                rc = L.gnnpp_filter_head_team_lists_fwd(_ptr(x), _ptr(lists), _ptr(gf.packed_taps()), _ptr(bias), aw_p,
-                                                        ab_p, _ptr(logits), _ptr(ws), ws.numel(), B, N, gf.G, gf.F,
-                                                        gf.K, self.E, prec, st)
-                _native.check(rc, 'gnnpp_filter_head_team_lists_fwd')
-                return logits
+        gml.team_lists_check(lists, B * self.E, N, exact=True, who='forward_logits_lists (lists are built for the team, a '
+                             'GSO larger than the team goes through addGSO): a lists block')
+        return self._forward_eval_team(obs, None, lists, B, N, N, self._prec(), None, enc, gfs, act, dev,
+                                       self.L == 1 and gfs[-1].F == 128)
 
     def _train_encoder(self, inputTensor, with_packs=False):
         """The train-mode encoder over all agents (_EncoderTrainFunction): features [B,N,128] (and the step's packs)."""
         _native.require_gpu(inputTensor, self.compressMLP[0].weight)
-        B, N = inputTensor.shape[0], self.numAgents
-        obs = inputTensor.detach()
-        if obs.shape[1] != N:
-            obs = obs[:, :N]
-        obs = obs.contiguous().float()
+        obs = self._observations(inputTensor)
         tensors, buffers = [], []
         eps, momentum, track = self._bn_settings(True)
         for ci, bi in zip(_CONV_IDX, _BN_IDX):
@@ -855,65 +853,58 @@ class DecentralPlannerNet(nn.Module):
         their backward products on gnnpp_gemm_kmajor_multi; every weight re-ordering of the step in one
         gnnpp_train_pack launch per weight version; both ReLU backward passes around the filter folded into the
         launches that produce the masked gradients.  No library GEMM and no aten kernel is left in the step (r06).  A
-        GSO with more nodes than numAgents (graphML.py:2464-2476: every layer zero-pads its input and drops the extra
-        nodes' outputs) is honoured as in eval mode."""
+        GSO with more nodes than numAgents is honoured as in eval mode (_pad_nodes)."""
         if self.S is None:
             raise TypeError('addGSO() must be called before forward()')
         _native.require_gpu(inputTensor, self.S, self.compressMLP[0].weight)
         B, N = inputTensor.shape[0], self.numAgents
         feat, packs = self._train_encoder(inputTensor, True)
-        fc = self.compressMLP[0]
         if self.S.shape[0] != B:
             raise _native.GnnppError('addGSO() was given %d graphs, the input has %d samples' % (self.S.shape[0], B))
         Ns = self.S.shape[-1]
         if Ns < N:
             raise _native.GnnppError('the GSO has %d nodes, the planner %d agents' % (Ns, N))
-        # The two ReLU backward passes around the graph filter are folded into the launches that produce the gradients
-        # they mask (r06): compressMLP's into the filter's input-gradient launch (`fold` bit 1 <-> relu = 2), the
-        # filter's own into the action head's dx product (`fold` bit 0 <-> mask_dx) -- when the filter's input / output
-        # ARE those tensors (no zero-padded nodes in between) and the filter runs on the LDS-resident kernels.
-        direct = Ns == N and Ns <= gml.MAX_NODES
-        if Ns > gml.MAX_NODES and self.largeGraphTraining == 'lists':
+        route = planner_route(True, N, Ns, self.L, self.E, self.F[1:], largeGraphTraining=self.largeGraphTraining)
+        if route == 'train_lists':
             ent = self._train_lists                # the lists of S and of S^T: two launches, once per addGSO
             if ent is None or ent[0] is not self.S or ent[1] != self.S._version:
                 lists = gml.team_lists_from_dense(self.S)
                 ent = (self.S, self.S._version, lists, gml.team_lists_transpose(lists, B * self.E, Ns))
                 self.__dict__['_train_lists'] = ent
-            return self._train_tail_lists(feat, ent[2], ent[3], B, N, Ns)
-        # (`direct`: the head's and the filter's parameter-gradient products wait for the compress layer's backward launch)
-        x = _LinearFunction.apply(feat, fc.weight, fc.bias, 2 if direct else 1, False, 2 if direct else 0)   # [B,N,F]
-        # every activation stays node-major [B,N,*] (the layout the filter kernel keeps in LDS): no transposing
-        # copy between encoder, filter layers and head; each GFL ReLU runs inside its filter launch
-        for l in range(self.L):
-            gf = self.GFL[2 * l]
-            gf.addGSO(self.S)
-            if Ns != N:                            # Nin < N: EVERY layer puts a zero signal on the extra nodes
-                x = torch.cat([x, x.new_zeros(B, Ns - N, x.shape[2])], 1)         # (graphML.py:2464-2469) ...
-            fold = ((2 if l == 0 else 0) | (1 if l == self.L - 1 else 0)) if direct else 0
-            x = gf.forward_node_major(x, relu=True, packed=packs[1] if packs else None,
-                                      packed_T=packs[2] if packs else None, fold=fold | (4 if direct else 0))  # [B,Ns,F_l]
-            if Ns != N:                            # ... and drops its outputs there (index_select, :2471-2476): neither
-                x = x[:, :N]                       # an activation nor a cotangent passes them from layer to layer
-        act = self.actionsMLP[0]
-        return _LinearFunction.apply(x, act.weight, act.bias, 0, direct, 1 if direct else 0).permute(1, 0, 2)   # [N,B,5]
+            return self._train_tail(feat, Ns, lists=ent[2:])
+        return self._train_tail(feat, Ns, packs=packs, direct=route == 'train_direct')
 
-    def _train_tail_lists(self, feat, lists, lists_t, B, N, Ns):
-        """compressMLP, the filter layers on graphML.lsigf_team_train and the action head for encoder features feat
-        [B,N,128] and the neighbour lists of a graph of Ns >= N nodes: largeGraphTraining='lists'.  The per-layer zero
-        padding of the dense route is kept; no ReLU backward is folded (large teams never run `direct`)."""
-        if self._prec() == _native.PREC_SPLIT_F16:
+    def _train_tail(self, feat, Ns, lists=None, packs=None, direct=False):
+        """compressMLP, the filter layers and the action head for encoder features feat [B,N,128] on a graph of Ns >= N
+        nodes, every activation node-major [B,N,*] (the layout the filter kernels keep in LDS: no transposing copy
+        between encoder, filter layers and head; each GFL ReLU runs inside its filter launch).  A layer is filtered
+        on (lists of S, lists of S^T) by graphML.lsigf_team_train where `lists` is given, else on addGSO's dense matrix
+        (packs: the step's gnnpp_train_pack).
+        direct (dense matrix only): the two ReLU backward passes around the graph filter are folded into the launches
+        that produce the gradients they mask (r06): compressMLP's into the filter's input-gradient launch (`fold` bit 1
+        <-> relu = 2), the filter's own into the action head's dx product (`fold` bit 0 <-> mask_dx) -- the filter's
+        input / output ARE those tensors (no zero-padded nodes in between) and the filter runs on the LDS-resident
+        kernels; the head's and the filter's parameter-gradient products wait for the compress layer's backward launch
+        (`fold` bit 2 <-> defer)."""
+        if lists is not None and self._prec() == _native.PREC_SPLIT_F16:
             raise _native.GnnppError("largeGraphTraining='lists': precision 'split_f16' has no team kernels; use "
                                      "largeGraphTraining='dense'")
         fc, act = self.compressMLP[0], self.actionsMLP[0]
-        x = _LinearFunction.apply(feat, fc.weight, fc.bias, 1, False, 0)                  # [B,N,F]
+        N = feat.shape[1]
+        x = _LinearFunction.apply(feat, fc.weight, fc.bias, 2 if direct else 1, False, 2 if direct else 0)   # [B,N,F]
         for l in range(self.L):
             gf = self.GFL[2 * l]
-            if Ns != N:                            # every layer zero-pads its input again (graphML.py:2464-2476) ...
-                x = torch.cat([x, x.new_zeros(B, Ns - N, x.shape[2])], 1)
-            x = gf.forward_node_major_lists(x, lists, lists_t, relu=True)                 # [B,Ns,F_l]
-            if Ns != N:                            # ... and drops its outputs there
+            x = _pad_nodes(x, Ns)
+            if lists is not None:
+                x = gf.forward_node_major_lists(x, lists[0], lists[1], relu=True)         # [B,Ns,F_l]
+            else:
+                gf.addGSO(self.S)
+                fold = ((2 if l == 0 else 0) | (1 if l == self.L - 1 else 0) | 4) if direct else 0
+                x = gf.forward_node_major(x, relu=True, packed=packs[1] if packs else None,
+                                          packed_T=packs[2] if packs else None, fold=fold)
+            if Ns != N:
                 x = x[:, :N]
-        return _LinearFunction.apply(x, act.weight, act.bias, 0, False, 0).permute(1, 0, 2)   # [N,B,5]
+        return _LinearFunction.apply(x, act.weight, act.bias, 0, direct, 1 if direct else 0).permute(1, 0, 2)   # [N,B,5]
 
     def forward_train_lists(self, inputTensor, lists, lists_t=None, symmetric=False):
         """The train-mode forward with the communication graph given as NEIGHBOUR LISTS instead of addGSO's dense matrix:
@@ -927,18 +918,14 @@ class DecentralPlannerNet(nn.Module):
             raise _native.GnnppError('forward_train_lists is the train-mode forward (call model.train()); '
                                      'forward_logits_lists is the eval-mode one')
         B, N = inputTensor.shape[0], self.numAgents
-        need = gml.team_lists_bytes(B * self.E, N)
         for blk in (lists, lists_t):
-            if blk is not None and (blk.dtype is not torch.uint8 or blk.dim() != 1 or blk.numel() != need
-                                    or blk.data_ptr() % 16):
-                raise _native.GnnppError('forward_train_lists: the lists must be a 16-byte aligned uint8 block of %d '
-                                         'bytes (%d x %d graphs of the team\'s %d nodes)' % (need, B, self.E, N))
+            if blk is not None:
+                gml.team_lists_check(blk, B * self.E, N, exact=True, who='forward_train_lists: a lists block')
         if symmetric:
             lists_t = lists
         elif lists_t is None:
             lists_t = gml.team_lists_transpose(lists, B * self.E, N)
-        feat = self._train_encoder(inputTensor)
-        return LogitList(self._train_tail_lists(feat, lists, lists_t, B, N, N))
+        return LogitList(self._train_tail(self._train_encoder(inputTensor), N, lists=(lists, lists_t)))
 
     def _train_packs(self, conv_tensors):
         """(encoder train pack, filter taps forward, filter taps transposed) of the CURRENT weights by ONE

@@ -77,6 +77,18 @@ def _bias_arg(b, F_out, N):
     return b.detach().contiguous().float(), 1
 
 
+def _gso_arg(S):
+    """S as the kernels read it: detached, contiguous, fp32 or fp64 (they round fp64 like the reference's S.float())."""
+    Sc = S.detach().contiguous()
+    return Sc if Sc.dtype in (torch.float32, torch.float64) else Sc.float()
+
+
+def _fp32_arg(x):
+    """x as the kernels read it: detached, contiguous, fp32."""
+    xc = x.detach().contiguous()
+    return xc if xc.dtype is torch.float32 else xc.float()
+
+
 # How an eval-mode, no-grad filter call treats graphs of more than MAX_NODES nodes: 'dense' (default) = _lsigf_large
 # (exact fp32 GEMMs over the dense S), 'lists' = lsigf_team (neighbour lists, the graph spread over workgroups; G, F <=
 # 128, not split-f16).  The two round differently, which is why the default stays.  Training has a field of its own
@@ -118,14 +130,6 @@ def team_lists_bytes(graphs, N):
     return int(_native.lib().gnnpp_team_lists_bytes(int(graphs), int(N)))
 
 
-def _team_lists_offsets(graphs, N):
-    Np = (N + 3) & ~3
-    up = lambda v: (v + 15) & ~15                                              # noqa: E731
-    idx = up(graphs * N * 4)
-    val = idx + up(graphs * N * Np * 2)
-    return idx, val, val + up(graphs * N * Np * 4), Np
-
-
 def team_lists_from_dense(S, out=None):
     """The neighbour lists of the non-zeros of S [..., N, N] (fp32, or fp64 rounded like S.float()), one graph per
     leading index, as a uint8 device block (gnnpp_team_lists_from_dense): what lsigf_team(lists=...) and
@@ -133,9 +137,7 @@ def team_lists_from_dense(S, out=None):
     dev = _native.require_gpu(S)
     N = int(S.shape[-1])
     assert S.dim() >= 2 and S.shape[-2] == N
-    Sc = S.detach().contiguous()
-    if Sc.dtype not in (torch.float32, torch.float64):
-        Sc = Sc.float()
+    Sc = _gso_arg(S)
     graphs = Sc.numel() // (N * N)
     nbytes = team_lists_bytes(graphs, N)
     if nbytes == 0:
@@ -149,12 +151,25 @@ def team_lists_from_dense(S, out=None):
     return block
 
 
+def team_lists_check(block, graphs, N, exact=False, who='a lists block'):
+    """GnnppError unless `block` is a lists block for `graphs` graphs of N nodes: a 16-byte aligned 1-D uint8 tensor of at
+    least -- exact: exactly -- team_lists_bytes(graphs, N) bytes.  Returns (offset of idx, offset of val, Np)."""
+    Np = (N + 3) & ~3
+    up = lambda v: (v + 15) & ~15                                              # noqa: E731
+    idx = up(graphs * N * 4)
+    val = idx + up(graphs * N * Np * 2)
+    total = val + up(graphs * N * Np * 4)
+    if (block.dtype is not torch.uint8 or block.dim() != 1 or block.data_ptr() % 16
+            or (block.numel() != total if exact else block.numel() < total)):
+        raise _native.GnnppError('%s for %d graphs of %d nodes is a 16-byte aligned uint8 tensor of %s %d bytes (got %s '
+                                 'of %d elements)' % (who, graphs, N, 'exactly' if exact else 'at least', total,
+                                                      block.dtype, block.numel()))
+    return idx, val, Np
+
+
 def team_lists_views(block, graphs, N):
     """(cnt [graphs,N] int32, idx [graphs,N,Np] uint16, val [graphs,N,Np] float32): tensor views of a lists block."""
-    idx_o, val_o, total, Np = _team_lists_offsets(graphs, N)
-    if block.dtype is not torch.uint8 or block.dim() != 1 or block.numel() < total or block.data_ptr() % 16:
-        raise _native.GnnppError('a lists block for %d graphs of %d nodes is a 16-byte aligned uint8 tensor of at least '
-                                 '%d bytes' % (graphs, N, total))
+    idx_o, val_o, Np = team_lists_check(block, graphs, N)
     return (block[:graphs * N * 4].view(torch.int32).view(graphs, N),
             block[idx_o:idx_o + graphs * N * Np * 2].view(torch.uint16).view(graphs, N, Np),
             block[val_o:val_o + graphs * N * Np * 4].view(torch.float32).view(graphs, N, Np))
@@ -196,15 +211,11 @@ def lsigf_team(h, S, x, b, relu=False, precision=None, workspace=None, packed=No
         batched = S.dim() == 4
         assert S.shape[-1] == N and S.shape[-2] == N and S.shape[-3] == E
         assert not batched or S.shape[0] == B
-        Sc = S.detach().contiguous()
-        if Sc.dtype not in (torch.float32, torch.float64):
-            Sc = Sc.float()
+        Sc = _gso_arg(S)
     else:
         batched = True if batched is None else bool(batched)
-        team_lists_views(lists, (B if batched else 1) * E, N)          # (size, dtype, alignment)
-    xc = x.detach().contiguous()
-    if xc.dtype != torch.float32:
-        xc = xc.float()
+        team_lists_check(lists, (B if batched else 1) * E, N)
+    xc = _fp32_arg(x)
     if packed is None:
         packed = pack_filter_taps(h)
     bias, per_node = _bias_arg(b, F_out, N)
@@ -244,11 +255,11 @@ def team_lists_transpose(block, graphs, N, out=None):
     of the result holds every n with m in column n of `block`, in ascending n, with the same weight.  One launch, no
     dense matrix.  out: a block of the same size to write into (not `block` itself)."""
     dev = _native.require_gpu(block, out)
-    team_lists_views(block, graphs, N)                                 # (size, dtype, alignment)
+    team_lists_check(block, graphs, N)
     if out is None:
         out = torch.empty(team_lists_bytes(graphs, N), dtype=torch.uint8, device=dev)
     else:
-        team_lists_views(out, graphs, N)
+        team_lists_check(out, graphs, N)
     with _native.device_guard(dev):
         rc = _native.lib().gnnpp_team_lists_transpose(_ptr(block), _ptr(out), min(block.numel(), out.numel()),
                                                       int(graphs), int(N), _native.stream_ptr(dev))
@@ -271,6 +282,28 @@ def _team_train_refusal(N, G, F_out, precision):
     return None
 
 
+def _param_grad_specs(ctx, h, zs, dy, need_dh, need_db):
+    """(dh, db, the gnnpp_gemm_kmajor_multi specs that fill them, the parameters they belong to) of a node-major filter
+    call, from its output gradient dy [B,N,F] (already masked by the ReLU) and the saved tap signals zs [E*K, B*N, G].
+    A per-node bias [F,N] has no spec: its sum is taken here."""
+    F_out, E, K, G = h.shape
+    B, N = dy.shape[0], dy.shape[1]
+    dh = db = None
+    specs, prms = [], []
+    if need_dh:
+        dh = _native.grad_out(ctx.param_ptrs[0], (F_out, E, K, G), dy.device)
+        specs.append((dy, (0, 1, F_out), zs, (B * N * G, G), dh, (G, E * K * G), E * K, F_out, G, B * N))
+        prms.append(h)
+    if ctx.bias_ref is not None and need_db:
+        if ctx.bias_shape[-1] == 1 or len(ctx.bias_shape) == 1:
+            db = _native.grad_out(ctx.param_ptrs[1], ctx.bias_shape, dy.device)          # sum over (b, n)
+            specs.append((_ones(B * N, dy.device), (0, 0, 1), dy, (0, F_out), db, (0, F_out), 1, 1, F_out, B * N))
+            prms.append(ctx.bias_ref)
+        else:                                                         # per-node bias [F,N]: sum over b
+            db = dy.sum(dim=0).t().contiguous().reshape(ctx.bias_shape)
+    return dh, db, specs, prms
+
+
 class _TeamTrainFunction(torch.autograd.Function):
     """lsigf_team_train: forward = gnnpp_lsigf_team_lists_fwd_save, backward = gnnpp_lsigf_team_lists_input_grad on the
     lists of S^T (dx) and one gnnpp_gemm_kmajor_multi launch over the saved tap signals (dh, db)."""
@@ -281,9 +314,7 @@ class _TeamTrainFunction(torch.autograd.Function):
         L = _native.lib()
         F_out, E, K, G = h.shape
         B, N = x.shape[0], x.shape[1]
-        xc = x.detach().contiguous()
-        if xc.dtype != torch.float32:
-            xc = xc.float()
+        xc = _fp32_arg(x)
         bias, per_node = _bias_arg(b, F_out, N)
         y = torch.empty(B, N, F_out, dtype=torch.float32, device=dev)
         zs = torch.empty(E * K, B * N, G, dtype=torch.float32, device=dev)
@@ -310,27 +341,18 @@ class _TeamTrainFunction(torch.autograd.Function):
         dy = dy.contiguous().float()
         if ctx.relu:
             dy = torch.ops.aten.threshold_backward(dy, yrelu, 0)          # dy where y > 0, else 0
-        dh = dx = db = None
+        dx = None
         if ctx.needs_input_grad[1]:
             dx = torch.empty(B, N, G, dtype=torch.float32, device=dev)
             with _native.device_guard(dev):
                 st = _native.stream_ptr(dev)
                 ws = team_workspace(B, N, F_out, K, E, ctx.batched, dev, st.value)
                 rc = _native.lib().gnnpp_lsigf_team_lists_input_grad(
-                    _ptr(dy), _ptr(lists_t) if K > 1 else None, _ptr(_packed_transposed_taps(h)), _ptr(dx), _ptr(ws),
+                    _ptr(dy), _ptr(lists_t) if K > 1 else None, _ptr(_cached_pack(h, True)), _ptr(dx), _ptr(ws),
                     ws.numel(), B, N, G, F_out, K, E, int(ctx.batched), st)
             _native.check(rc, 'gnnpp_lsigf_team_lists_input_grad')
             team_train_calls['input_grad'] += 1
-        specs = []
-        if ctx.needs_input_grad[0]:                                       # (the specs of _LSIGFFunction._backward_node_major)
-            dh = _native.grad_out(ctx.param_ptrs[0], (F_out, E, K, G), dev)
-            specs.append((dy, (0, 1, F_out), zs, (B * N * G, G), dh, (G, E * K * G), E * K, F_out, G, B * N))
-        if ctx.bias_ref is not None and ctx.needs_input_grad[2]:
-            if ctx.bias_shape[-1] == 1 or len(ctx.bias_shape) == 1:
-                db = _native.grad_out(ctx.param_ptrs[1], ctx.bias_shape, dev)                # sum over (b, n)
-                specs.append((_ones(B * N, dev), (0, 0, 1), dy, (0, F_out), db, (0, F_out), 1, 1, F_out, B * N))
-            else:                                                         # per-node bias [F,N]: sum over b
-                db = dy.sum(dim=0).t().contiguous().reshape(ctx.bias_shape)
+        dh, db, specs, _ = _param_grad_specs(ctx, h, zs, dy, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
         if specs:
             _native.gemm_kmajor_multi(specs)
         return dh, dx, db, None, None, None, None, None
@@ -354,13 +376,13 @@ def lsigf_team_train(h, lists, x, b, relu=False, precision=None, lists_t=None, s
     if why:
         raise _native.GnnppError('lsigf_team_train: ' + why)
     graphs = (B if batched else 1) * E
-    team_lists_views(lists, graphs, N)
+    team_lists_check(lists, graphs, N)
     if symmetric:
         lists_t = lists
     elif lists_t is None:
         lists_t = team_lists_transpose(lists, graphs, N) if K > 1 and _wants_grad(x) else lists
     else:
-        team_lists_views(lists_t, graphs, N)
+        team_lists_check(lists_t, graphs, N)
     prec = _native.precision_code(DEFAULT_PRECISION if precision is None else precision)
     return _TeamTrainFunction.apply(h, x, b, lists, lists_t, bool(relu), prec, bool(batched))
 
@@ -371,8 +393,7 @@ def _large_tap_signals(h, S, x, batched):
     dev = _native.require_gpu(h, S, x)
     F_out, E, K, G = h.shape
     B, N, _ = x.shape
-    S32 = S.detach()
-    S32 = (S32 if S32.dtype is torch.float32 else S32.float()).contiguous()       # S.float() of the reference (:2350)
+    S32 = _fp32_arg(S)                                                             # S.float() of the reference (:2350)
     EKG = E * K * G
     Z = torch.empty(B, N, E * K, G, dtype=torch.float32, device=dev)
     xc = x.detach().float()
@@ -440,6 +461,17 @@ def _lsigf_large_backward(h, S32, Z, dy, batched, need_dh, need_dx):
     return dh, dx
 
 
+def _on_all_nodes(filt, x, N, node_major):
+    """filt (node-major, all N nodes of the graph) on x: as it stands when node-major, else x [B,G,Nin] turned node-major
+    with zero rows for the missing nodes, the result cut to Nin and turned back."""
+    if node_major:
+        return filt(x)
+    B, G, Nin = x.shape
+    xn = torch.zeros(B, N, G, dtype=torch.float32, device=x.device)
+    xn[:, :Nin] = x.detach().permute(0, 2, 1)
+    return filt(xn)[:, :Nin].permute(0, 2, 1).contiguous()
+
+
 def _lsigf_device(h, S, x, b, batched, Nin, packed=None, relu=False, transposed=False,
                   save_taps=False, node_major=False, precision=None, out_mask=None, large='dense'):
     """Shared driver: h [F,E,K,G], S [E,N,N] | [B,E,N,N], x [B,G,Nin] -> y [B,F,Nin]
@@ -461,20 +493,9 @@ def _lsigf_device(h, S, x, b, batched, Nin, packed=None, relu=False, transposed=
         # large='lists': the team kernels -- except under split-f16, which keeps the dense form; a shape they do not
         # serve (G or F > 128, N > TEAM_MAX_NODES) is an error there, not a silent change of route
         if large == 'lists' and precision != _native.PREC_SPLIT_F16:
-            filt = lambda xn: lsigf_team(h, S, xn, b, relu, precision, packed=packed)      # noqa: E731
-        else:
-            filt = lambda xn: _lsigf_large(h, S, xn, b, batched, relu)                     # noqa: E731
-        if node_major:
-            return filt(x)
-        xn = torch.zeros(B, N, G, dtype=torch.float32, device=dev)                 # zero padding of missing nodes
-        xn[:, :Nin] = x.detach().permute(0, 2, 1)
-        return filt(xn)[:, :Nin].permute(0, 2, 1).contiguous()
-    xc = x.detach().contiguous()
-    if xc.dtype != torch.float32:
-        xc = xc.float()
-    Sc = S.detach().contiguous()
-    if Sc.dtype not in (torch.float32, torch.float64):
-        Sc = Sc.float()
+            return _on_all_nodes(lambda xn: lsigf_team(h, S, xn, b, relu, precision, packed=packed), x, N, node_major)
+        return _on_all_nodes(lambda xn: _lsigf_large(h, S, xn, b, batched, relu), x, N, node_major)
+    xc, Sc = _fp32_arg(x), _gso_arg(S)
     if packed is None:
         packed = pack_filter_taps(h)
     bias, per_node = _bias_arg(b, F_out, N)
@@ -504,11 +525,7 @@ def _lsigf_device(h, S, x, b, batched, Nin, packed=None, relu=False, transposed=
         # GNNPP_ERR_UNSUPPORTED below MAX_NODES, confirmed by gnnpp_lsigf_fits: the graph's rows do not fit the kernel's
         # LDS budget (wide input features, or 101..112 nodes at G = F = 128).  The reference has no such limit: the
         # dense exact-fp32 form.
-        if node_major:
-            return _lsigf_large(h, S, x, b, batched, relu)
-        xn = torch.zeros(B, N, G, dtype=torch.float32, device=dev)
-        xn[:, :Nin] = x.detach().permute(0, 2, 1)
-        return _lsigf_large(h, S, xn, b, batched, relu)[:, :Nin].permute(0, 2, 1).contiguous()
+        return _on_all_nodes(lambda xn: _lsigf_large(h, S, xn, b, batched, relu), x, N, node_major)
     if rc == -2 and (transposed or save_taps):
         return None                                # the training driver (_LSIGFFunction) takes its dense path instead
     _native.check(rc, 'gnnpp_lsigf_fwd')
@@ -534,10 +551,6 @@ def _cached_pack(h, transposed):
         ent = (key, weakref.ref(h), pack_filter_taps(src))
         _weight_packs[slot] = ent
     return ent[2]
-
-
-def _packed_transposed_taps(h):
-    return _cached_pack(h, True)
 
 
 class _LSIGFFunction(torch.autograd.Function):
@@ -621,7 +634,7 @@ class _LSIGFFunction(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             hT = h.detach().permute(3, 1, 2, 0)                          # [G,E,K,F] (shape only)
             dx = _lsigf_device(hT, S, dy, None, ctx.batched, ctx.Nin,
-                               ctx.packed_T if ctx.packed_T is not None else _packed_transposed_taps(h),
+                               ctx.packed_T if ctx.packed_T is not None else _cached_pack(h, True),
                                transposed=True)
             if dx is None:                                               # (wide F: the dense adjoint, needs no Z)
                 dx = _LSIGFFunction._dense_dx(ctx, h, S, dy.permute(0, 2, 1)).permute(0, 2, 1).contiguous()
@@ -646,42 +659,28 @@ class _LSIGFFunction(torch.autograd.Function):
         N, B = S.shape[-1], dyn.shape[0]
         if ctx.Nin != N:
             dyn = torch.cat([dyn, dyn.new_zeros(B, N - ctx.Nin, dyn.shape[2])], 1)
-        S32 = S.detach()
-        S32 = (S32 if S32.dtype is torch.float32 else S32.float()).contiguous()
-        _, dxn = _lsigf_large_backward(h, S32, None, dyn.contiguous(), ctx.batched, False, True)
+        _, dxn = _lsigf_large_backward(h, _fp32_arg(S), None, dyn.contiguous(), ctx.batched, False, True)
         return dxn[:, :ctx.Nin]
 
     @staticmethod
     def _backward_node_major(ctx, h, S, zs, dy):
         """dy [B,N,F] (rows (b,n), the row order of the saved tap signals): the input gradient is the
         transposed filter on dy, node-major in and out; dh and db come from ONE multi-product GEMM launch."""
-        F_out, E, K, G = h.shape
-        B, N = dy.shape[0], dy.shape[1]
+        N = dy.shape[1]
         assert ctx.Nin == N
-        dh = dx = db = None
+        dx = None
         if ctx.needs_input_grad[2]:
             hT = h.detach().permute(3, 1, 2, 0)
             # (fold bit 1: tap signal 0 of edge feature 0 IS the filter's input x -- the mask of the ReLU that made it)
             mask = zs[0] if (ctx.fold & 2) else None
             dx = _lsigf_device(hT, S, dy, None, ctx.batched, N,
-                               ctx.packed_T if ctx.packed_T is not None else _packed_transposed_taps(h),
+                               ctx.packed_T if ctx.packed_T is not None else _cached_pack(h, True),
                                transposed=True, node_major=True, out_mask=mask)
             if dx is None:
                 dx = _LSIGFFunction._dense_dx(ctx, h, S, dy)
                 if mask is not None:
                     dx = torch.ops.aten.threshold_backward(dx.contiguous(), mask.reshape(dx.shape), 0)
-        specs, prms = [], []
-        if ctx.needs_input_grad[0]:
-            dh = _native.grad_out(ctx.param_ptrs[0], (F_out, E, K, G), dy.device)
-            specs.append((dy, (0, 1, F_out), zs, (B * N * G, G), dh, (G, E * K * G), E * K, F_out, G, B * N))
-            prms.append(h)
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            if ctx.bias_shape[-1] == 1 or len(ctx.bias_shape) == 1:
-                db = _native.grad_out(ctx.param_ptrs[1], ctx.bias_shape, dy.device)          # sum over (b, n)
-                specs.append((_ones(B * N, dy.device), (0, 0, 1), dy, (0, F_out), db, (0, F_out), 1, 1, F_out, B * N))
-                prms.append(ctx.bias_ref)
-            else:                                                         # per-node bias [F,N]: sum over b
-                db = dy.sum(dim=0).t().contiguous().reshape(ctx.bias_shape)
+        dh, db, specs, prms = _param_grad_specs(ctx, h, zs, dy, ctx.needs_input_grad[0], ctx.needs_input_grad[3])
         if specs:
             if (ctx.fold & 4) and _native.may_defer(h, ctx.bias_ref):
                 _native.defer_gemms(specs, prms)

@@ -69,6 +69,27 @@ def test_route_edges():
     assert r(True, 113, 113, 1, 1, (128,)) == 'train_dense'
 
 
+def test_package_route_function_is_the_restated_one():
+    """The package's one route decision (decentralplanner.planner_route) against the restatement of this suite, over
+    every combination of the grid; largeGraphTraining='lists' turns training on more than MAX_NODES nodes into
+    'train_lists' and changes nothing else."""
+    import itertools
+    from gnn_pathplanning_amd.decentralplanner import planner_route
+    grid = itertools.product((False, True),
+                             ((6, 6), (6, 9), (112, 112), (111, 112), (113, 113), (100, 113), (1024, 1024)),
+                             ((1, (128,)), (1, (64,)), (1, (129,)), (2, (128, 128)), (2, (128, 160))),
+                             (1, 2), prc.PRECISIONS, ('dense', 'lists'))
+    n = 0
+    for training, (N, Ns), (L, widths), E, prec, lgf in grid:
+        want = prc.route(training, N, Ns, L, E, widths, prec, lgf)
+        assert planner_route(training, N, Ns, L, E, widths, prec, lgf, 'dense') == want, (training, N, Ns, L, E, prec, lgf)
+        assert planner_route(training, N, Ns, L, E, widths, prec, lgf) == want           # 'dense' is the default
+        lists = planner_route(training, N, Ns, L, E, widths, prec, lgf, 'lists')
+        assert lists == ('train_lists' if training and Ns > prc.MAX_NODES else want), (training, N, Ns, L, E, prec, lgf)
+        n += 1
+    assert n == 2 * 7 * 5 * 2 * 3 * 2
+
+
 @pytest.mark.parametrize('case', prc.CASES, ids=prc.case_id)
 def test_case_inputs(case):
     """Shapes, dtypes, non-zero biases on every layer and logits of the scale the yardstick's floor assumes."""
