@@ -43,7 +43,8 @@ EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get
            'gnnpp_filter_head_team_fwd', 'gnnpp_policy_team_fwd', 'gnnpp_team_lists_bytes',
            'gnnpp_team_lists_from_dense', 'gnnpp_rollout_lists', 'gnnpp_lsigf_team_lists_fwd',
            'gnnpp_filter_head_team_lists_fwd', 'gnnpp_policy_team_lists_fwd', 'gnnpp_team_lists_transpose',
-           'gnnpp_lsigf_team_lists_fwd_save', 'gnnpp_lsigf_team_lists_input_grad')
+           'gnnpp_lsigf_team_lists_fwd_save', 'gnnpp_lsigf_team_lists_input_grad', 'gnnpp_schedule_team_plan',
+           'gnnpp_schedule_team_fill_lists', 'gnnpp_team_lists_gather')
 
 
 class GnnppError(RuntimeError):
@@ -329,6 +330,12 @@ def _bind(path):
     L.gnnpp_schedule_team_workspace_bytes.restype = cs
     L.gnnpp_schedule_team_samples.argtypes = [ctypes.POINTER(ScheduleStruct), vp, cs, vp]
     L.gnnpp_schedule_team_samples.restype = ci
+    L.gnnpp_schedule_team_plan.argtypes = [ctypes.POINTER(ScheduleStruct), vp, cs, vp, vp]
+    L.gnnpp_schedule_team_plan.restype = ci
+    L.gnnpp_schedule_team_fill_lists.argtypes = [ctypes.POINTER(ScheduleStruct), vp, cs, vp, vp, vp, ci, vp]
+    L.gnnpp_schedule_team_fill_lists.restype = ci
+    L.gnnpp_team_lists_gather.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, cs, ci, vp]
+    L.gnnpp_team_lists_gather.restype = ci
     L.gnnpp_mapf_workspace_bytes.argtypes = [ci] * 4
     L.gnnpp_mapf_workspace_bytes.restype = cs
     L.gnnpp_mapf_solve.argtypes = [ctypes.POINTER(MapfStruct), vp]

@@ -233,24 +233,35 @@ __global__ __launch_bounds__(256) void expert_team_observe_kernel(const Schedule
 
 inline size_t schedule_team_workspace_bytes(int N, int T_total) { return round16((size_t)T_total * N * sizeof(double)); }
 
+// the observation launch of gnnpp_schedule_team_samples and gnnpp_schedule_team_fill_lists (expert_team_lists_kernel.hip)
+inline void schedule_team_observe_launch(const ScheduleArgs& a, int groups, hipStream_t st) {
+    static LdsAttrOnce once;
+    set_lds_attr_once(once, reinterpret_cast<const void*>(&expert_team_observe_kernel), kTeamLdsBytes);
+    hipLaunchKernelGGL(expert_team_observe_kernel, dim3(a.T_total * groups), dim3(256),
+                       team_observe_smem(a.N, a.H, a.W), st, a, groups);
+}
+
+// the map fits the LDS occupancy grid and the workgroups a grid dimension
+inline bool schedule_team_fits(const ScheduleArgs& a) {
+    const int groups = (a.N + kObsAgentsPerWg - 1) / kObsAgentsPerWg;
+    return (long long)a.H * a.W <= kTeamMaxCells && (long long)a.T_total * groups <= 0x7fffffffLL;
+}
+
 // GNNPP_OK, or GNNPP_ERR_UNSUPPORTED (the map does not fit the LDS occupancy grid, or more workgroups than a grid
 // dimension holds) with nothing enqueued
 int schedule_team_samples_launch(const ScheduleArgs& a, double* inv_ws, hipStream_t st) {
     const int nt = team_threads(a.N);
     const int tiles = (a.N + kTeamGraphRows - 1) / kTeamGraphRows;
     const int groups = (a.N + kObsAgentsPerWg - 1) / kObsAgentsPerWg;
-    if ((long long)a.H * a.W > kTeamMaxCells || (long long)a.T_total * groups > 0x7fffffffLL) return GNNPP_ERR_UNSUPPORTED;
+    if (!schedule_team_fits(a)) return GNNPP_ERR_UNSUPPORTED;
     const size_t align = reinterpret_cast<size_t>(a.S) | reinterpret_cast<size_t>(a.S64);
     const int vec = (a.N & 3) == 0 && (align & 15) == 0;
-    static LdsAttrOnce once;
-    set_lds_attr_once(once, reinterpret_cast<const void*>(&expert_team_observe_kernel), kTeamLdsBytes);
     hipLaunchKernelGGL(expert_team_scan_kernel, dim3(a.T_total), dim3(nt), expert_team_scan_smem(a.N), st, a);
     hipLaunchKernelGGL(expert_case_kernel, dim3(a.C), dim3(64), 0, st, a);
     hipLaunchKernelGGL(expert_team_degree_kernel, dim3(a.T_total), dim3(nt), (size_t)8 * a.N, st, a, inv_ws);
     hipLaunchKernelGGL(expert_team_graph_kernel, dim3(a.T_total * tiles), dim3(256), (size_t)16 * ((a.N + 3) & ~3), st, a,
                        static_cast<const double*>(inv_ws), tiles, vec);
-    hipLaunchKernelGGL(expert_team_observe_kernel, dim3(a.T_total * groups), dim3(256),
-                       team_observe_smem(a.N, a.H, a.W), st, a, groups);
+    schedule_team_observe_launch(a, groups, st);
     return hipGetLastError() == hipSuccess ? GNNPP_OK : GNNPP_ERR_LAUNCH;
 }
 

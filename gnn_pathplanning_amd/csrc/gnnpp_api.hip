@@ -22,6 +22,7 @@
 #include "lsigf_team_kernel.hip"   // forward filter / head / policy step for graphs of up to 1024 nodes, spread over workgroups
 #include "lsigf_team_train_kernel.hip"   // ... its training calls: lists of S^T, the forward that keeps the tap signals
 #include "rollout_team_lists_kernel.hip"   // the rollout's communication graph as the team filter's neighbour lists
+#include "expert_team_lists_kernel.hip"    // the expert schedules' graphs as capped neighbour lists, and the draw from them
 #include "train_encoder.hip"
 #include "train_ops.hip"
 
@@ -764,8 +765,9 @@ int gnnpp_rollout_policy_steps(const gnnpp_rollout* r, const float* enc_packed, 
 
 // pointers and sizes first (GNNPP_ERR_ARG; the team call's workspace among them), then the supported range: nothing is
 // enqueued on an error
-static bool schedules_ok(const gnnpp_schedules* s, int max_agents) {
-    return s && s->grid && s->goal && s->pos && s->case_start && s->obs && s->S && s->target && s->radius &&
+static bool schedules_ok(const gnnpp_schedules* s, int max_agents, bool need_obs = true, bool need_S = true) {
+    return s && s->grid && s->goal && s->pos && s->case_start && (s->obs || !need_obs) && (s->S || !need_S) && s->target &&
+           s->radius &&
            s->growth && s->status && s->step_info && s->C > 0 && s->T_total > 0 && s->C <= s->T_total && s->N > 0 &&
            s->N <= max_agents && s->H > 0 && s->W > 0 && s->radius0 > 0.0 && s->radius0 < 1e300;
 }
@@ -787,6 +789,44 @@ int gnnpp_schedule_team_samples(const gnnpp_schedules* s, void* workspace, size_
         return GNNPP_ERR_ARG;
     if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;
     return schedule_team_samples_launch(*s, static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
+}
+
+// the workspace of the team calls: present, 8-byte aligned, large enough
+static bool schedule_team_workspace_ok(const gnnpp_schedules* s, const void* workspace, size_t workspace_bytes) {
+    return workspace && (reinterpret_cast<size_t>(workspace) & 7) == 0 &&
+           workspace_bytes >= schedule_team_workspace_bytes(s->N, s->T_total);
+}
+
+int gnnpp_schedule_team_plan(const gnnpp_schedules* s, void* workspace, size_t workspace_bytes, int* step_deg,
+                             void* stream) {
+    if (!schedules_ok(s, GNNPP_ROLLOUT_MAX_TEAM, false, false) || !schedule_team_workspace_ok(s, workspace, workspace_bytes) ||
+        !step_deg)
+        return GNNPP_ERR_ARG;
+    if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;
+    return schedule_team_plan_launch(*s, static_cast<double*>(workspace), step_deg, static_cast<hipStream_t>(stream));
+}
+
+// a capped lists set: cap a multiple of 4 in 4 .. roundup4(N), the three arrays present and 16-byte aligned
+static bool capped_lists_ok(const void* cnt, const void* idx, const void* val, int cap, int N) {
+    const uintptr_t align = reinterpret_cast<uintptr_t>(cnt) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(val);
+    return cnt && idx && val && !(align & 15) && cap >= 4 && !(cap & 3) && cap <= ((N + 3) & ~3);
+}
+
+int gnnpp_schedule_team_fill_lists(const gnnpp_schedules* s, const void* workspace, size_t workspace_bytes, int* cnt,
+                                   unsigned short* idx, float* val, int cap, void* stream) {
+    if (!schedules_ok(s, GNNPP_ROLLOUT_MAX_TEAM, true, false) || !schedule_team_workspace_ok(s, workspace, workspace_bytes) ||
+        !capped_lists_ok(cnt, idx, val, cap, s->N))
+        return GNNPP_ERR_ARG;
+    if (s->N < 2) return GNNPP_ERR_UNSUPPORTED;
+    return schedule_team_fill_lists_launch(*s, static_cast<const double*>(workspace), cnt, idx, val, cap,
+                                           static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_team_lists_gather(const int* cnt, const unsigned short* idx, const float* val, int graphs_src, int cap,
+                            const int* index, int B, void* lists, size_t lists_bytes, int N, void* stream) {
+    if (graphs_src <= 0 || !index || !team_lists_block_ok(lists, lists_bytes, B, N) || !capped_lists_ok(cnt, idx, val, cap, N))
+        return GNNPP_ERR_ARG;
+    return team_lists_gather_launch(cnt, idx, val, graphs_src, cap, index, B, lists, N, static_cast<hipStream_t>(stream));
 }
 
 size_t gnnpp_mapf_workspace_bytes(int C, int R, int H, int T_max) {

@@ -11,6 +11,8 @@ bit-exact with the reference; there is no CPU fallback.  Teams of up to MAX_TEAM
 samples_from_schedules_team: ONE gnnpp_schedule_team_samples call (csrc/expert_team_kernels.hip), the same tensors.
 The prioritized expert itself runs on the device too (mapf.py): solve_failures plans the failed episodes of a rollout
 and samples_from_solutions turns the solved ones into samples (team=True: teams of any size up to MAX_TEAM).
+Large teams can keep their graphs as neighbour lists from the schedule to the training step, with no [N,N] matrix in
+between: samples_from_schedules_team(graph='lists') -> SampleListPool.draw -> training.train_step_lists.
 
 The schedule's communication radius is NOT the rollout's: it starts at commR (5 in both transformers), grows by
 * 1.1 until every step of the case is connected, and the final radius builds every step's graph.
@@ -32,7 +34,10 @@ BAD_MOVE, BAD_STATE, NO_RADIUS = 1, 2, 4          # GNNPP_SCHEDULE_* status bits
 class ScheduleSamples:
     """Device tensors of one samples_from_schedules call: input [T,N,3,11,11] f32, GSO [T,N,N] f32, GSO64 (f64 or
     None), target [T,N,5] f32, case_start [C+1] i32, radius [C] f64, growth [C] i32, step_growth [T] i32 (the growths
-    each step needs on its own)."""
+    each step needs on its own).
+    With graph='lists' (samples_from_schedules_team) GSO and GSO64 are None and the graphs are a capped lists set
+    (include/gnnpp.h): cnt [T,N] i32, idx [T,N,cap] (uint16 row indices held in an int16 tensor: torch concatenates
+    those), val [T,N,cap] f32, cap, and step_deg [T] i32, the largest degree of each step."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -46,6 +51,8 @@ class ScheduleSamples:
     def case(self, c):
         """(input, GSO, target) views of case c."""
         a, b = self.bounds[c], self.bounds[c + 1]
+        if self.GSO is None:                            # graph='lists': (cnt, idx, val) in the place of the GSO
+            return self.input[a:b], (self.cnt[a:b], self.idx[a:b], self.val[a:b]), self.target[a:b]
         return self.input[a:b], self.GSO[a:b], self.target[a:b]
 
 
@@ -67,8 +74,9 @@ def _schedule_struct(grid, goal, pos, case_start, out, commR):
     s.case_start, s.C, s.N = case_start.data_ptr(), int(goal.shape[0]), int(goal.shape[1])
     s.H, s.W, s.T_total = int(grid.shape[-2]), int(grid.shape[-1]), int(pos.shape[0])
     s.radius0 = float(commR)
-    s.obs, s.S, s.target = out.input.data_ptr(), out.GSO.data_ptr(), out.target.data_ptr()
-    s.S64 = out.GSO64.data_ptr() if out.GSO64 is not None else None
+    ptr = lambda t: t.data_ptr() if t is not None else None                     # noqa: E731
+    s.obs, s.S, s.target = ptr(out.input), ptr(out.GSO), out.target.data_ptr()
+    s.S64 = ptr(out.GSO64)
     s.radius, s.growth, s.status = out.radius.data_ptr(), out.growth.data_ptr(), out.status.data_ptr()
     s.step_info = out.step_growth.data_ptr()
     return s
@@ -87,6 +95,44 @@ def enqueue_schedule_team_samples(grid, goal, pos, case_start, out, commR=5.0):
                       'gnnpp_schedule_team_samples')
 
 
+def enqueue_schedule_team_plan(grid, goal, pos, case_start, out, commR=5.0):
+    """gnnpp_schedule_team_plan alone (arguments as enqueue_schedule_team_samples): target, radius, growth, status,
+    step_growth and the workspace as that call writes them, and out.step_deg [T] int32, the largest degree of each step.
+    out.input / out.GSO / out.GSO64 may be None.  No allocation, no host synchronisation, capturable."""
+    dev = _native.require_gpu(grid, goal, pos, case_start, out.target, out.workspace, out.step_deg)
+    s = _schedule_struct(grid, goal, pos, case_start, out, commR)
+    ws = out.workspace
+    with _native.device_guard(dev):
+        _native.check(_native.lib().gnnpp_schedule_team_plan(ctypes.byref(s), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                                             out.step_deg.data_ptr(), _native.stream_ptr(dev)),
+                      'gnnpp_schedule_team_plan')
+
+
+def enqueue_schedule_team_fill_lists(grid, goal, pos, case_start, out, commR=5.0):
+    """gnnpp_schedule_team_fill_lists alone, after enqueue_schedule_team_plan on the same `out`: out.input and the capped
+    lists out.cnt [T,N] int32, out.idx [T,N,cap] int16 (read as uint16), out.val [T,N,cap] float32 with out.cap.  No dense
+    GSO is written.  No allocation, no host synchronisation, capturable."""
+    dev = _native.require_gpu(grid, goal, pos, case_start, out.input, out.workspace, out.cnt, out.idx, out.val)
+    s = _schedule_struct(grid, goal, pos, case_start, out, commR)
+    ws = out.workspace
+    T, N, cap = int(pos.shape[0]), int(pos.shape[1]), int(out.cap)
+    if (tuple(out.cnt.shape) != (T, N) or out.cnt.dtype is not torch.int32 or tuple(out.idx.shape) != (T, N, cap)
+            or out.idx.dtype is not torch.int16 or tuple(out.val.shape) != (T, N, cap) or out.val.dtype is not torch.float32
+            or not (out.cnt.is_contiguous() and out.idx.is_contiguous() and out.val.is_contiguous())):
+        raise _native.GnnppError('capped lists of %d steps of %d agents at cap %d: contiguous cnt [T,N] int32, idx [T,N,cap] '
+                                 'int16 and val [T,N,cap] float32' % (T, N, cap))
+    with _native.device_guard(dev):
+        _native.check(_native.lib().gnnpp_schedule_team_fill_lists(
+            ctypes.byref(s), ws.data_ptr(), ws.numel() * ws.element_size(), out.cnt.data_ptr(), out.idx.data_ptr(),
+            out.val.data_ptr(), cap, _native.stream_ptr(dev)), 'gnnpp_schedule_team_fill_lists')
+
+
+def team_lists_output_bytes(T_total, N, cap):
+    """Bytes of the input, target and capped-lists tensors of T_total steps of N agents: 1.7 MB per step at N = 1024 and
+    cap = 24, of which the graph is 0.15 MB."""
+    return T_total * N * (1452 + 20 + 4 + 6 * cap)
+
+
 def team_output_bytes(T_total, N, keep_fp64_gso=False):
     """Bytes of the input, GSO and target tensors (+ the fp64 GSO) of T_total steps of N agents: 5.7 MB per step at
     N = 1024."""
@@ -101,15 +147,35 @@ def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64
     return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, False)
 
 
-def samples_from_schedules_team(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False):
+def samples_from_schedules_team(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False, graph='dense'):
     """samples_from_schedules for teams of 2 to MAX_TEAM = 1024 agents on maps of up to 65 536 cells: same arguments,
     same ScheduleSamples (the same bytes for every team both take), same errors naming the bad case.  The outputs are
     team_output_bytes(T, N, keep_fp64_gso) bytes; a call that would not fit the device's free memory raises GnnppError
-    with that figure before anything is allocated."""
-    return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, True)
+    with that figure before anything is allocated.
+    graph='lists': the graphs are delivered as a capped lists set (ScheduleSamples.cnt / idx / val / cap / step_deg; GSO
+    is None) and no [N,N] matrix is written: gnnpp_schedule_team_plan, the host read of the cases' status and the steps'
+    largest degrees, cap = that maximum rounded up to 4, then gnnpp_schedule_team_fill_lists.  The outputs are
+    team_lists_output_bytes(T, N, cap) bytes, checked against the free memory once cap is known.  SampleListPool takes
+    the result.  keep_fp64_gso is refused."""
+    if graph not in ('dense', 'lists'):
+        raise _native.GnnppError("unknown graph %r (one of ['dense', 'lists'])" % (graph,))
+    if graph == 'lists' and keep_fp64_gso:
+        raise _native.GnnppError("samples_from_schedules_team: graph='lists' keeps no dense GSO, keep_fp64_gso=True needs "
+                                 "graph='dense'")
+    return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, True, graph == 'lists')
 
 
-def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, team):
+def _raise_if_flagged(bad, C):
+    if bool((bad != 0).any()):
+        c = int((bad != 0).nonzero()[0])
+        what = [w for bit, w in ((BAD_MOVE, 'a move that is not one of the five actions'),
+                                 (BAD_STATE, 'a state off the map or on an obstacle'),
+                                 (NO_RADIUS, 'no radius connects the team')) if int(bad[c]) & bit]
+        raise _native.GnnppError('schedule of case %d (of %d) cannot be transformed: %s (status %d; %d case(s) flagged)'
+                                 % (c, C, ' and '.join(what), int(bad[c]), int((bad != 0).sum())))
+
+
+def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, team, lists=False):
     name = 'samples_from_schedules_team' if team else 'samples_from_schedules'
     dev = torch.device(device)
     if dev.type != 'cuda':
@@ -135,17 +201,40 @@ def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gs
         bounds.append(bounds[-1] + int(s.shape[0]))
     T = bounds[-1]
     workspace = None
-    if team:
-        need = team_output_bytes(T, N, keep_fp64_gso)
+
+    def must_fit(need):
         free = torch.cuda.mem_get_info(dev)[0]
         if need > free:
             raise _native.GnnppError('%s: the tensors of %d steps of %d agents take %d bytes (%.1f GB), the device has '
                                      '%d bytes free: pass fewer cases per call' % (name, T, N, need, need / 1e9, free))
+    if team:
+        # (lists: the graph's bytes are known once the plan has run; every column holds at least one group of four)
+        must_fit(team_lists_output_bytes(T, N, 4) if lists else team_output_bytes(T, N, keep_fp64_gso))
         workspace = torch.empty(L.gnnpp_schedule_team_workspace_bytes(N, T), dtype=torch.uint8, device=dev)
     grid = g.to(torch.uint8).contiguous().to(dev)
     goal = goal.contiguous().to(dev)
     pos = torch.cat(sched, 0).contiguous().to(dev)
     case_start = torch.tensor(bounds, dtype=torch.int32).to(dev)
+    if lists:
+        flags = torch.empty(C + T, dtype=torch.int32, device=dev)        # status | step_deg: one read for both
+        out = ScheduleSamples(
+            input=None, GSO=None, GSO64=None, target=torch.empty(T, N, 5, dtype=torch.float32, device=dev),
+            case_start=case_start, bounds=bounds, radius=torch.empty(C, dtype=torch.float64, device=dev),
+            growth=torch.empty(C, dtype=torch.int32, device=dev), status=flags[:C], step_deg=flags[C:],
+            step_growth=torch.empty(T, dtype=torch.int32, device=dev), workspace=workspace)
+        out._keep = (grid, goal, pos)
+        enqueue_schedule_team_plan(grid, goal, pos, case_start, out, commR)
+        host = flags.cpu()
+        _raise_if_flagged(host[:C], C)
+        out.cap = max(4, (int(host[C:].max()) + 3) & ~3)
+        must_fit(team_lists_output_bytes(T, N, out.cap) - T * N * 20)
+        out.input = torch.empty(T, N, 3, 11, 11, dtype=torch.float32, device=dev)
+        out.cnt = torch.empty(T, N, dtype=torch.int32, device=dev)
+        out.idx = torch.empty(T, N, out.cap, dtype=torch.int16, device=dev)
+        out.val = torch.empty(T, N, out.cap, dtype=torch.float32, device=dev)
+        enqueue_schedule_team_fill_lists(grid, goal, pos, case_start, out, commR)
+        out.step_growth &= 0xffff
+        return out
     out = ScheduleSamples(
         input=torch.empty(T, N, 3, 11, 11, dtype=torch.float32, device=dev),
         GSO=torch.empty(T, N, N, dtype=torch.float32, device=dev),
@@ -163,14 +252,7 @@ def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gs
     else:
         enqueue_schedule_samples(grid, goal, pos, case_start, out, commR)
     out.step_growth &= 0xffff                           # (the status bits of a step live above; reported per case)
-    bad = out.status.cpu()
-    if bool((bad != 0).any()):
-        c = int((bad != 0).nonzero()[0])
-        what = [w for bit, w in ((BAD_MOVE, 'a move that is not one of the five actions'),
-                                 (BAD_STATE, 'a state off the map or on an obstacle'),
-                                 (NO_RADIUS, 'no radius connects the team')) if int(bad[c]) & bit]
-        raise _native.GnnppError('schedule of case %d (of %d) cannot be transformed: %s (status %d; %d case(s) flagged)'
-                                 % (c, C, ' and '.join(what), int(bad[c]), int((bad != 0).sum())))
+    _raise_if_flagged(out.status.cpu(), C)
     return out
 
 
@@ -197,16 +279,19 @@ def solve_failures(rollout, results=None, **kw):
     return sol
 
 
-def samples_from_solutions(solutions, grids, goals, commR=5.0, team=False):
+def samples_from_solutions(solutions, grids, goals, commR=5.0, team=False, graph='dense'):
     """(ScheduleSamples of the solved cases of a mapf.Solutions, their case ids numpy int64 [S]) through
     samples_from_schedules / enqueue_schedule_samples, or with team=True through samples_from_schedules_team (teams of
-    up to MAX_TEAM agents, what mapf.solve_team plans).  grids [C,H,W] or [H,W] and goals [C,N,2]: the cases' maps and
-    goals as solve() was given them (host or device).  Unsolved cases are left out (their ids are missing from the
-    list); (None, empty ids) when no case was solved."""
+    up to MAX_TEAM agents, what mapf.solve_team plans; graph='lists' is passed on to it and needs team=True).
+    grids [C,H,W] or [H,W] and goals [C,N,2]: the cases' maps and goals as solve() was given them (host or device).
+    Unsolved cases are left out (their ids are missing from the list); (None, empty ids) when no case was solved."""
     if not team and int(solutions.arrival.shape[1]) > MAX_AGENTS:
         raise _native.GnnppError('samples_from_solutions: samples are built for teams of at most %d agents; these '
                                  'solutions have %d (pass team=True: samples_from_schedules_team takes teams of up to '
                                  '%d agents)' % (MAX_AGENTS, solutions.arrival.shape[1], MAX_TEAM))
+    if graph != 'dense' and not team:
+        raise _native.GnnppError("samples_from_solutions: graph=%r needs team=True (samples_from_schedules_team builds the "
+                                 "lists)" % (graph,))
     status = solutions.status.cpu().numpy()
     ids = np.nonzero(status == 0)[0]
     if len(ids) == 0:
@@ -218,6 +303,8 @@ def samples_from_solutions(solutions, grids, goals, commR=5.0, team=False):
     g = g.to(dev).index_select(0, idx) if g.dim() == 3 else g
     gl = (goals if torch.is_tensor(goals) else torch.as_tensor(np.asarray(goals))).to(dev).index_select(0, idx)
     sched = [solutions.schedules[c, :int(makespan[c]) + 1] for c in ids]
+    if graph != 'dense':
+        return samples_from_schedules_team(g, gl, sched, dev, commR=commR, graph=graph), ids
     return (samples_from_schedules_team if team else samples_from_schedules)(g, gl, sched, dev, commR=commR), ids
 
 
@@ -334,3 +421,77 @@ class SamplePool:
     def gather(self, idx):
         idx = torch.as_tensor(idx, dtype=torch.long).to(self.input.device)
         return self.input.index_select(0, idx), self.target.index_select(0, idx), self.GSO.index_select(0, idx)
+
+
+class SampleListPool:
+    """SamplePool for samples_from_schedules_team(graph='lists'): device-resident samples of ONE team size whose graphs
+    stay a capped lists set (cnt [S,N], idx [S,N,cap], val [S,N,cap]); a draw expands the chosen graphs into the standard
+    lists block the team filter takes (gnnpp_team_lists_gather), so no [N,N] matrix exists between the schedule and
+    training.train_step_lists.  The pool's cap is the largest appended so far."""
+
+    def __init__(self):
+        self.input = self.target = self.cnt = self.idx = self.val = None
+        self.cap = 0
+
+    def __len__(self):
+        return 0 if self.input is None else int(self.input.shape[0])
+
+    @staticmethod
+    def _widen(idx, val, cap):
+        """idx / val with `cap` entries per column, zeros behind the old ones (a copy: off the hot path)."""
+        if idx.shape[2] == cap:
+            return idx, val
+        wide = [torch.zeros(t.shape[0], t.shape[1], cap, dtype=t.dtype, device=t.device) for t in (idx, val)]
+        for w, t in zip(wide, (idx, val)):
+            w[:, :, :t.shape[2]] = t
+        return wide
+
+    def append(self, samples):
+        if getattr(samples, 'cnt', None) is None:
+            raise _native.GnnppError("a SampleListPool takes the samples of samples_from_schedules_team(graph='lists')")
+        if int(samples.cnt.max()) > int(samples.cap):   # (a host read: appending is off the hot path)
+            raise _native.GnnppError('capped lists with a column of %d entries at cap %d are invalid (include/gnnpp.h): '
+                                     'they were filled below their need' % (int(samples.cnt.max()), int(samples.cap)))
+        if self.input is None:
+            self.input, self.target, self.cnt, self.idx, self.val = (
+                t.clone() for t in (samples.input, samples.target, samples.cnt, samples.idx, samples.val))
+            self.cap = int(samples.cap)
+            return
+        if samples.input.shape[1] != self.input.shape[1] or samples.input.device != self.input.device:
+            raise _native.GnnppError('a SampleListPool holds one team size on one device (%d agents on %s)'
+                                     % (self.input.shape[1], self.input.device))
+        cap = max(self.cap, int(samples.cap))
+        old, new = self._widen(self.idx, self.val, cap), self._widen(samples.idx, samples.val, cap)
+        self.idx, self.val = torch.cat((old[0], new[0]), 0), torch.cat((old[1], new[1]), 0)
+        self.input, self.target, self.cnt = (torch.cat((o, t), 0) for o, t in
+                                             zip((self.input, self.target, self.cnt),
+                                                 (samples.input, samples.target, samples.cnt)))
+        self.cap = cap
+
+    def draw(self, batch_size, generator=None):
+        """(batch_input [B,N,3,11,11], batch_target [B,N,5], lists) of batch_size samples drawn as SamplePool.draw draws
+        them; lists: a lists block of B graphs of N nodes (graphML.team_lists_bytes(B, N) bytes): what
+        train_step_lists / DecentralPlannerNet.forward_train_lists(..., symmetric=True) take."""
+        n = len(self)
+        if n == 0:
+            raise _native.GnnppError('the pool is empty')
+        gdev = generator.device if generator is not None else self.input.device
+        if batch_size <= n:
+            idx = torch.randperm(n, generator=generator, device=gdev)[:batch_size]
+        else:
+            idx = torch.randint(n, (batch_size,), generator=generator, device=gdev)
+        return self.gather(idx)
+
+    def gather(self, idx):
+        dev = self.input.device
+        idx = torch.as_tensor(idx, dtype=torch.long).to(dev)
+        B, N = int(idx.numel()), int(self.input.shape[1])
+        L = _native.lib()
+        lists = torch.empty(L.gnnpp_team_lists_bytes(B, N), dtype=torch.uint8, device=dev)
+        index = idx.to(torch.int32)
+        with _native.device_guard(dev):
+            _native.check(L.gnnpp_team_lists_gather(self.cnt.data_ptr(), self.idx.data_ptr(), self.val.data_ptr(),
+                                                    len(self), self.cap, index.data_ptr(), B, lists.data_ptr(),
+                                                    lists.numel(), N, _native.stream_ptr(dev)),
+                          'gnnpp_team_lists_gather')
+        return self.input.index_select(0, idx), self.target.index_select(0, idx), lists

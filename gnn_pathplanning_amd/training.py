@@ -161,7 +161,21 @@ def train_step(model, optimizer, batch_input, batch_target, batch_GSO, dp=None):
     """zero_grad -> addGSO -> forward -> loss -> backward -> (gradient all-reduce) -> step."""
     optimizer.zero_grad()
     model.addGSO(batch_GSO)
-    predict = model(batch_input)
+    return _finish_step(model(batch_input), optimizer, batch_target, dp)
+
+
+def train_step_lists(model, optimizer, batch_input, batch_target, lists, symmetric=True, dp=None):
+    """train_step with the graphs given as a neighbour-lists block of B graphs (expert.SampleListPool.draw,
+    graphML.team_lists_from_dense) instead of a dense batch_GSO: model.forward_train_lists(batch_input, lists,
+    symmetric=symmetric) in the place of addGSO + forward.  symmetric=True is the caller's promise that every graph
+    equals its transpose bit for bit, which holds for the graphs of expert schedules and of the rollout; False spends
+    one graphML.team_lists_transpose launch."""
+    optimizer.zero_grad()
+    return _finish_step(model.forward_train_lists(batch_input, lists, symmetric=symmetric), optimizer, batch_target, dp)
+
+
+def _finish_step(predict, optimizer, batch_target, dp):
+    """loss -> backward -> (gradient all-reduce) -> step for the logits of a train-mode forward."""
     stacked = getattr(predict, 'stacked', None)
     if stacked is not None and stacked.is_cuda:
         # loss and d loss / d logits from one launch; backward starts at the logits (what loss.backward() does,

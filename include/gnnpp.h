@@ -689,6 +689,51 @@ int gnnpp_schedule_samples(const gnnpp_schedules* s, void* stream);
 size_t gnnpp_schedule_team_workspace_bytes(int N, int T_total);   /* 0 on invalid arguments */
 int gnnpp_schedule_team_samples(const gnnpp_schedules* s, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same samples with the graphs kept as CAPPED NEIGHBOUR LISTS up to training: no dense S is written anywhere (the
+ * symbols below were added without a version change, like the lists calls; csrc/expert_team_lists_kernel.hip).
+ * A capped lists set is three device arrays for `graphs` graphs of N nodes and a capacity `cap`, a multiple of 4 with
+ * 4 <= cap <= roundup4(N), each array 16-byte aligned:
+ *     int32 cnt [graphs][N]      uint16 idx [graphs][N][cap]      fp32 val [graphs][N][cap]
+ * A column holds its cnt entries (row index, weight) in ASCENDING row order, then (0, 0.0f) up to the next multiple of
+ * four entries; entries behind the padding are unspecified.  With cap == roundup4(N) the three arrays are the regions of
+ * a standard lists block ("Neighbour lists as an INPUT format" above).  A standard block reserves roundup4(N) entries
+ * per column, more bytes than the dense S; the schedules' graphs have a few dozen neighbours per agent, so a set sized
+ * by the largest degree is what a sample pool can afford to keep (N = 1024, cap = 24: 152 KB per step, S: 4 MB).
+ * The schedule's graph is symmetric bit for bit (the weight is (float)(s_i * s_j) in fp64): the lists of S are those of
+ * S^T, gnnpp_lsigf_team_lists_input_grad takes them as they are.
+ *   gnnpp_schedule_team_plan        the first three launches of gnnpp_schedule_team_samples -- target, radius, growth,
+ *                                   status, step_info and the workspace, byte for byte what that call writes -- and one
+ *                                   more for step_deg [T_total] (device): the largest degree of step t under its
+ *                                   case's final radius, 0 for the steps of a flagged case.  s->obs, s->S and s->S64 may
+ *                                   be NULL and are not written.  Arguments, limits and errors as
+ *                                   gnnpp_schedule_team_samples; step_deg NULL: GNNPP_ERR_ARG.  Four launches.
+ *   gnnpp_schedule_team_fill_lists  reads radius, status and the workspace as gnnpp_schedule_team_plan left them (same
+ *                                   struct, same stream order) and writes s->obs and the capped lists of all T_total
+ *                                   steps (graphs = T_total); s->S and s->S64 are ignored.  The lists of step t are, per
+ *                                   column, the non-zeros of S[t] of gnnpp_schedule_team_samples.  The steps of a
+ *                                   flagged case are left unwritten.  cnt always holds the TRUE degree: where it exceeds
+ *                                   cap only the first cap entries are stored and nothing is written outside the
+ *                                   column -- a consumer must treat cnt > cap as invalid (the caller sizes cap from
+ *                                   step_deg: roundup4 of its maximum).  Errors as the plan call (s->obs required),
+ *                                   plus a cap that is no multiple of 4 in 4 .. roundup4(N), a NULL or not 16-byte
+ *                                   aligned cnt / idx / val: GNNPP_ERR_ARG.  Two launches.
+ *   gnnpp_team_lists_gather         graph b of the standard block `lists` (gnnpp_team_lists_bytes(B, N) bytes, 16-byte
+ *                                   aligned) := graph index[b] of the capped set of graphs_src graphs: cnt and the first
+ *                                   roundup4(cnt) entries of every column -- what the team kernels read; where cnt > cap
+ *                                   (an invalid set) cnt is copied as it is and cap entries.  index [B]: int32, device;
+ *                                   indices may repeat; an index outside [0, graphs_src) is CLAMPED into that range
+ *                                   (never an out-of-range read).  NULL / misaligned pointers, graphs_src or B <= 0, N
+ *                                   outside 1 .. GNNPP_ROLLOUT_MAX_TEAM, a bad cap, a block too small: GNNPP_ERR_ARG.
+ *                                   One launch.
+ * The checks come before any HIP call and nothing is enqueued on an error.  No atomics, one writer per element (two
+ * calls give the same bytes), no host synchronisation, capturable in a HIP graph. */
+int gnnpp_schedule_team_plan(const gnnpp_schedules* s, void* workspace, size_t workspace_bytes, int* step_deg,
+                             void* stream);
+int gnnpp_schedule_team_fill_lists(const gnnpp_schedules* s, const void* workspace, size_t workspace_bytes, int* cnt,
+                                   unsigned short* idx, float* val, int cap, void* stream);
+int gnnpp_team_lists_gather(const int* cnt, const unsigned short* idx, const float* val, int graphs_src, int cap,
+                            const int* index, int B, void* lists, size_t lists_bytes, int N, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MAPF solver: prioritized planning of C cases (the reference's SIPP expert option, offlineExpert/CasesSolver.py:517-539
  * `mapf_prioritized_sipp`, a binary without source).  Per case: a grid (1 = obstacle), starts / goals [N,2] (row, col),

@@ -1,7 +1,7 @@
 """Time one gnnpp_schedule_samples call: agent-samples per second and achieved write bandwidth.
 
     python tools/expert_bench.py [--agents 10] [--side 20] [--steps 1000,32000,256000] [--reps 10] [--out FILE]
-    python tools/expert_bench.py --team [--only 0,2] [--reps 10] [--out FILE]
+    python tools/expert_bench.py --team [--lists] [--only 0,2] [--reps 10] [--out FILE]
 
 Synthetic solved cases (tests/expert_cases.py: ~25 steps each, 64 distinct ones tiled up to the requested number of
 steps) are transformed in ONE call, outputs preallocated, timed with HIP events after warm-up, mean over --reps calls.
@@ -11,7 +11,9 @@ GSO, targets), over the HBM peak bench.py's roofline uses.  One JSON record per 
 --team times gnnpp_schedule_team_samples (5 launches) on its own fixed sizes (TEAM_SIZES): synthetic walks -- every
 agent takes a random legal move or waits, the goal is where it ends -- because the call's time does not depend on whose
 schedule it is.  The 1024-agent sizes are also run with S starting 4 bytes past a 16-byte boundary (the 4-byte store
-path), and the 128-agent size through BOTH entry points.
+path), and the 128-agent size through BOTH entry points.  --lists adds, per size and in the same process, the route that
+keeps the graphs as capped neighbour lists: gnnpp_schedule_team_plan + gnnpp_schedule_team_fill_lists (6 launches) with
+cap = the largest degree rounded up to 4, read from an untimed plan; its bytes are observations, targets and the lists.
 """
 import argparse
 import json
@@ -109,6 +111,31 @@ def team_main(a):
             print(json.dumps(rec), flush=True)
             records.append(rec)
             del out
+        if a.lists:
+            out = outputs(0)
+            out.GSO = None
+            out.step_deg = torch.empty(T, dtype=torch.int32, device=dev)
+            expert.enqueue_schedule_team_plan(grid, goal, pos, start, out)
+            out.cap = cap = max(4, (int(out.step_deg.max().item()) + 3) & ~3)
+            out.cnt = torch.empty(T, N, dtype=torch.int32, device=dev)
+            out.idx = torch.empty(T, N, cap, dtype=torch.int16, device=dev)
+            out.val = torch.empty(T, N, cap, device=dev)
+
+            def lists_route():
+                expert.enqueue_schedule_team_plan(grid, goal, pos, start, out)
+                expert.enqueue_schedule_team_fill_lists(grid, goal, pos, start, out)
+            sec = timed(lists_route, a.reps)
+            assert int(out.status.abs().sum().item()) == 0 and int(out.cnt.max().item()) <= cap
+            nbytes = expert.team_lists_output_bytes(T, N, cap)
+            rec = {'what': 'gnnpp_schedule_team_plan + gnnpp_schedule_team_fill_lists (6 launches), both calls, HIP events, '
+                           'mean of %d calls after 3' % a.reps, 'size': label, 'agents': N, 'map': '%dx%d' % (side, side),
+                   'cases': C, 'steps': T, 'cap': cap, 'ms_per_call': round(sec * 1e3, 4),
+                   'agent_samples_per_s': round(T * N / sec), 'steps_per_s': round(T / sec), 'bytes_written_min': nbytes,
+                   'graph_bytes': T * N * (4 + 6 * cap), 'dense_graph_bytes': 4 * T * N * N,
+                   'write_GBps': round(nbytes / sec / 1e9, 1)}
+            print(json.dumps(rec), flush=True)
+            records.append(rec)
+            del out
         del flat, grid, goal, pos
         torch.cuda.empty_cache()
     return records
@@ -117,6 +144,7 @@ def team_main(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--team', action='store_true', help='gnnpp_schedule_team_samples on TEAM_SIZES')
+    ap.add_argument('--lists', action='store_true', help='--team: also time the capped-lists route (plan + fill_lists)')
     ap.add_argument('--only', default=None, help='--team: indices into TEAM_SIZES, comma separated')
     ap.add_argument('--agents', type=int, default=10)
     ap.add_argument('--side', type=int, default=20)
