@@ -159,3 +159,150 @@ def load_golden():
     meta = json.loads(bytes(z['meta']).decode())
     keys = ('grid', 'goal', 'failure_yaml', 'solution_yaml', 'schedule', 'input', 'GSO', 'target', 'rollout_start')
     return [(m, {k: z['c%d_%s' % (ci, k)] for k in keys if 'c%d_%s' % (ci, k) in z.files}) for ci, m in enumerate(meta)]
+
+
+# ---- hand-built calls: defined once, run under the host emulation and on the device ---------------------------
+# A call is dict(name, grids [H,W] | [C,H,W], goals [C,N,2], schedules [C x [T_c,N,2]], fp64 (whether the call is given
+# an S64 output), status [C x (how, bits)]): ('eq', 0) -- the case is built and must equal reference_samples;
+# ('eq', bits) / ('has', bits) -- its status is / contains the bits and none of its rows is written.
+BAD_MOVE, BAD_STATE = 1, 2                               # GNNPP_SCHEDULE_* status bits
+
+
+def make_call(name, grids, goals, schedules, status=None, fp64=True):
+    return {'name': name, 'grids': np.ascontiguousarray(grids, dtype=np.uint8),
+            'goals': np.ascontiguousarray(np.stack(goals), dtype=np.int32),
+            'schedules': [np.ascontiguousarray(s, dtype=np.int32) for s in schedules],
+            'status': status or [('eq', 0)] * len(schedules), 'fp64': fp64}
+
+
+def flipped(grid, goal, schedule):
+    """The case turned by 180 degrees: another map, the same distances."""
+    shape = np.array(grid.shape)
+    return np.ascontiguousarray(grid[::-1, ::-1]), (shape - 1 - goal).astype(np.int32), \
+        (shape - 1 - schedule).astype(np.int32)
+
+
+def ragged_call(ci=0):
+    """Cases of 25, 7 and 3 steps share a call: golden case ci, its first 7 steps and its last 3 (each a schedule of
+    its own, with its own radius).  A schedule cut at step T is a schedule whose "goal" is the state that followed."""
+    m, g = load_golden()[ci]
+    sched = g['schedule']
+    return make_call('ragged_%d' % ci, g['grid'], [g['goal'], sched[7], g['goal']], [sched, sched[:7], sched[-3:]])
+
+
+def ragged_call_with_a_map_per_case(ci, fp64=True):
+    """ragged_call with a map per case, the middle case turned by 180 degrees (24 agents: 16-byte stores; 10 agents:
+    4-byte stores)."""
+    m, g = load_golden()[ci]
+    sched = g['schedule']
+    other, fgoal, fpart = flipped(g['grid'], sched[7], sched[:7])
+    return make_call('ragged_maps_%d_%s' % (ci, 'fp64' if fp64 else 'fp32'), np.stack([g['grid'], other, g['grid']]),
+                     [g['goal'], fgoal, g['goal']], [sched, fpart, sched[-3:]], fp64=fp64)
+
+
+def batched_maps_call_without_fp64_copy(ci):
+    """One map per case (grid_batched), S64 = NULL: golden case ci turned by 180 degrees, then itself."""
+    m, g = load_golden()[ci]
+    other, fgoal, fsched = flipped(g['grid'], g['goal'], g['schedule'])
+    return make_call('batched_maps_%d' % ci, np.stack([other, g['grid']]), [fgoal, g['goal']], [fsched, g['schedule']],
+                     fp64=False)
+
+
+def status_bits_call():
+    """Golden case 2 six times: legal, a diagonal move, a state on an obstacle, a state off the map, a last state two
+    cells from the goal, legal.  The flags are the kernel's; the legal cases next to them are built as if alone."""
+    m, g = load_golden()[2]
+    sched = g['schedule'].copy()
+    jump = sched.copy()
+    diag = next(d for d in ([1, 1], [1, -1], [-1, 1], [-1, -1]) if g['grid'][tuple(jump[2, 1] + d)] == 0)
+    jump[3, 1] = jump[2, 1] + diag                      # a diagonal move into step 3, onto a free cell
+    obstacle = np.argwhere(g['grid'] != 0)[0]
+    stuck = sched.copy()
+    stuck[1, 0] = obstacle                              # a state on an obstacle (also breaks the moves around it)
+    off = sched.copy()
+    off[0, 4] = [-1, 3]                                 # a state off the map
+    late = sched.copy()
+    late[-1, 2] = g['goal'][2] + [2, 0]                 # the last state is two cells from the goal
+    return make_call('status_bits', g['grid'], [g['goal']] * 6, [sched, jump, stuck, off, late, sched],
+                     [('eq', 0), ('eq', BAD_MOVE), ('has', BAD_STATE), ('has', BAD_STATE), ('has', BAD_MOVE), ('eq', 0)])
+
+
+def calls_without_stage():
+    """128 agents (both halves of every lane pair) and a 230 x 230 map: the occupancy grid leaves no room for the LDS
+    output stage, the rows go straight to memory."""
+    rng = np.random.default_rng(11)
+    grid, goal, paths = random_case(rng, 128, 30, 30, density=0.1, max_steps=3)
+    full = make_call('128_agents_on_30x30', grid, [goal], [schedule_of(paths, goal)])
+    grid, goal, paths = random_case(rng, 3, 230, 230, density=0.05, max_steps=2)
+    return full, make_call('3_agents_on_230x230', grid, [goal], [schedule_of(paths, goal)])
+
+
+def team_growths_call():
+    """A team of 132 spread over the map and one kept in a box share a call, without an S64 output: each gets its own
+    radius."""
+    rng = np.random.default_rng(77)
+    N, side = 132, 48
+    wide = random_case(rng, N, side, side, density=0.05, max_steps=3)
+    tight = random_case(rng, N, side, side, density=0.05, box=(8, 8, 20), max_steps=2)
+    scheds = [schedule_of(paths, goal) for _, goal, paths in (wide, tight)]
+    return make_call('team_growths', np.stack([wide[0], tight[0]]), [wide[1], tight[1]], scheds, fp64=False)
+
+
+def team_status_bits_call():
+    """140 agents, four steps, six times: legal, a diagonal move of agent 133, agent 70 on an obstacle, agent 139 off
+    the map at step 0, agent 0 beyond the last column at step 2, legal."""
+    rng = np.random.default_rng(5)
+    N = 140
+    grid, goal, paths = random_case(rng, N, 44, 44, density=0.1, max_steps=4)
+    sched = schedule_of(paths, goal).astype(np.int32)
+    assert len(sched) == 4
+    jump = sched.copy()
+    diag = next(d for d in ([1, 1], [1, -1], [-1, 1], [-1, -1])
+                if 0 <= min(jump[2, 133] + d) and max(jump[2, 133] + d) < 44 and grid[tuple(jump[2, 133] + d)] == 0)
+    jump[3, 133] = jump[2, 133] + diag                  # a diagonal move into step 3, onto a free cell
+    stuck = sched.copy()
+    stuck[1, 70] = np.argwhere(grid != 0)[0]            # a state on an obstacle (also breaks the moves around it)
+    off = sched.copy()
+    off[0, 139] = [-1, 3]                               # a state off the map
+    off2 = sched.copy()
+    off2[2, 0] = [5, 44]
+    return make_call('team_status_bits', grid, [goal] * 6, [sched, jump, stuck, off, off2, sched],
+                     [('eq', 0), ('eq', BAD_MOVE), ('has', BAD_STATE), ('has', BAD_STATE), ('has', BAD_STATE), ('eq', 0)])
+
+
+_CALL_WANTS = {}
+
+
+def call_wants(call):
+    """reference_samples of every case of the call that is to be built (None for the flagged ones), computed once."""
+    if call['name'] not in _CALL_WANTS:
+        grids = call['grids']
+        _CALL_WANTS[call['name']] = [
+            reference_samples(grids if grids.ndim == 2 else grids[c], call['goals'][c], call['schedules'][c])
+            if call['status'][c] == ('eq', 0) else None for c in range(len(call['schedules']))]
+    return _CALL_WANTS[call['name']]
+
+
+def assert_call_outputs(out, call, poison, untouched=('obs', 'S')):
+    """out: host arrays obs, S, S64 (None when the call has no fp64 copy), target, radius, growth, status, step_info.
+    Every built case equals the restatement, element for element; a flagged case shows its bits and `poison` still
+    fills its rows of the `untouched` outputs."""
+    bounds = np.cumsum([0] + [len(s) for s in call['schedules']])
+    for c, want in enumerate(call_wants(call)):
+        a, b = int(bounds[c]), int(bounds[c + 1])
+        how, bits = call['status'][c]
+        if want is None:
+            assert (out['status'][c] == bits) if how == 'eq' else (out['status'][c] & bits), (c, out['status'][c])
+            for k in untouched:
+                rows = out[k][a:b]
+                assert (np.isnan(rows) if np.isnan(poison) else rows == poison).all(), (c, k)
+            continue
+        assert out['status'][c] == 0, (c, out['status'][c])
+        assert out['radius'][c] == want['radius'] and out['growth'][c] == want['growth'], c
+        assert np.array_equal(out['obs'][a:b], want['input']), c
+        assert np.array_equal(out['target'][a:b], want['target']), c
+        assert np.array_equal(out['S'][a:b], want['GSO'].astype(np.float32)), c
+        if out.get('S64') is not None:
+            assert np.array_equal(out['S64'][a:b], want['GSO']), c
+        info = out['step_info'][a:b]
+        assert (info >> 16 == 0).all() and (info & 0xffff).max() == want['growth'], c

@@ -87,10 +87,10 @@ def test_ragged_cases_in_one_call(lib):
     """Cases of 25, 7 and 3 steps share a call: the 10-agent 20 x 20 case, its first 7 steps and its last 3 (each a
     schedule of its own, with its own radius)."""
     m, g = ec.load_golden()[0]
-    sched = g['schedule']
-    # a schedule cut at step T is a schedule whose "goal" is the state that followed
-    parts, goals = [sched, sched[:7], sched[-3:]], [g['goal'], sched[7], g['goal']]
-    out = call(lib, g['grid'], np.stack(goals), parts)
+    case = ec.ragged_call(0)
+    parts, goals = case['schedules'], case['goals']
+    out = call(lib, case['grids'], goals, parts)
+    ec.assert_call_outputs(out, case, np.nan)
     assert_case_equals_golden(out, 0, m, g)
     assert list(out['start']) == [0, 25, 32, 35]
     for c, part in enumerate(parts):
@@ -106,12 +106,11 @@ def test_ragged_cases_in_one_call(lib):
 def test_batched_maps_and_no_fp64_copy(lib):
     """One map per case (grid_batched), S64 = NULL."""
     gold = ec.load_golden()
-    (m0, g0), (m4, g4) = gold[0], gold[4]              # 10 and 24 agents: two calls; per call two maps
-    for m, g in ((m0, g0), (m4, g4)):
-        other = np.ascontiguousarray(g['grid'][::-1, ::-1])
-        flipped = (np.array(g['grid'].shape) - 1 - g['schedule']).astype(np.int32)
-        fgoal = (np.array(g['grid'].shape) - 1 - g['goal']).astype(np.int32)
-        out = call(lib, np.stack([other, g['grid']]), np.stack([fgoal, g['goal']]), [flipped, g['schedule']], fp64=False)
+    for ci in (0, 4):                                   # 10 and 24 agents: two calls; per call two maps
+        m, g = gold[ci]
+        case = ec.batched_maps_call_without_fp64_copy(ci)
+        other, fgoal, flipped = case['grids'][0], case['goals'][0], case['schedules'][0]
+        out = call(lib, case['grids'], case['goals'], case['schedules'], fp64=False)
         a = int(out['start'][1])
         assert out['status'].tolist() == [0, 0] and out['growth'].tolist() == [m['growth']] * 2
         assert np.array_equal(out['obs'][a:], g['input'].astype(np.float32))
@@ -134,18 +133,11 @@ def test_restatement_equals_reference():
 
 def test_status_bits_flag_only_their_case(lib):
     m, g = ec.load_golden()[2]
-    sched = g['schedule'].copy()
-    jump = sched.copy()
-    diag = next(d for d in ([1, 1], [1, -1], [-1, 1], [-1, -1]) if g['grid'][tuple(jump[2, 1] + d)] == 0)
-    jump[3, 1] = jump[2, 1] + diag                      # a diagonal move into step 3, onto a free cell
-    obstacle = np.argwhere(g['grid'] != 0)[0]
-    stuck = sched.copy()
-    stuck[1, 0] = obstacle                              # a state on an obstacle (also breaks the moves around it)
-    off = sched.copy()
-    off[0, 4] = [-1, 3]                                 # a state off the map
-    late = sched.copy()
-    late[-1, 2] = g['goal'][2] + [2, 0]                 # the last state is two cells from the goal
+    case = ec.status_bits_call()
+    sched, jump, stuck, off, late, _ = case['schedules']
+    assert [len(x) for x in case['schedules']] == [len(sched)] * 6
     out = call(lib, g['grid'], np.stack([g['goal']] * 6), [sched, jump, stuck, off, late, sched])
+    ec.assert_call_outputs(out, case, np.nan)
     assert out['status'][0] == 0 and out['status'][5] == 0
     assert out['status'][1] == BAD_MOVE
     assert out['status'][2] & BAD_STATE and out['status'][3] & BAD_STATE
@@ -183,17 +175,12 @@ def test_argument_errors(lib):
 def test_large_team_and_map_without_stage(lib):
     """128 agents (both halves of every lane pair) and a 230 x 230 map: the occupancy grid leaves no room for the LDS
     output stage, the rows go straight to memory."""
-    rng = np.random.default_rng(11)
-    grid, goal, paths = ec.random_case(rng, 128, 30, 30, density=0.1, max_steps=3)
-    sched = ec.schedule_of(paths, goal)
-    out = call(lib, grid, goal[None], [sched])
-    want = ec.reference_samples(grid, goal, sched)
-    assert out['status'][0] == 0 and out['radius'][0] == want['radius'] and out['growth'][0] == want['growth']
-    assert np.array_equal(out['obs'], want['input']) and np.array_equal(out['S64'], want['GSO'])
-    assert np.array_equal(out['target'], want['target'])
-    grid, goal, paths = ec.random_case(rng, 3, 230, 230, density=0.05, max_steps=2)
-    sched = ec.schedule_of(paths, goal)
-    out = call(lib, grid, goal[None], [sched])
-    want = ec.reference_samples(grid, goal, sched)
-    assert out['status'][0] == 0 and out['radius'][0] == want['radius'] and out['growth'][0] == want['growth']
-    assert np.array_equal(out['obs'], want['input']) and np.array_equal(out['S64'], want['GSO'])
+    full, wide = ec.calls_without_stage()
+    for case in (full, wide):
+        out = call(lib, case['grids'], case['goals'], case['schedules'])
+        ec.assert_call_outputs(out, case, np.nan)
+        want = ec.call_wants(case)[0]
+        assert out['status'][0] == 0 and out['radius'][0] == want['radius'] and out['growth'][0] == want['growth']
+        assert np.array_equal(out['obs'], want['input']) and np.array_equal(out['S64'], want['GSO'])
+        assert np.array_equal(out['target'], want['target'])
+    assert full['goals'].shape[1] == 128 and wide['grids'].shape == (230, 230)

@@ -150,13 +150,11 @@ def test_ragged_cases_and_batched_maps_same_bytes_as_one_wave_call(lib):
     """Cases of 20, 7 and 3 steps with a map each (24 agents: 16-byte stores; 10 agents: 4-byte stores)."""
     for ci in (4, 0):
         m, g = ec.load_golden()[ci]
-        sched = g['schedule']
-        shape = np.array(g['grid'].shape)
-        parts = [sched, (shape - 1 - sched[:7]).astype(np.int32), sched[-3:]]
-        goals = [g['goal'], (shape - 1 - sched[7]).astype(np.int32), g['goal']]
-        grids = np.stack([g['grid'], np.ascontiguousarray(g['grid'][::-1, ::-1]), g['grid']])
         for fp64 in (False, True):
+            case = ec.ragged_call_with_a_map_per_case(ci, fp64)
+            parts, goals, grids = case['schedules'], case['goals'], case['grids']
             out = call(lib, grids, np.stack(goals), parts, fp64=fp64)
+            ec.assert_call_outputs(dict(out, S64=out['S64'] if fp64 else None), case, np.nan)
             assert_same_bytes(out, call(lib, grids, np.stack(goals), parts, fp64=fp64, team=False))
             assert out['status'].tolist() == [0, 0, 0]
             if not fp64:
@@ -171,6 +169,10 @@ def test_unaligned_graph_outputs_give_the_same_bytes(lib):
     m, g = load_team_golden()[0]
     out = call(lib, g['grid'], g['goal'][None], [g['schedule']], misalign=True)
     assert_case_equals_golden(out, 0, m, g)
+    case = ec.ragged_call_with_a_map_per_case(4, True)  # (24 agents: the rows are 16-byte multiples)
+    out = call(lib, case['grids'], case['goals'], case['schedules'], misalign=True)
+    ec.assert_call_outputs(out, case, np.nan)
+    assert_same_bytes(out, call(lib, case['grids'], case['goals'], case['schedules']))
 
 
 @pytest.mark.parametrize('N,side,steps', [(129, 40, 3), (130, 60, 3), (191, 50, 2), (512, 90, 2)])
@@ -184,14 +186,11 @@ def test_random_case_against_restatement(lib, N, side, steps):
 
 def test_cases_of_different_growths_in_one_call_without_fp64_copy(lib):
     """A team spread over the map and one kept in a box share a call: each gets its own radius."""
-    rng = np.random.default_rng(77)
-    N, side = 132, 48
-    wide = ec.random_case(rng, N, side, side, density=0.05, max_steps=3)
-    tight = ec.random_case(rng, N, side, side, density=0.05, box=(8, 8, 20), max_steps=2)
-    scheds = [ec.schedule_of(paths, goal) for _, goal, paths in (wide, tight)]
-    out = call(lib, np.stack([wide[0], tight[0]]), np.stack([wide[1], tight[1]]), scheds, fp64=False)
-    wants = [assert_case_equals_restatement(out, c, case[0], case[1], scheds[c], fp64=False)
-             for c, case in enumerate((wide, tight))]
+    case = ec.team_growths_call()
+    scheds = case['schedules']
+    out = call(lib, case['grids'], case['goals'], scheds, fp64=False)
+    wants = [assert_case_equals_restatement(out, c, case['grids'][c], case['goals'][c], scheds[c], fp64=False)
+             for c in (0, 1)]
     assert wants[0]['growth'] != wants[1]['growth']
     assert np.isnan(out['S64']).all()
     for c in (0, 1):                                    # step_info: every step's own growths, the case's the largest
@@ -201,22 +200,11 @@ def test_cases_of_different_growths_in_one_call_without_fp64_copy(lib):
 
 
 def test_status_bits_flag_only_their_case(lib):
-    rng = np.random.default_rng(5)
-    N = 140
-    grid, goal, paths = ec.random_case(rng, N, 44, 44, density=0.1, max_steps=4)
-    sched = ec.schedule_of(paths, goal).astype(np.int32)
-    assert len(sched) == 4
-    jump = sched.copy()
-    diag = next(d for d in ([1, 1], [1, -1], [-1, 1], [-1, -1])
-                if 0 <= min(jump[2, 133] + d) and max(jump[2, 133] + d) < 44 and grid[tuple(jump[2, 133] + d)] == 0)
-    jump[3, 133] = jump[2, 133] + diag                  # a diagonal move into step 3, onto a free cell
-    stuck = sched.copy()
-    stuck[1, 70] = np.argwhere(grid != 0)[0]            # a state on an obstacle (also breaks the moves around it)
-    off = sched.copy()
-    off[0, 139] = [-1, 3]                               # a state off the map
-    off2 = sched.copy()
-    off2[2, 0] = [5, 44]
+    case = ec.team_status_bits_call()
+    grid, goal = case['grids'], case['goals'][0]
+    sched, jump, stuck, off, off2, _ = case['schedules']
     out = call(lib, grid, np.stack([goal] * 6), [sched, jump, stuck, off, off2, sched])
+    ec.assert_call_outputs(out, case, np.nan, untouched=('obs', 'S', 'S64', 'target'))
     assert out['status'][0] == 0 and out['status'][5] == 0
     assert out['status'][1] == BAD_MOVE
     assert out['status'][2] & BAD_STATE and out['status'][3] & BAD_STATE and out['status'][4] & BAD_STATE

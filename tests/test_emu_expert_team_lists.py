@@ -3,7 +3,7 @@
 neighbour lists against the lists of what the REAL reference transformer made (tests/golden/expert_schedules_team.npz),
 of the sequential restatement tests/expert_cases.py::reference_samples on random cases, and of
 gnnpp_schedule_team_samples' own S; every other output against that call's, byte for byte.  Equality everywhere.
-Statement and runner: tests/expert_team_lists_cases.py."""
+Statement, runner and the hand-built cases (run on the device too): tests/expert_team_lists_cases.py."""
 import ctypes
 import os
 import sys
@@ -30,12 +30,7 @@ def lib():
     return lc.bind(emu_lib.load())
 
 
-def assert_plan_outputs_equal_dense(h, dense, obs=True):
-    """target, radius, growth, status, step_info, the workspace (and obs) byte for byte what the dense call writes --
-    NaN poison included: the same elements are left unwritten."""
-    for k in lc.PLAN_OUTPUTS + (('obs',) if obs else ()):
-        assert h.out[k].tobytes() == dense[k].tobytes(), k
-    assert h.ws.tobytes() == dense['ws'].tobytes()
+assert_plan_outputs_equal_dense = lc.assert_plan_outputs_equal_dense
 
 
 def true_step_deg(S32):
@@ -61,28 +56,13 @@ def test_golden_case(lib, ci, N, deg):
         assert a.tobytes() == b.tobytes()
 
 
-def _random(N, side, steps, seed, **kw):
-    rng = np.random.default_rng(seed)
-    grid, goal, paths = ec.random_case(rng, N, side, side, max_steps=steps, **kw)
-    return grid, goal, ec.schedule_of(paths, goal)
-
-
-def _want(grid, goal, sched, radius0=5.0):
-    return ec.reference_samples(grid, goal, sched, radius0)['GSO'].astype(np.float32)
+_random, _want = lc.random_schedule, lc.want_gso
 
 
 @pytest.mark.parametrize('N,side', [(2, 3), (5, 4), (7, 4), (130, 17)])
 def test_tiny_map_where_everybody_neighbours_everybody(lib, N, side):
-    """radius0 = 30 spans the whole map: degree N - 1 everywhere.  cap = roundup4(N - 1), which is roundup4(N) -- the
-    standard block's stride -- unless N = 1 mod 4; at N = 5 the degree 4 IS cap: a column without padding."""
-    grid, goal, sched = _random(N, side, 3, 40 + N, density=0.0)
-    h = lc.plan_and_fill(lib, grid, goal[None], [sched], radius0=30.0)
-    assert (h.out['step_deg'] == N - 1).all() and h.cap == lc.roundup4(N - 1)
-    assert h.cap == (lc.roundup4(N) if N % 4 != 1 else N - 1)
-    assert (h.out['cnt'] == N - 1).all()
-    lc.check_lists('full %d' % N, *h.lists(), lc.lists_of_dense(_want(grid, goal, sched, 30.0)))
-    assert h.margins_intact()
-    assert_plan_outputs_equal_dense(h, h.dense())
+    assert (N, side) in lc.TINY_MAPS
+    lc.case_tiny_map_where_everybody_neighbours_everybody(lib, N, side)
 
 
 @pytest.mark.parametrize('N,side,steps', [(2, 6, 3), (5, 9, 4), (7, 12, 4), (130, 60, 3)])
@@ -95,136 +75,56 @@ def test_random_case_against_restatement(lib, N, side, steps):
     assert_plan_outputs_equal_dense(h, h.dense())
 
 
-def _chain7():
-    """Seven agents waiting in a row, four cells apart: at most two neighbours each under radius 5."""
-    pos = np.stack([np.zeros(7, np.int64), 4 * np.arange(7)], 1)
-    return np.zeros((1, 30), np.uint8), pos, np.stack([pos, pos])
-
-
 @pytest.mark.parametrize('N', [7, 130])
 def test_set_four_entries_wider_than_needed(lib, N):
-    """The tail of every column stays poison (a chain of 7 at the standard stride 8; a random team of 130)."""
-    grid, goal, sched = _chain7() if N == 7 else _random(N, 60, 3, 1000 + N, density=0.1)
-    want = lc.lists_of_dense(_want(grid, goal, sched))
-    h = lc.plan_and_fill(lib, grid, goal[None], [sched])
-    assert h.cap + 4 <= lc.roundup4(N)
-    wide = lc.plan_and_fill(lib, grid, goal[None], [sched], extra=4)
-    assert wide.cap == h.cap + 4
-    lc.check_lists('wide %d' % N, *wide.lists(), want)
-    assert (wide.out['idx'][:, :, h.cap:] == 0xFFFF).all()
-    assert (wide.out['val'][:, :, h.cap:].view(np.uint32) == 0xFFFFFFFF).all()
-    assert wide.margins_intact()
-    lc.same_lists('wide %d' % N, wide.lists(), h.lists())
+    lc.case_set_four_entries_wider_than_needed(lib, N)
 
 
 def test_largest_degree_exactly_cap(lib):
-    """129 agents on a 17 x 17 map that radius0 = 30 spans: degree 128 = cap, below the standard stride of 132; every
-    column is full, no padding anywhere, and the last store of a column ends where the next column begins."""
-    N = 129
-    grid, goal, sched = _random(N, 17, 2, 7, density=0.0)
-    h = lc.plan_and_fill(lib, grid, goal[None], [sched], radius0=30.0)
-    assert h.cap == 128 and (h.out['cnt'] == 128).all() and h.cap < lc.roundup4(N)
-    lc.check_lists('exact', *h.lists(), lc.lists_of_dense(_want(grid, goal, sched, 30.0)))
-    assert h.margins_intact()
+    lc.case_largest_degree_exactly_cap(lib)
 
 
 def test_flagged_case_between_two_good_ones(lib):
-    N = 130
-    grid, goal, sched = _random(N, 44, 3, 5, density=0.1)
-    bad = sched.copy()
-    bad[1, 70] = np.argwhere(grid != 0)[0]              # a state on an obstacle
-    h = lc.HostCall(lib, grid, np.stack([goal] * 3), [sched, bad, sched]).plan()
-    T = len(sched)
-    assert h.out['status'][0] == 0 and h.out['status'][1] != 0 and h.out['status'][2] == 0
-    assert (h.out['step_deg'][T:2 * T] == 0).all() and (h.out['step_deg'][:T] > 0).all()
-    h.fill(max(4, lc.roundup4(h.out['step_deg'].max())))
-    want = lc.lists_of_dense(_want(grid, goal, sched))
-    lc.check_lists('left', *h.lists(), want, graphs=[(t, t) for t in range(T)])
-    lc.check_lists('right', *h.lists(), want, graphs=[(2 * T + t, t) for t in range(T)])
-    for k in ('cnt', 'idx', 'val'):                     # the flagged case's steps stay poison
-        assert (h.out[k][T:2 * T].view(np.uint8) == 0xFF).all(), k
-    assert np.isnan(h.out['obs'][T:2 * T]).all() and np.isnan(h.out['target'][T:2 * T]).all()
-    assert h.margins_intact()
-    assert_plan_outputs_equal_dense(h, h.dense())
-    alone = lc.plan_and_fill(lib, grid, goal[None], [sched])
-    for k in ('cnt', 'idx', 'val', 'obs'):              # the neighbours are unaffected
-        assert h.out[k][:T].tobytes() == alone.out[k].tobytes() == h.out[k][2 * T:].tobytes(), k
+    lc.case_flagged_case_between_two_good_ones(lib)
 
 
 @pytest.mark.parametrize('N,side,radius0', [(130, 60, 5.0), (7, 4, 30.0)])
 def test_cap_four_below_the_need(lib, N, side, radius0):
-    """cnt is the true degree, the first cap entries are right, nothing is written outside a column's cap entries."""
-    grid, goal, sched = _random(N, side, 3, 1000 + N, density=0.1 if N > 7 else 0.0)
-    h = lc.HostCall(lib, grid, goal[None], [sched], radius0).plan()
-    need = lc.roundup4(h.out['step_deg'].max())
-    assert need >= 8
-    h.fill(need - 4)
-    assert (h.out['cnt'] > need - 4).any() and h.out['cnt'].max() == h.out['step_deg'].max()
-    lc.check_lists('short %d' % N, *h.lists(), lc.lists_of_dense(_want(grid, goal, sched, radius0)), cap=need - 4)
-    assert h.margins_intact()
-    full = lc.HostCall(lib, grid, goal[None], [sched], radius0).plan().fill(need)
-    assert (h.out['cnt'] == full.out['cnt']).all()
-    live = np.arange(need - 4)[None, None, :] < ((full.out['cnt'] + 3) & ~3)[:, :, None]
-    assert (h.out['idx'][live] == full.out['idx'][:, :, :need - 4][live]).all()
+    assert (N, side, radius0) in lc.SHORT_CAPS
+    lc.case_cap_four_below_the_need(lib, N, side, radius0)
 
 
 # ---- gnnpp_team_lists_gather ------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def pool(lib):
     """The capped set of the 5 steps of a 130-agent case, its dense S and the standard blocks of S."""
-    grid, goal, sched = _random(130, 60, 5, 2030, density=0.1)
-    h = lc.plan_and_fill(lib, grid, goal[None], [sched])
-    return h, h.dense()['S']
-
-
-def _from_dense(lib, S):
-    graphs, N = S.shape[:2]
-    nbytes = lib.gnnpp_team_lists_bytes(graphs, N)
-    raw, block = lc.guarded(nbytes)
-    S = np.ascontiguousarray(S)
-    assert lib.gnnpp_team_lists_from_dense(S.ctypes.data, block.ctypes.data, nbytes, graphs, N, 0, None) == 0
-    return block
+    return lc.gather_pool(lib)
 
 
 @pytest.mark.parametrize('index', [[0, 1, 2, 3, 4], [2, 2, 0, 2], [4, 3, 2, 1, 0], [3]],
                          ids=['identity', 'repeated', 'reversed', 'B1'])
 def test_gather(lib, pool, index):
-    h, S = pool
-    N, B = h.N, len(index)
-    raw, block = lc.host_gather(lib, h.lists(), h.T, h.cap, index, N)
-    assert lc.margins_intact(raw, block)
-    got = lc.block_views(block, B, N)
-    want = _from_dense(lib, S[index])
-    lc.same_lists('gather', got, lc.block_views(want, B, N))
-    lc.check_lists('gather', *got, lc.lists_of_dense(S[index]))
-    nbytes = lib.gnnpp_team_lists_bytes(B, N)                                  # symmetry: the lists of S^T are the same
-    rawt, blockt = lc.guarded(nbytes)
-    assert lib.gnnpp_team_lists_transpose(block.ctypes.data, blockt.ctypes.data, nbytes, B, N, None) == 0
-    lc.same_lists('transpose', got, lc.block_views(blockt, B, N))
-    # entries behind roundup4(cnt) are not copied
-    cnt, idx, _ = got
-    behind = np.arange(idx.shape[2])[None, None, :] >= ((cnt + 3) & ~3)[:, :, None]
-    assert (idx[behind] == 0xFFFF).all()
+    assert index in lc.GATHERS.values()
+    lc.case_gather(lib, pool, index)
 
 
 def test_gather_clamps_an_index_out_of_range(lib, pool):
-    """include/gnnpp.h: an index outside [0, graphs_src) is clamped into that range."""
-    h, S = pool
-    raw, block = lc.host_gather(lib, h.lists(), h.T, h.cap, [-3, 5, 1 << 30, 1], h.N)
-    assert lc.margins_intact(raw, block)
-    lc.check_lists('clamped', *lc.block_views(block, 4, h.N), lc.lists_of_dense(S[[0, 4, 4, 1]]))
+    lc.case_gather_clamps_an_index_out_of_range(lib, pool)
 
 
 def test_gather_from_a_set_at_the_standard_stride(lib):
-    """cap == roundup4(N), N % 4 != 0: the three arrays are the regions of a standard block."""
-    N = 7
-    grid, goal, sched = _random(N, 4, 3, 47, density=0.0)
-    h = lc.plan_and_fill(lib, grid, goal[None], [sched], radius0=30.0)
-    assert h.cap == 8 == lc.roundup4(N)
-    raw, block = lc.host_gather(lib, h.lists(), h.T, h.cap, np.arange(h.T), N)
-    for a, b in zip(lc.block_views(block, h.T, N), h.lists()):
-        assert a.tobytes() == b.tobytes()
-    assert lc.margins_intact(raw, block)
+    lc.case_gather_from_a_set_at_the_standard_stride(lib)
+
+
+def test_runner_with_twins_of_every_array(lib):
+    """lc.DeviceRunner, which the device tests run every case through, on twins in host memory: the emulated library
+    sees only the twins, and the cases hold as they do on the arrays themselves."""
+    run = lc.DeviceRunner('cpu')
+    lc.case_tiny_map_where_everybody_neighbours_everybody(lib, 5, 4, run)
+    lc.case_flagged_case_between_two_good_ones(lib, run)
+    lc.case_gather(lib, lc.gather_pool(lib, run), [2, 2, 0, 2], run)
+    with pytest.raises(AssertionError, match='lies in none of the buffers'):
+        run(lib.gnnpp_team_lists_bytes, (1 << 40, 4), [])
 
 
 # ---- errors -----------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """CPU: gnnpp_mapf_solve (csrc/mapf_kernels.hip), compiled unmodified for the host emulation, against the sequential
 numpy restatement of the contract (tests/mapf_cases.py): equality of every output element, on small random cases and
-on hand-built edge cases."""
+on hand-built edge cases.  The cases are built in mapf_cases.ONE_WAVE, with the facts the yardstick's answer must show;
+tests/test_gpu_mapf_cases.py runs the same ones on the device."""
 import ctypes
 import os
 import sys
@@ -18,7 +19,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang
                                 reason='host clang++ from ROCm not present')
 
 ERR_ARG, ERR_UNSUPPORTED = -1, -2
-POISON = -7
+POISON = mc.POISON
 
 
 class Mapf(ctypes.Structure):
@@ -68,160 +69,67 @@ def call(lib, grids, starts, goals, T, orders=None, expect=0, ws_bytes=None):
     return out
 
 
-def assert_matches(out, c, want):
-    for k in ('status', 'restart', 'makespan', 'flowtime', 'failing'):
-        assert int(out[k][c]) == want[k], (k, int(out[k][c]), want[k])
-    assert np.array_equal(out['arrival'][c], want['arrival'])
-    assert np.array_equal(out['schedule'][c], want['schedule'])
-
-
-def run_and_compare(lib, cases, T, orders=None, batched=True):
-    """cases: [(grid, starts, goals)] of one map size; every output of every case equal to the yardstick's."""
-    grids = np.stack([g for g, _, _ in cases]) if batched else cases[0][0]
-    out = call(lib, grids, np.stack([s for _, s, _ in cases]), np.stack([g for _, _, g in cases]), T, orders)
-    wants = []
-    for c, (g, s, gl) in enumerate(cases):
-        want = mc.solve_case(g, s, gl, T, None if orders is None else list(orders[c]))
-        assert_matches(out, c, want)
-        wants.append(want)
+def run_case(lib, name, shared=False):
+    """One call of a case of mapf_cases.ONE_WAVE: every output of every case equal to the yardstick's, the case's facts
+    asserted on the yardstick's answer (mc.wants_of).  shared: the map of case 0 passed once, for the whole call."""
+    case = mc.ONE_WAVE[name]()
+    out = call(lib, case['grid'][0] if shared else case['grid'], case['starts'], case['goals'], case['T'], case['orders'])
+    wants = mc.wants_of(case)
+    mc.assert_outputs_equal(out, wants)
     return out, wants
 
 
 def test_random_cases_equal_the_restatement(lib):
-    rng = np.random.default_rng(5)
-    cases = mc.random_cases(rng, 6, 6, 10, density=0.15)
-    out, wants = run_and_compare(lib, cases, mc.default_horizon(10, 10))
-    assert any(w['status'] == 0 for w in wants)
+    run_case(lib, 'random_10x10')
 
 
 def test_crowded_cases_with_failures(lib):
     """Dense maps and many agents: some cases end with NO_PATH, the agents after the failing one left unplanned."""
-    rng = np.random.default_rng(8)
-    cases = mc.random_cases(rng, 6, 10, 7, density=0.25)
-    out, wants = run_and_compare(lib, cases, 20)
-    assert {w['status'] for w in wants} == {0, mc.NO_PATH}
+    run_case(lib, 'crowded_cases_with_failures')
 
 
 def test_agent_on_its_goal_steps_aside_and_comes_back(lib):
-    grid = np.array([[1, 1, 0, 1, 1],
-                     [0, 0, 0, 0, 0],
-                     [1, 1, 1, 1, 1]], np.uint8)
-    starts, goals = np.array([[1, 0], [1, 2]]), np.array([[1, 4], [1, 2]])
-    out = call(lib, grid, starts[None], goals[None], 12)
-    want = mc.solve_case(grid, starts, goals, 12)
-    assert_matches(out, 0, want)
-    assert want['arrival'].tolist() == [4, 3]
-    assert want['schedule'][1:4, 1].tolist() == [[0, 2], [0, 2], [1, 2]]
+    run_case(lib, 'agent_on_its_goal_steps_aside_and_comes_back')
 
 
 def test_target_conflict(lib):
-    grid = np.zeros((3, 7), np.uint8)
-    starts, goals = np.array([[1, 0], [0, 3]]), np.array([[1, 6], [1, 3]])
-    out = call(lib, grid, starts[None], goals[None], 20)
-    want = mc.solve_case(grid, starts, goals, 20)
-    assert_matches(out, 0, want)
-    assert want['arrival'].tolist() == [6, 4]                   # not 1: agent 0 crosses the goal at t = 3
+    run_case(lib, 'target_conflict')
 
 
 def test_swap_is_not_a_shortcut(lib):
-    grid = np.zeros((2, 2), np.uint8)
-    starts, goals = np.array([[0, 0], [0, 1]]), np.array([[0, 1], [0, 0]])
-    out = call(lib, grid, starts[None], goals[None], 8)
-    want = mc.solve_case(grid, starts, goals, 8)
-    assert_matches(out, 0, want)
-    assert want['arrival'].tolist() == [1, 3]                   # the swap would have taken 1 step
+    run_case(lib, 'swap_is_not_a_shortcut')
 
 
 def test_walled_in_agent_stops_the_plan(lib):
-    grid = np.zeros((6, 6), np.uint8)
-    grid[3:6, 3] = 1
-    grid[3, 3:6] = 1                                            # (4,4), (4,5), (5,4), (5,5) walled in
-    starts = np.array([[0, 0], [5, 5], [0, 5], [2, 0]])
-    goals = np.array([[1, 1], [0, 3], [2, 5], [1, 0]])
-    out = call(lib, grid, starts[None], goals[None], 30)
-    want = mc.solve_case(grid, starts, goals, 30)
-    assert_matches(out, 0, want)
-    assert want['status'] == mc.NO_PATH and want['failing'] == 1
-    assert want['arrival'][2:].tolist() == [-1, -1] and (want['schedule'][:, 1:] == -1).all()
+    out, _ = run_case(lib, 'walled_in_agent_stops_the_plan')
     assert out['makespan'][0] == -1 and out['flowtime'][0] == -1
 
 
 def test_bad_cases_flag_only_themselves(lib):
-    grid = np.zeros((5, 5), np.uint8)
-    grid[2, 2] = 1
-    ok_s, ok_g = np.array([[0, 0], [4, 4], [0, 4]]), np.array([[4, 0], [0, 0], [4, 4]])
-    variants = []
-    for k, v in (('s', [-1, 0]), ('s', [0, 5]), ('g', [5, 1]), ('g', [1, -1]), ('s', [2, 2]), ('g', [2, 2]),
-                 ('s', [4, 4]), ('g', [0, 0])):
-        s, g = ok_s.copy(), ok_g.copy()
-        (s if k == 's' else g)[0] = v                           # off the map, on the obstacle, a duplicate
-        variants.append((s, g))
-    starts = np.stack([ok_s] + [s for s, _ in variants] + [ok_s, ok_s, ok_s])
-    goals = np.stack([ok_g] + [g for _, g in variants] + [ok_g, ok_g, ok_g])
-    C = len(starts)
-    orders = np.tile(np.array([[0, 1, 2], [2, 1, 0]]), (C, 1, 1))
-    orders[-3, 1] = [0, 0, 2]                                   # not a permutation
-    orders[-2, 0] = [0, 1, 3]                                   # out of range
-    out = call(lib, grid, starts, goals, 16, orders)
-    for c in range(C):
-        want = mc.solve_case(grid, starts[c], goals[c], 16, list(orders[c]))
-        assert_matches(out, c, want)
-        assert (want['status'] == mc.BAD_CASE) == (c not in (0, C - 1)), c
+    out, _ = run_case(lib, 'bad_cases_flag_only_themselves')
     assert out['status'][0] == 0 and out['status'][-1] == 0
 
 
 @pytest.mark.parametrize('H,W', [(64, 64), (5, 64), (64, 5)])
 def test_widest_and_tallest_maps(lib, H, W):
     """Bit 63 of a row and lane 63 of the wave."""
-    grid = np.zeros((H, W), np.uint8)
-    grid[H // 2, 1:W - 1] = 1
-    starts = np.array([[0, 0], [H - 1, 0], [0, W - 1]])
-    goals = np.array([[H - 1, W - 1], [0, W - 1], [H - 1, 0]])
-    T = 2 * (H + W)
-    out = call(lib, grid, starts[None], goals[None], T)
-    want = mc.solve_case(grid, starts, goals, T)
-    assert want['status'] == 0
-    assert_matches(out, 0, want)
+    run_case(lib, 'widest_and_tallest_maps_%dx%d' % (H, W))
 
 
 def test_non_square_random_maps(lib):
-    rng = np.random.default_rng(13)
-    run_and_compare(lib, mc.random_cases(rng, 3, 5, 7, 13, density=0.1), 40)
-    run_and_compare(lib, mc.random_cases(rng, 3, 5, 13, 7, density=0.1), 40)
+    run_case(lib, 'non_square_7x13')
+    run_case(lib, 'non_square_13x7')
 
 
 def test_restarts_pick_the_best_and_ties_the_lowest(lib):
-    rng = np.random.default_rng(21)
-    cases = mc.random_cases(rng, 4, 8, 8, density=0.2)
-    N = 8
-    orders = np.stack([np.stack([np.arange(N)] + [rng.permutation(N) for _ in range(3)]) for _ in cases])
-    orders[1, 2] = orders[1, 0]                                 # restart 2 repeats restart 0: a tie
-    orders[2, 1:] = orders[2, 0]                                # every restart the same order
-    out, wants = run_and_compare(lib, cases, 32, orders)
-    assert wants[2]['restart'] == 0 and out['restart'][1] != 2
-    # the index order fails (agent 0 parks in the corridor agent 1 must cross), the reversed order solves the case;
-    # restart 2 repeats restart 1: the tie keeps restart 1
-    grid = np.array([[0, 0, 0],
-                     [1, 0, 1]], np.uint8)
-    starts, goals = np.array([[1, 1], [0, 0]]), np.array([[0, 1], [0, 2]])
-    orders = np.array([[[0, 1], [1, 0], [1, 0]]])
-    out = call(lib, grid, starts[None], goals[None], 10, orders)
-    want = mc.solve_case(grid, starts, goals, 10, list(orders[0]))
-    assert_matches(out, 0, want)
-    assert mc.plan_order(grid, starts, goals, [0, 1], 10)[0] == mc.NO_PATH
-    assert want['restart'] == 1 and want['status'] == 0 and want['arrival'].tolist() == [2, 2]
+    out, _ = run_case(lib, 'restarts_pick_the_best_and_ties_the_lowest')
+    assert out['restart'][1] != 2
+    run_case(lib, 'only_the_reversed_order_solves')
 
 
 def test_batched_grid_next_to_shared_grid(lib):
-    rng = np.random.default_rng(34)
-    grid, _, _ = mc.random_cases(rng, 1, 5, 9)[0]
-    cases = []
-    for _ in range(3):
-        free = np.argwhere(grid == 0)
-        idx = rng.choice(len(free), 10, replace=False)
-        cases.append((grid, free[idx[:5]], free[idx[5:]]))
-    shared, _ = run_and_compare(lib, cases, 36, batched=False)
-    batched, _ = run_and_compare(lib, cases, 36, batched=True)
+    shared, _ = run_case(lib, 'batched_grid_next_to_shared_grid', shared=True)
+    batched, _ = run_case(lib, 'batched_grid_next_to_shared_grid')
     for k in shared:
         assert np.array_equal(shared[k], batched[k]), k
 

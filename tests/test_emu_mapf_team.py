@@ -2,7 +2,8 @@
 sequential numpy restatement of the contract (tests/mapf_cases.py): equality of every output element.  The shapes are
 small (a lane-accurate workgroup is slow) but cross every boundary of the layout: teams beyond 128 agents, rows of two
 and three words (W = 65, 128, 129), more than one wave of rows (H = 65 .. 70), and the one-wave call's own sizes, where
-the two entry points must write the same bytes."""
+the two entry points must write the same bytes.  The cases are built in mapf_cases.TEAM and mapf_cases.BOTH, with the
+facts the yardstick's answer must show; tests/test_gpu_mapf_cases.py runs the same ones on the device."""
 import ctypes
 import os
 import sys
@@ -20,7 +21,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang
                                 reason='host clang++ from ROCm not present')
 
 ERR_ARG, ERR_UNSUPPORTED = -1, -2
-POISON = -7
+POISON = mc.POISON
 KEYS = ('status', 'restart', 'makespan', 'flowtime', 'failing', 'arrival', 'schedule')
 
 
@@ -87,247 +88,104 @@ def call(lib, grids, starts, goals, T, orders=None, expect=0, ws_bytes=None, tea
     return out
 
 
-def assert_matches(out, c, want):
-    for k in ('status', 'restart', 'makespan', 'flowtime', 'failing'):
-        assert int(out[k][c]) == want[k], (k, int(out[k][c]), want[k])
-    assert np.array_equal(out['arrival'][c], want['arrival'])
-    assert np.array_equal(out['schedule'][c], want['schedule'])
-
-
-def run_and_compare(lib, cases, T, orders=None, batched=True, **kw):
-    """cases: [(grid, starts, goals)] of one map size; every output of every case equal to the yardstick's."""
-    grids = np.stack([g for g, _, _ in cases]) if batched else cases[0][0]
-    out = call(lib, grids, np.stack([s for _, s, _ in cases]), np.stack([g for _, _, g in cases]), T, orders, **kw)
-    wants = []
-    for c, (g, s, gl) in enumerate(cases):
-        want = mc.solve_case(g, s, gl, T, None if orders is None else list(orders[c]))
-        assert_matches(out, c, want)
-        wants.append(want)
-    return out, wants
-
-
 def assert_same_bytes(a, b):
     for k in KEYS:
         assert a[k].tobytes() == b[k].tobytes(), k
 
 
+def run_case(lib, name, shared=False, ws_bytes=None):
+    """One call of a case of mapf_cases.TEAM: every output of every case equal to the yardstick's, the case's facts
+    asserted on the yardstick's answer (mc.wants_of).  shared: the map of case 0 passed once, for the whole call."""
+    case = mc.TEAM[name]()
+    out = call(lib, case['grid'][0] if shared else case['grid'], case['starts'], case['goals'], case['T'], case['orders'],
+               ws_bytes=ws_bytes, poison_ws=case['poison_ws'])
+    wants = mc.wants_of(case)
+    mc.assert_outputs_equal(out, wants)
+    return out, wants
+
+
 def test_more_than_128_agents_on_one_word_rows(lib):
-    """129 agents on 20 x 20: an open map where all of them are planned, and one with obstacles where a late agent
-    finds no path (more than 128 agents have been looked at by then or not: both are the yardstick's answer)."""
-    cases = mc.random_cases(np.random.default_rng(40), 1, 129, 20, density=0.0) + \
-        mc.random_cases(np.random.default_rng(41), 1, 129, 20, density=0.1)
-    out, wants = run_and_compare(lib, cases, mc.default_horizon(20, 20), poison_ws=True)
-    assert wants[0]['status'] == 0 and (wants[0]['arrival'] >= 0).all()
-    assert wants[1]['status'] == mc.NO_PATH and wants[1]['failing'] > 64
+    run_case(lib, 'more_than_128_agents_on_one_word_rows')
 
 
 @pytest.mark.parametrize('W', [65, 128, 129])
 def test_random_cases_on_rows_of_several_words(lib, W):
-    rng = np.random.default_rng(100 + W)
-    cases = mc.random_cases(rng, 2, 12, 5, W, density=0.1)
-    out, wants = run_and_compare(lib, cases, 2 * (5 + W), poison_ws=True)
-    assert any(w['status'] == 0 for w in wants)
-    if W >= 128:                                                # (W = 65: one column beyond the boundary; the corridor
-        crossed = False                                         # test below forces the crossing there)
-        for w, (_, s, g) in zip(wants, cases):
-            n = int((w['arrival'] >= 0).sum())                  # the planned agents: some go right, some left
-            crossed |= bool(((s[:n, 1] // 64) < (g[:n, 1] // 64)).any() and ((s[:n, 1] // 64) > (g[:n, 1] // 64)).any())
-        assert crossed
+    run_case(lib, 'random_cases_on_rows_of_several_words_W%d' % W)
 
 
 @pytest.mark.parametrize('W', [65, 128, 129])
 def test_corridor_forces_the_crossing_both_ways(lib, W):
-    """Five rows; the middle one is a wall with two doors, one on each side of the last word boundary b (columns
-    b - 1 and b).  Agent 0 goes from the top left to the bottom right corner, agent 1 from the top right to the bottom
-    left: both must pass the boundary column, in opposite directions, whichever door they take.  For W = 65 and 129
-    column b is the last word's only valid bit."""
-    b = 64 if W < 129 else 128
-    grid = np.zeros((5, W), np.uint8)
-    grid[2, :] = 1
-    grid[2, b - 1:b + 1] = 0
-    starts = np.array([[0, 0], [0, W - 1], [1, 10], [4, 5]])
-    goals = np.array([[4, W - 1], [4, 0], [0, W - 2], [0, 3]])
-    T = 4 * W
-    out = call(lib, grid, starts[None], goals[None], T, poison_ws=True)
-    want = mc.solve_case(grid, starts, goals, T)
-    assert want['status'] == 0
-    assert_matches(out, 0, want)
-    for n, step in ((0, 1), (1, -1)):
-        cols = want['schedule'][:want['arrival'][n] + 1, n, 1]
-        k = int(np.nonzero(cols == (b if step > 0 else b - 1))[0][0])
-        assert cols[k - 1] == cols[k] - step                    # entered the boundary column from the other word
+    run_case(lib, 'corridor_forces_the_crossing_both_ways_W%d' % W)
 
 
 def test_swap_refused_across_the_word_boundary(lib):
-    """Agents in columns 63 and 64 want each other's cell.  The swap over the boundary is no move: on a 2 x 2 block of
-    free cells astride the boundary the second agent goes round (the 2 x 2 case of the one-wave tests, shifted)."""
-    grid = np.ones((2, 66), np.uint8)
-    grid[0:2, 63:65] = 0
-    starts, goals = np.array([[0, 63], [0, 64]]), np.array([[0, 64], [0, 63]])
-    out = call(lib, grid, starts[None], goals[None], 12)
-    want = mc.solve_case(grid, starts, goals, 12)
-    assert_matches(out, 0, want)
-    assert want['status'] == 0 and want['arrival'].tolist() == [1, 3]      # the swap would have taken 1 step
-    # with those two cells alone there is no way round: NO_PATH for agent 1, not a swap
-    grid2 = np.ones((1, 66), np.uint8)
-    grid2[0, 63:65] = 0
-    out = call(lib, grid2, starts[None], goals[None], 12)
-    want = mc.solve_case(grid2, starts, goals, 12)
-    assert_matches(out, 0, want)
-    assert want['status'] == mc.NO_PATH and want['failing'] == 1
+    run_case(lib, 'swap_refused_across_the_word_boundary')
+    run_case(lib, 'no_way_round_on_the_1x66_strip')
 
 
 @pytest.mark.parametrize('H,W', [(65, 6), (70, 9), (66, 65)])
 def test_more_than_one_wave_of_rows(lib, H, W):
     """The vertical exchange across waves: a wall with one door between rows 63 and 64."""
-    grid = np.zeros((H, W), np.uint8)
-    grid[63, :] = 1
-    grid[63, W // 2] = 0
-    starts = np.array([[0, 0], [H - 1, 0], [0, W - 1], [H - 1, W - 1]])
-    goals = np.array([[H - 1, W - 1], [0, W - 1], [H - 1, 0], [1, 1]])
-    T = 2 * (H + W)
-    out = call(lib, grid, starts[None], goals[None], T, poison_ws=True)
-    want = mc.solve_case(grid, starts, goals, T)
-    assert want['status'] == 0
-    assert_matches(out, 0, want)
+    run_case(lib, 'more_than_one_wave_of_rows_%dx%d' % (H, W))
 
 
 def test_random_cases_on_tall_maps(lib):
-    rng = np.random.default_rng(67)
-    run_and_compare(lib, mc.random_cases(rng, 2, 10, 67, 7, density=0.1), 2 * (67 + 7))
+    run_case(lib, 'random_cases_on_tall_maps')
 
 
 def test_several_waves_of_rows_of_several_words(lib):
     """70 x 130: 210 threads in four waves, rows of three words, 140 agents."""
-    cases = mc.random_cases(np.random.default_rng(70130), 1, 140, 70, 130, density=0.1)
-    out, wants = run_and_compare(lib, cases, 200, poison_ws=True)
-    assert (wants[0]['arrival'] >= 0).sum() > 128
+    run_case(lib, 'several_waves_of_rows_of_several_words')
 
 
 def test_given_orders_with_a_failing_restart(lib):
-    rng = np.random.default_rng(21)
-    cases = mc.random_cases(rng, 3, 8, 6, 70, density=0.15)
-    N = 8
-    orders = np.stack([np.stack([np.arange(N)] + [rng.permutation(N) for _ in range(2)]) for _ in cases])
-    orders[1, 2] = orders[1, 0]                                 # a tie: the lower index wins
-    run_and_compare(lib, cases, 160, orders)
-    # the index order fails (agent 0 parks in the corridor agent 1 must cross), the reversed order solves the case
-    grid = np.ones((2, 67), np.uint8)
-    grid[0, 63:66] = 0
-    grid[1, 64] = 0
-    starts, goals = np.array([[1, 64], [0, 63]]), np.array([[0, 64], [0, 65]])
-    orders = np.array([[[0, 1], [1, 0], [1, 0]]])
-    out = call(lib, grid, starts[None], goals[None], 10, orders)
-    want = mc.solve_case(grid, starts, goals, 10, list(orders[0]))
-    assert_matches(out, 0, want)
-    assert mc.plan_order(grid, starts, goals, [0, 1], 10)[0] == mc.NO_PATH
-    assert want['restart'] == 1 and want['status'] == 0 and want['arrival'].tolist() == [2, 2]
+    run_case(lib, 'given_orders_with_a_tie')
+    run_case(lib, 'failing_restart_on_2x67')
 
 
 def test_crowded_cases_solved_and_failing(lib):
-    rng = np.random.default_rng(8)
-    cases = mc.random_cases(rng, 6, 10, 5, 66, density=0.2)
-    out, wants = run_and_compare(lib, cases, 60)
-    assert {w['status'] for w in wants} == {0, mc.NO_PATH}
+    run_case(lib, 'crowded_cases_solved_and_failing')
 
 
 def test_bad_cases_flag_only_themselves(lib):
-    grid = np.zeros((5, 70), np.uint8)
-    grid[2, 66] = 1
-    ok_s, ok_g = np.array([[0, 0], [4, 69], [0, 68]]), np.array([[4, 0], [0, 0], [4, 69]])
-    variants = []
-    for k, v in (('s', [-1, 0]), ('s', [0, 70]), ('g', [5, 1]), ('g', [1, -1]), ('s', [2, 66]), ('g', [2, 66]),
-                 ('s', [4, 69]), ('g', [0, 0]), ('s', [0, 100]), ('g', [3, 127])):
-        s, g = ok_s.copy(), ok_g.copy()
-        (s if k == 's' else g)[0] = v                           # off the map, on the obstacle, a duplicate
-        variants.append((s, g))
-    starts = np.stack([ok_s] + [s for s, _ in variants] + [ok_s, ok_s, ok_s])
-    goals = np.stack([ok_g] + [g for _, g in variants] + [ok_g, ok_g, ok_g])
-    C = len(starts)
-    orders = np.tile(np.array([[0, 1, 2], [2, 1, 0]]), (C, 1, 1))
-    orders[-3, 1] = [0, 0, 2]                                   # not a permutation
-    orders[-2, 0] = [0, 1, 3]                                   # out of range
-    out = call(lib, grid, starts, goals, 160, orders)
-    for c in range(C):
-        want = mc.solve_case(grid, starts[c], goals[c], 160, list(orders[c]))
-        assert_matches(out, c, want)
-        assert (want['status'] == mc.BAD_CASE) == (c not in (0, C - 1)), c
+    out, _ = run_case(lib, 'bad_cases_flag_only_themselves')
     assert out['status'][0] == 0 and out['status'][-1] == 0
 
 
 def test_batched_grid_next_to_shared_grid(lib):
-    rng = np.random.default_rng(34)
-    grid, _, _ = mc.random_cases(rng, 1, 5, 4, 66)[0]
-    cases = []
-    for _ in range(3):
-        free = np.argwhere(grid == 0)
-        idx = rng.choice(len(free), 10, replace=False)
-        cases.append((grid, free[idx[:5]], free[idx[5:]]))
-    shared, _ = run_and_compare(lib, cases, 140, batched=False)
-    batched, _ = run_and_compare(lib, cases, 140, batched=True)
+    shared, _ = run_case(lib, 'batched_grid_next_to_shared_grid', shared=True)
+    batched, _ = run_case(lib, 'batched_grid_next_to_shared_grid')
     assert_same_bytes(shared, batched)
-
-
-def _both(lib, grids, starts, goals, T, orders=None):
-    a = call(lib, grids, starts, goals, T, orders, team=False)
-    b = call(lib, grids, starts, goals, T, orders, team=True, poison_ws=True)
-    assert_same_bytes(a, b)
-    return a
 
 
 def test_same_bytes_as_the_one_wave_call(lib):
     """Every case both entry points accept: all outputs byte-equal (random, crowded with failures, restarts with a bad
-    order, the widest one-word map)."""
-    rng = np.random.default_rng(5)
-    cases = mc.random_cases(rng, 4, 6, 10, density=0.15)
-    _both(lib, np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]), np.stack([c[2] for c in cases]), 40)
-    rng = np.random.default_rng(8)
-    cases = mc.random_cases(rng, 6, 10, 7, density=0.25)
-    out = _both(lib, np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]), np.stack([c[2] for c in cases]), 20)
-    assert set(out['status'].tolist()) == {0, mc.NO_PATH}
-    rng = np.random.default_rng(21)
-    cases = mc.random_cases(rng, 3, 8, 8, density=0.2)
-    orders = np.stack([np.stack([np.arange(8)] + [rng.permutation(8) for _ in range(2)]) for _ in cases])
-    orders[2, 1] = [0, 0, 1, 2, 3, 4, 5, 6]
-    out = _both(lib, np.stack([c[0] for c in cases]), np.stack([c[1] for c in cases]), np.stack([c[2] for c in cases]), 32,
-                orders)
-    assert out['status'][2] == mc.BAD_CASE
-    grid = np.zeros((64, 64), np.uint8)
-    grid[32, 1:63] = 1
-    starts = np.array([[[0, 0], [63, 0], [0, 63]]])
-    goals = np.array([[[63, 63], [0, 63], [63, 0]]])
-    out = _both(lib, grid, starts, goals, 256)
-    assert out['status'][0] == 0
-    cases = mc.random_cases(np.random.default_rng(77), 1, 128, 16, density=0.05)
-    _both(lib, cases[0][0], cases[0][1][None], cases[0][2][None], 64)
+    order, the widest one-word map, 128 agents)."""
+    for name in ('random_10x10', 'crowded_with_failures', 'restarts_with_a_bad_order', 'widest_one_word_map',
+                 '128_agents_on_16x16'):
+        case = mc.BOTH[name]()
+        args = (lib, case['grid'], case['starts'], case['goals'], case['T'], case['orders'])
+        a = call(*args, team=False)
+        b = call(*args, team=True, poison_ws=True)
+        assert_same_bytes(a, b)
+        mc.assert_outputs_equal(a, mc.wants_of(case))
 
 
 def test_outputs_do_not_depend_on_the_slot_count(lib):
-    rng = np.random.default_rng(55)
-    cases = mc.random_cases(rng, 5, 6, 4, 66, density=0.15)
-    N = 6
-    orders = np.stack([np.stack([np.arange(N), rng.permutation(N)]) for _ in cases])
-    grids, starts, goals = (np.stack([c[k] for c in cases]) for k in range(3))
-    full = call(lib, grids, starts, goals, 60, orders, poison_ws=True)
+    name = 'outputs_do_not_depend_on_the_slot_count'
+    full, _ = run_case(lib, name)
     one = one_slot_bytes(lib, 5, 2, 4, 66, 60)
     assert one < lib.gnnpp_mapf_team_workspace_bytes(5, 2, 4, 66, 60)
-    single = call(lib, grids, starts, goals, 60, orders, ws_bytes=one, poison_ws=True)
-    three = call(lib, grids, starts, goals, 60, orders, ws_bytes=one + 2 * (61 * 6 * 4 * 2 * 8) + 100, poison_ws=True)
+    single, _ = run_case(lib, name, ws_bytes=one)
+    three, _ = run_case(lib, name, ws_bytes=one + 2 * (61 * 6 * 4 * 2 * 8) + 100)
     assert_same_bytes(full, single)
     assert_same_bytes(full, three)
-    for c, (g, s, gl) in enumerate(cases):
-        assert_matches(single, c, mc.solve_case(g, s, gl, 60, list(orders[c])))
 
 
 def test_zero_horizon_and_single_agent(lib):
-    grid = np.zeros((2, 65), np.uint8)
-    s, g = np.array([[[0, 64]]]), np.array([[[0, 64]]])
-    out = call(lib, grid, s, g, 0)
-    assert_matches(out, 0, mc.solve_case(grid, s[0], g[0], 0))
+    out, _ = run_case(lib, 'zero_horizon_agent_on_its_goal')
     assert out['status'][0] == 0 and out['arrival'][0, 0] == 0
-    g2 = np.array([[[1, 64]]])
-    out = call(lib, grid, s, g2, 0)
-    assert_matches(out, 0, mc.solve_case(grid, s[0], g2[0], 0))
+    out, _ = run_case(lib, 'zero_horizon_agent_off_its_goal')
     assert out['status'][0] == mc.NO_PATH
 
 

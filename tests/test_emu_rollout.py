@@ -127,55 +127,58 @@ def test_emu_rollout_argument_checks():
     assert lib.gnnpp_rollout_move(ctypes.byref(r), None) == -1
 
 
+def run_move_case(lib, case):
+    """A case of tests/rollout_cases.py through the emulated move kernel, lowest-index tie-break: flags, positions,
+    reached, start and end steps and tie-break counts of every episode after every step equal the oracle's trace (for a
+    `loop` case also done, and at the end the statistics)."""
+    from gnn_pathplanning_amd._native import RolloutStruct
+    import rollout_cases as rc
+    trace = rc.oracle_trace(case)
+    T, B, N = case['actions'].shape
+    grids, goals, limits = case['grids'], case['goals'], case['maxstep']
+    pos = np.ascontiguousarray(case['starts'].copy())
+    reached = np.zeros((B, N), np.int32)
+    start = np.full((B, N), -1, np.int32); end = np.full((B, N), -1, np.int32)
+    flags = np.zeros((B, 3), np.int32); stats = np.zeros((B, 2), np.int32)
+    done = np.zeros(B, np.int32)
+    ccount = np.zeros(B, np.int32)
+    r = RolloutStruct()
+    r.grid, r.grid_batched, r.goal, r.pos = grids.ctypes.data, 1, goals.ctypes.data, pos.ctypes.data
+    r.B, r.N, r.H, r.W = B, N, grids.shape[1], grids.shape[2]
+    r.reached, r.start_step, r.end_step = reached.ctypes.data, start.ctypes.data, end.ctypes.data
+    r.maxstep, r.flags, r.stats = limits.ctypes.data, flags.ctypes.data, stats.ctypes.data
+    if case['loop']:
+        r.done = done.ctypes.data
+    r.tie_mode, r.choice_count = 0, ccount.ctypes.data
+    for t in range(T):
+        acts = np.ascontiguousarray(case['actions'][t])
+        r.logits, r.actions, r.currentstep = None, acts.ctypes.data, t + 1
+        assert lib.gnnpp_rollout_move(ctypes.byref(r), None) == 0
+        for b in range(B):
+            assert list(trace['flags'][t, b]) == list(flags[b]), (case['name'], t, b)
+            assert (pos[b] == trace['pos'][t, b]).all(), (case['name'], t, b)
+            assert (reached[b] == trace['reached'][t, b]).all(), (case['name'], t, b)
+            assert ccount[b] == trace['calls'][t, b], (case['name'], t, b)
+            assert (start[b] == trace['start_step'][t, b]).all(), (case['name'], t, b)
+            assert (end[b] == trace['end_step'][t, b]).all(), (case['name'], t, b)
+            if case['loop']:
+                assert bool(done[b]) == trace['done'][t, b], (case['name'], t, b)
+    if case['loop']:
+        assert (done == 1).all() and trace['done'][-1].all()
+        assert np.array_equal(stats, trace['stats']) and np.array_equal(reached, trace['reached'][-1])
+        assert np.array_equal(end, trace['end_step'][-1]) and np.array_equal(start, trace['start_step'][-1])
+    return trace, stats
+
+
 def test_emu_mixed_maxstep_freezes_finished_episodes():
     """Batch with different per-episode limits through the emulated move kernel vs the oracle's case
     loop (oracle.rollout_oracle.loop_step): an episode past its own maxstep, or whose loop broke
     after allReachGoal, is left untouched (success/makespan were inflated)."""
     import emu_lib
-    from gnn_pathplanning_amd._native import RolloutStruct
-    from oracle import rollout_oracle as ro
-    lib = emu_lib.load()
-    rng = np.random.default_rng(3)
-    B, N, W = 6, 5, 7
-    grids = (rng.random((B, W, W)) < 0.05).astype(np.uint8)
-    starts = np.zeros((B, N, 2), np.int32); goals = np.zeros((B, N, 2), np.int32)
-    for b in range(B):
-        free = np.argwhere(grids[b] == 0)
-        pick = rng.choice(len(free), 2 * N, replace=False)
-        starts[b], goals[b] = free[pick[:N]], free[pick[N:]]
-    grids[0] = 0                              # episode 0: every agent one step (action 3) from its goal
-    starts[0] = [[i, 0] for i in range(N)]
-    goals[0] = [[i, 1] for i in range(N)]
-    limits = np.array([6, 2, 3, 8, 1, 5], np.int32)
-    pos = np.ascontiguousarray(starts.copy())
-    reached = np.zeros((B, N), np.int32)
-    start = np.full((B, N), -1, np.int32); end = np.full((B, N), -1, np.int32)
-    flags = np.zeros((B, 3), np.int32); stats = np.zeros((B, 2), np.int32)
-    done = np.zeros(B, np.int32)
-    r = RolloutStruct()
-    r.grid, r.grid_batched, r.goal, r.pos = grids.ctypes.data, 1, goals.ctypes.data, pos.ctypes.data
-    r.B, r.N, r.H, r.W = B, N, W, W
-    r.reached, r.start_step, r.end_step = reached.ctypes.data, start.ctypes.data, end.ctypes.data
-    r.maxstep, r.flags, r.stats, r.done = limits.ctypes.data, flags.ctypes.data, stats.ctypes.data, done.ctypes.data
-    r.tie_mode = 0
-    eps = [ro.EpisodeState(grids[b], goals[b], starts[b], limits[b]) for b in range(B)]
-    for t in range(10):
-        acts = np.ascontiguousarray(rng.integers(0, 5, size=(B, N)).astype(np.int32))
-        if t == 0:
-            acts[0] = 3                        # all arrive at call 1; call 2 sees allReachGoal and ends the loop
-        r.logits, r.actions, r.currentstep = None, acts.ctypes.data, t + 1
-        assert lib.gnnpp_rollout_move(ctypes.byref(r), None) == 0
-        for b in range(B):
-            f = ro.loop_step(eps[b], acts[b], t + 1, lambda c: c[0])
-            assert [int(v) for v in f] == list(flags[b]), (t, b)
-            assert (pos[b] == eps[b].cur).all(), (t, b)
-            assert bool(done[b]) == eps[b].done, (t, b)
-    for b in range(B):
-        assert eps[b].done and done[b] == 1
-        assert list(stats[b]) == [eps[b].makespan, eps[b].flowtime], b
-        assert list(reached[b]) == [int(v) for v in eps[b].reached]
-        assert list(end[b]) == eps[b].end_step
-    assert list(stats[0]) == [1, N] and limits[0] == 6   # ended by allReachGoal, long before its maxstep
+    import rollout_cases as rc
+    case = rc.mixed_maxstep_case()
+    _, stats = run_move_case(emu_lib.load(), case)
+    assert list(stats[0]) == [1, 5] and case['maxstep'][0] == 6   # ended by allReachGoal, long before its maxstep
 
 
 def test_emu_move_dense_conflicts_vs_oracle():
@@ -183,56 +186,13 @@ def test_emu_move_dense_conflicts_vs_oracle():
     swaps per step.  The kernel's candidate-driven collision passes must reproduce the oracle's
     agent-by-agent loops exactly (positions, flags, tie-break counts), lowest-index tie-break."""
     import emu_lib
-    from gnn_pathplanning_amd._native import RolloutStruct
-    from oracle import rollout_oracle as ro
+    import rollout_cases as rc
     lib = emu_lib.load()
-    rng = np.random.default_rng(21)
-    # (the last case: a map of more than 32 768 cells has no LDS cell-count map -- the collision candidates come
-    # from the all-pairs scan; its agents start in one 5 x 5 corner so that they still collide)
-    for (B, N, W) in ((24, 9, 4), (12, 14, 5), (6, 70, 10), (3, 14, 182)):
-        grids = (rng.random((B, W, W)) < 0.04).astype(np.uint8)
-        starts = np.zeros((B, N, 2), np.int32); goals = np.zeros((B, N, 2), np.int32)
-        for b in range(B):
-            if W > 100:
-                grids[b, :5, :5] = 0
-            free = np.argwhere(grids[b] == 0)
-            if W > 100:
-                free = free[(free[:, 0] < 5) & (free[:, 1] < 5)]
-            while len(free) < N:
-                grids[b] = 0
-                free = np.argwhere(grids[b] == 0)
-            starts[b] = free[rng.choice(len(free), N, replace=False)]
-            goals[b] = free[rng.choice(len(free), N, replace=False)]
-        pos = np.ascontiguousarray(starts.copy())
-        reached = np.zeros((B, N), np.int32)
-        start = np.full((B, N), -1, np.int32); end = np.full((B, N), -1, np.int32)
-        flags = np.zeros((B, 3), np.int32); stats = np.zeros((B, 2), np.int32)
-        ccount = np.zeros(B, np.int32)
-        limits = np.full(B, 50, np.int32)
-        r = RolloutStruct()
-        r.grid, r.grid_batched, r.goal, r.pos = grids.ctypes.data, 1, goals.ctypes.data, pos.ctypes.data
-        r.B, r.N, r.H, r.W = B, N, W, W
-        r.reached, r.start_step, r.end_step = reached.ctypes.data, start.ctypes.data, end.ctypes.data
-        r.maxstep, r.flags, r.stats = limits.ctypes.data, flags.ctypes.data, stats.ctypes.data
-        r.tie_mode, r.choice_count = 0, ccount.ctypes.data
-        eps = [ro.EpisodeState(grids[b], goals[b], starts[b], 50) for b in range(B)]
-        collisions = 0
-        for t in range(6):
-            acts = np.ascontiguousarray(rng.integers(0, 5, size=(B, N)).astype(np.int32))
-            r.logits, r.actions, r.currentstep = None, acts.ctypes.data, t + 1
-            assert lib.gnnpp_rollout_move(ctypes.byref(r), None) == 0
-            for b in range(B):
-                calls = [0]
-
-                def lowest(c, calls=calls):
-                    calls[0] += 1
-                    return c[0]
-                f = ro.move_step(eps[b], acts[b], t + 1, lowest)
-                assert [int(v) for v in f] == list(flags[b]), (N, t, b)
-                assert (pos[b] == eps[b].cur).all(), (N, t, b)
-                assert ccount[b] == calls[0], (N, t, b)
-                collisions += calls[0]
-        assert collisions > 20 * B // 6
+    assert [c['actions'].shape[1:] + c['grids'].shape[2:] for c in rc.dense_conflict_cases()] == \
+        [(24, 9, 4), (12, 14, 5), (6, 70, 10), (3, 14, 182)]
+    for case in rc.dense_conflict_cases():
+        trace, _ = run_move_case(lib, case)
+        assert trace['calls'].sum() > 20 * len(case['starts']) // 6
 
 
 def test_emu_mt19937_tie_break_is_random_choice():

@@ -116,39 +116,24 @@ def test_emu_team_random_actions_vs_oracle(N):
     assert collisions > 10
 
 
-def test_emu_team_dense_corridors_vs_oracle(monkeypatch):
+def test_emu_team_dense_corridors_vs_oracle():
     """Agents packed head to tail in corridors, mostly pushing forward: the fall-backs chain through many repeat
     passes of the collision check and the all-stop branch fires; positions, flags and tie-break counts match."""
     import emu_lib
-    from oracle import rollout_oracle as ro
-    from rollout_team_cases import Recorder, corridor_instance
-    lib = emu_lib.load()
-    passes = [0]
-    orig = ro._inter_robot_collision
+    import rollout_cases as rc
+    from test_emu_rollout import run_move_case
+    trace, _ = run_move_case(emu_lib.load(), rc.team_corridor_case())
+    assert trace['all_stop'] > 0 and trace['most_passes'] >= 4, (trace['all_stop'], trace['most_passes'])
 
-    def counted(ep, choose):
-        passes[0] += 1
-        return orig(ep, choose)
-    monkeypatch.setattr(ro, '_inter_robot_collision', counted)
-    B, N, H, W = 2, 200, 24, 36
-    grids, starts, goals = corridor_instance(B, N, H, W)
-    env = Episodes(grids, starts, goals, 50)
-    eps = [ro.EpisodeState(grids[b], goals[b], starts[b], 50) for b in range(B)]
-    rng = np.random.default_rng(5)
-    all_stop = most_passes = 0
-    for t in range(4):
-        acts = np.where(rng.random((B, N)) < 0.8, 3, rng.integers(0, 5, size=(B, N)))
-        env.move(lib, acts, t + 1)
-        for b in range(B):
-            rec = Recorder(eps[b], lambda c: c[0])
-            passes[0] = 0
-            f = ro.move_step(eps[b], acts[b], t + 1, rec)
-            most_passes = max(most_passes, passes[0])
-            assert [int(v) for v in f] == list(env.flags[b]), (t, b)
-            assert (env.pos[b] == eps[b].cur).all(), (t, b)
-            assert env.ccount[b] == rec.calls, (t, b)
-            all_stop += rec.all_stop
-    assert all_stop > 0 and most_passes >= 4, (all_stop, most_passes)
+
+def test_emu_team_dense_conflicts_vs_oracle():
+    """129 agents on 16 x 16, random joint actions: the dense-conflict case of the one-wave kernels at the smallest team
+    the large-team kernels take."""
+    import emu_lib
+    import rollout_cases as rc
+    from test_emu_rollout import run_move_case
+    trace, _ = run_move_case(emu_lib.load(), rc.team_dense_conflict_case())
+    assert trace['calls'].sum() > rc.TEAM_DENSE_FLOOR
 
 
 def test_emu_team_mt19937_is_random_choice():
@@ -183,33 +168,10 @@ def test_emu_team_mixed_maxstep_freezes_finished_episodes():
     """Per-episode limits at N = 160: an episode past its own maxstep, or whose loop broke after allReachGoal,
     is frozen; statistics as the oracle's case loop reports them."""
     import emu_lib
-    from oracle import rollout_oracle as ro
-    from rollout_team_cases import make_instances
-    lib = emu_lib.load()
-    rng = np.random.default_rng(4)
-    B, N, W = 3, 160, 32
-    grids, starts, goals = make_instances(rng, B, N, W, W, 0.04)
-    grids[0] = 0                                        # episode 0: every agent one step (action 3) from its goal
-    starts[0] = [[i // 16, 2 * (i % 16)] for i in range(N)]
-    goals[0] = starts[0] + [0, 1]
-    limits = np.array([5, 2, 3], np.int32)
-    env = Episodes(grids, starts, goals, limits)
-    eps = [ro.EpisodeState(grids[b], goals[b], starts[b], limits[b]) for b in range(B)]
-    for t in range(6):
-        acts = rng.integers(0, 5, size=(B, N))
-        if t == 0:
-            acts[0] = 3
-        env.move(lib, acts, t + 1)
-        for b in range(B):
-            f = ro.loop_step(eps[b], acts[b], t + 1, lambda c: c[0])
-            assert [int(v) for v in f] == list(env.flags[b]), (t, b)
-            assert (env.pos[b] == eps[b].cur).all(), (t, b)
-            assert bool(env.done[b]) == eps[b].done, (t, b)
-    for b in range(B):
-        assert eps[b].done and env.done[b] == 1
-        assert list(env.stats[b]) == [eps[b].makespan, eps[b].flowtime], b
-        assert list(env.end[b]) == eps[b].end_step
-    assert list(env.stats[0]) == [1, N]
+    import rollout_cases as rc
+    from test_emu_rollout import run_move_case
+    _, stats = run_move_case(emu_lib.load(), rc.team_mixed_maxstep_case())
+    assert list(stats[0]) == [1, 160]
 
 
 def test_emu_team_argument_checks():
