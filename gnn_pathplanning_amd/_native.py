@@ -29,30 +29,33 @@ HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
-EXPORTS = ('gnnpp_version', 'gnnpp_error_string', 'gnnpp_set_tuning', 'gnnpp_get_tuning', 'gnnpp_filter_packed_floats',
-           'gnnpp_filter_pack', 'gnnpp_lsigf_fwd', 'gnnpp_lsigf_fwd_save', 'gnnpp_lsigf_fits', 'gnnpp_encoder_packed_floats',
-           'gnnpp_encoder_pack', 'gnnpp_encoder_fwd', 'gnnpp_encoder_train_workspace_floats', 'gnnpp_encoder_train_fwd',
-           'gnnpp_encoder_train_bwd', 'gnnpp_gemm_workspace_floats', 'gnnpp_gemm_kmajor', 'gnnpp_gemm_multi_workspace_floats',
-           'gnnpp_gemm_kmajor_multi', 'gnnpp_policy_loss',
-           'gnnpp_filter_head_mode', 'gnnpp_train_pack_floats', 'gnnpp_train_pack', 'gnnpp_lsigf_input_grad', 'gnnpp_linear_fwd',
-           'gnnpp_adam_step', 'gnnpp_policy_fwd', 'gnnpp_filter_head_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
-           'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe', 'gnnpp_rollout_step', 'gnnpp_rollout_policy_step',
-           'gnnpp_rollout_policy_steps', 'gnnpp_schedule_samples', 'gnnpp_mapf_workspace_bytes', 'gnnpp_mapf_solve',
-           'gnnpp_mapf_team_workspace_bytes', 'gnnpp_mapf_team_solve', 'gnnpp_schedule_team_workspace_bytes',
-           'gnnpp_schedule_team_samples', 'gnnpp_lsigf_team_workspace_bytes', 'gnnpp_lsigf_team_fwd',
-           'gnnpp_filter_head_team_fwd', 'gnnpp_policy_team_fwd', 'gnnpp_team_lists_bytes',
-           'gnnpp_team_lists_from_dense', 'gnnpp_rollout_lists', 'gnnpp_lsigf_team_lists_fwd',
-           'gnnpp_filter_head_team_lists_fwd', 'gnnpp_policy_team_lists_fwd', 'gnnpp_team_lists_transpose',
-           'gnnpp_lsigf_team_lists_fwd_save', 'gnnpp_lsigf_team_lists_input_grad', 'gnnpp_schedule_team_plan',
-           'gnnpp_schedule_team_fill_lists', 'gnnpp_team_lists_gather')
-
 
 class GnnppError(RuntimeError):
     pass
 
 
-# include/gnnpp.h GNNPP_PREC_*: the arithmetic of a call's matrix-pipe contractions, passed PER CALL
+# ---- the C ABI of include/gnnpp.h, stated once for Python --------------------------------------------------------
+# Every `#define GNNPP_<NAME> <integer>` of the header under its name without the prefix, every struct as a
+# ctypes.Structure and every prototype as an entry of SIGNATURES.  This is the ONLY Python statement of the contract (the
+# package, the tools' measure library and the tests' host build of the same sources all bind through bind() below), and
+# tests/test_host_logic.py::test_python_abi_matches_header holds all three to the header.
+OK, ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH, ERR_RANGE = 0, -1, -2, -3, -4
+# GNNPP_PREC_*: the arithmetic of a call's matrix-pipe contractions, passed PER CALL
 PREC_FP32, PREC_FP32_MFMA, PREC_SPLIT_F16 = 0, 1, 2
+OBS_C, OBS_HW, FEAT, ACTIONS = 3, 11, 128, 5
+MAX_NODES, MAX_ROWS = 100, 112
+# GNNPP_TUNE_*: keys of gnnpp_set_tuning / gnnpp_get_tuning
+TUNE_FILTER_GPW, TUNE_FILTER_WAVES, TUNE_FUSED_POLICY, TUNE_FILTER_SPLIT, TUNE_POLICY_FILTER = 1, 2, 6, 7, 9
+TUNE_FILTER_SMALL, TUNE_FILTER_SMALL_ROWS, TUNE_FILTER_PIPE_GRID = 10, 11, 12
+TUNE_POLICY_CP, TUNE_ENCODER_CP_TILE, TUNE_TRAIN_FORK, TUNE_FILTER_PLANE_ALIAS = 13, 14, 15, 16
+TUNE_TRAIN_WGRAD_WGS, TUNE_TRAIN_WGRAD_MERGED, TUNE_TRAIN_RUNNING_FUSED, TUNE_ENCODER_ONE_PLANE = 17, 18, 19, 20
+ROLLOUT_MAX_AGENTS, ROLLOUT_MAX_TEAM, ROLLOUT_TEAM_MAX_CELLS = 128, 1024, 65536
+TIE_LOWEST, TIE_HASHED, TIE_REPLAY, TIE_MT19937 = 0, 1, 2, 3
+SCHEDULE_BAD_MOVE, SCHEDULE_BAD_STATE, SCHEDULE_NO_RADIUS = 1, 2, 4
+MAPF_NO_PATH, MAPF_BAD_CASE = 1, 2
+MAPF_MAX_SIDE, MAPF_MAX_STEPS, MAPF_TEAM_MAX_SIDE, MAPF_TEAM_MAX_STEPS = 64, 1024, 256, 2048
+# csrc/gnnpp_measure.h: keys that exist in the -DGNNPP_MEASURE build only (libgnnpp.so answers GNNPP_ERR_ARG)
+TUNE_FILTER_ABLATE, TUNE_ENCODER_STOP = 3, 4
 PRECISIONS = {'fp32': PREC_FP32, 'fp32_mfma': PREC_FP32_MFMA, 'split_f16': PREC_SPLIT_F16}
 
 
@@ -65,7 +68,7 @@ def precision_code(p):
         p = PRECISIONS[p]
     else:
         p = int(p)
-        if p not in (0, 1, 2):
+        if p not in (PREC_FP32, PREC_FP32_MFMA, PREC_SPLIT_F16):
             raise GnnppError('unknown precision code %d' % p)
     if p == PREC_SPLIT_F16 and os.path.exists(H2_UNSAFE_MARK):
         raise GnnppError("precision 'split_f16' is disabled in this build: the ISA hipcc generated for the opt-in "
@@ -229,126 +232,89 @@ class MapfStruct(ctypes.Structure):
                 ('restart', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
 
 
+_vp, _ci, _cs, _ll, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_float
+_enc, _rollout = ctypes.POINTER(EncoderParams), ctypes.POINTER(RolloutStruct)
+_sched, _mapf, _gemm = ctypes.POINTER(ScheduleStruct), ctypes.POINTER(MapfStruct), ctypes.POINTER(GemmDesc)
+
+# name -> (restype, argtypes) of every exported call, in the header's order
+SIGNATURES = {
+    'gnnpp_version': (_ci, []),
+    'gnnpp_error_string': (ctypes.c_char_p, [_ci]),
+    'gnnpp_set_tuning': (_ci, [_ci, _ci]),
+    'gnnpp_get_tuning': (_ci, [_ci]),
+    'gnnpp_filter_packed_floats': (_cs, [_ci] * 4),
+    'gnnpp_filter_pack': (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    'gnnpp_lsigf_fwd': (_ci, [_vp] * 5 + [_ci] * 14 + [_vp, _vp]),
+    'gnnpp_lsigf_fwd_save': (_ci, [_vp] * 6 + [_ci] * 15 + [_vp, _vp]),
+    'gnnpp_lsigf_fits': (_ci, [_ci] * 5),
+    'gnnpp_encoder_packed_floats': (_cs, []),
+    'gnnpp_encoder_pack': (_ci, [_enc, _vp, _vp]),
+    'gnnpp_encoder_fwd': (_ci, [_vp, _vp, _vp, _ci, _ci, _vp, _vp]),
+    'gnnpp_encoder_train_workspace_floats': (_cs, [_ci, _ci]),
+    'gnnpp_encoder_train_fwd': (_ci, [_enc, _vp, _vp, _vp, _ci, _ci, _cf, _ci, ctypes.POINTER(_vp), _ci, _vp, _vp]),
+    'gnnpp_encoder_train_bwd': (_ci, [_enc, _vp, _vp, _vp, ctypes.POINTER(EncoderGrads), _ci, _ci, _ci, _vp, _vp]),
+    'gnnpp_train_pack_floats': (_cs, []),
+    'gnnpp_train_pack': (_ci, [_enc, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    'gnnpp_lsigf_input_grad': (_ci, [_vp] * 5 + [_ci] * 9 + [_vp]),
+    'gnnpp_linear_fwd': (_ci, [_vp] * 4 + [_ci] * 4 + [_vp]),
+    'gnnpp_gemm_workspace_floats': (_cs, [_ci] * 4),
+    'gnnpp_gemm_kmajor': (_ci, [_vp, _ll, _ll, _ll, _vp, _ll, _ll, _vp, _ll, _ll, _ci, _ci, _ci, _ci, _vp, _vp]),
+    'gnnpp_gemm_multi_workspace_floats': (_cs, [_gemm, _ci]),
+    'gnnpp_gemm_kmajor_multi': (_ci, [_gemm, _ci, _vp, _vp]),
+    'gnnpp_policy_loss': (_ci, [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp]),
+    'gnnpp_adam_step': (_ci, [ctypes.POINTER(AdamTensors), _vp, _cf, _cf, _cf, _cf, _cf, _ci, _vp]),
+    'gnnpp_policy_fwd': (_ci, [_vp] * 9 + [_ci] * 6 + [_vp, _vp]),
+    'gnnpp_filter_head_fwd': (_ci, [_vp] * 7 + [_ci] * 8 + [_vp, _vp]),
+    'gnnpp_filter_head_mode': (_ci, [_ci] * 4),
+    'gnnpp_decode_actions': (_ci, [_vp, _vp, _ci, _ci, _vp]),
+    'gnnpp_lsigf_team_workspace_bytes': (_cs, [_ci] * 6),
+    'gnnpp_lsigf_team_fwd': (_ci, [_vp] * 6 + [_cs] + [_ci] * 11 + [_vp]),
+    'gnnpp_filter_head_team_fwd': (_ci, [_vp] * 8 + [_cs] + [_ci] * 8 + [_vp]),
+    'gnnpp_policy_team_fwd': (_ci, [_vp] * 9 + [_ci] * 6 + [_vp, _vp, _vp, _cs]),
+    'gnnpp_team_lists_bytes': (_cs, [_ci, _ci]),
+    'gnnpp_team_lists_from_dense': (_ci, [_vp, _vp, _cs, _ci, _ci, _ci, _vp]),
+    'gnnpp_lsigf_team_lists_fwd': (_ci, [_vp] * 6 + [_cs] + [_ci] * 10 + [_vp]),
+    'gnnpp_filter_head_team_lists_fwd': (_ci, [_vp] * 8 + [_cs] + [_ci] * 7 + [_vp]),
+    'gnnpp_policy_team_lists_fwd': (_ci, [_vp] * 9 + [_ci] * 5 + [_vp, _vp, _vp, _cs]),
+    'gnnpp_team_lists_transpose': (_ci, [_vp, _vp, _cs, _ci, _ci, _vp]),
+    'gnnpp_lsigf_team_lists_fwd_save': (_ci, [_vp] * 7 + [_cs] + [_ci] * 10 + [_vp]),
+    'gnnpp_lsigf_team_lists_input_grad': (_ci, [_vp] * 5 + [_cs] + [_ci] * 7 + [_vp]),
+    'gnnpp_rollout_observe': (_ci, [_rollout, _vp]),
+    'gnnpp_rollout_gso': (_ci, [_rollout, _vp]),
+    'gnnpp_rollout_move': (_ci, [_rollout, _vp]),
+    'gnnpp_rollout_gso_observe': (_ci, [_rollout, _vp]),
+    'gnnpp_rollout_lists': (_ci, [_rollout, _vp, _cs, _vp]),
+    'gnnpp_rollout_step': (_ci, [_rollout, _vp]),
+    'gnnpp_rollout_policy_step': (_ci, [_rollout] + [_vp] * 5 + [_ci, _ci, _vp]),
+    'gnnpp_rollout_policy_steps': (_ci, [_rollout] + [_vp] * 5 + [_ci, _ci, _ci, _vp]),
+    'gnnpp_schedule_samples': (_ci, [_sched, _vp]),
+    'gnnpp_schedule_team_workspace_bytes': (_cs, [_ci, _ci]),
+    'gnnpp_schedule_team_samples': (_ci, [_sched, _vp, _cs, _vp]),
+    'gnnpp_schedule_team_plan': (_ci, [_sched, _vp, _cs, _vp, _vp]),
+    'gnnpp_schedule_team_fill_lists': (_ci, [_sched, _vp, _cs, _vp, _vp, _vp, _ci, _vp]),
+    'gnnpp_team_lists_gather': (_ci, [_vp, _vp, _vp, _ci, _ci, _vp, _ci, _vp, _cs, _ci, _vp]),
+    'gnnpp_mapf_workspace_bytes': (_cs, [_ci] * 4),
+    'gnnpp_mapf_solve': (_ci, [_mapf, _vp]),
+    'gnnpp_mapf_team_workspace_bytes': (_cs, [_ci] * 5),
+    'gnnpp_mapf_team_solve': (_ci, [_mapf, _vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+# csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
+MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
+
+
+def bind(library):
+    """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
+    build) its prototype from SIGNATURES; returns the library."""
+    optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + optional:
+        f = getattr(library, name)                           # (a missing export raises here, at load time)
+        f.restype, f.argtypes = restype, argtypes
+    return library
+
+
 _lib = None
 _measure_lib = None
-
-
-def _bind(path):
-    L = ctypes.CDLL(path)
-    vp, ci, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    L.gnnpp_version.restype = ci
-    L.gnnpp_error_string.restype = ctypes.c_char_p
-    L.gnnpp_error_string.argtypes = [ci]
-    L.gnnpp_set_tuning.argtypes = [ci, ci]
-    L.gnnpp_set_tuning.restype = ci
-    L.gnnpp_get_tuning.argtypes = [ci]
-    L.gnnpp_get_tuning.restype = ci
-    L.gnnpp_filter_packed_floats.restype = cs
-    L.gnnpp_filter_packed_floats.argtypes = [ci] * 4
-    L.gnnpp_filter_pack.argtypes = [vp, vp, ci, ci, ci, ci, vp]
-    L.gnnpp_lsigf_fwd.argtypes = [vp] * 5 + [ci] * 14 + [vp, vp]
-    L.gnnpp_lsigf_fwd_save.argtypes = [vp] * 6 + [ci] * 15 + [vp, vp]
-    L.gnnpp_lsigf_fwd_save.restype = ci
-    L.gnnpp_lsigf_fits.argtypes = [ci] * 5
-    L.gnnpp_lsigf_fits.restype = ci
-    L.gnnpp_encoder_packed_floats.restype = cs
-    L.gnnpp_encoder_packed_floats.argtypes = []
-    L.gnnpp_encoder_pack.argtypes = [ctypes.POINTER(EncoderParams), vp, vp]
-    L.gnnpp_encoder_fwd.argtypes = [vp, vp, vp, ci, ci, vp, vp]
-    L.gnnpp_encoder_train_workspace_floats.restype = cs
-    L.gnnpp_encoder_train_workspace_floats.argtypes = [ci, ci]
-    L.gnnpp_encoder_train_fwd.argtypes = [ctypes.POINTER(EncoderParams), vp, vp, vp, ci, ci, ctypes.c_float, ci,
-                                          ctypes.POINTER(ctypes.c_void_p), ci, vp, vp]
-    L.gnnpp_encoder_train_fwd.restype = ci
-    L.gnnpp_encoder_train_bwd.argtypes = [ctypes.POINTER(EncoderParams), vp, vp, vp, ctypes.POINTER(EncoderGrads),
-                                          ci, ci, ci, vp, vp]
-    L.gnnpp_train_pack_floats.restype = cs
-    L.gnnpp_train_pack_floats.argtypes = []
-    L.gnnpp_train_pack.argtypes = [ctypes.POINTER(EncoderParams), vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    L.gnnpp_train_pack.restype = ci
-    L.gnnpp_lsigf_input_grad.argtypes = [vp] * 5 + [ci] * 9 + [vp]
-    L.gnnpp_lsigf_input_grad.restype = ci
-    L.gnnpp_linear_fwd.argtypes = [vp] * 4 + [ci] * 4 + [vp]
-    L.gnnpp_linear_fwd.restype = ci
-    L.gnnpp_encoder_train_bwd.restype = ci
-    ll, cf = ctypes.c_longlong, ctypes.c_float
-    L.gnnpp_gemm_workspace_floats.restype = cs
-    L.gnnpp_gemm_workspace_floats.argtypes = [ci] * 4
-    L.gnnpp_gemm_kmajor.argtypes = [vp, ll, ll, ll, vp, ll, ll, vp, ll, ll, ci, ci, ci, ci, vp, vp]
-    L.gnnpp_gemm_kmajor.restype = ci
-    L.gnnpp_gemm_multi_workspace_floats.restype = cs
-    L.gnnpp_gemm_multi_workspace_floats.argtypes = [ctypes.POINTER(GemmDesc), ci]
-    L.gnnpp_gemm_kmajor_multi.argtypes = [ctypes.POINTER(GemmDesc), ci, vp, vp]
-    L.gnnpp_gemm_kmajor_multi.restype = ci
-    L.gnnpp_policy_loss.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    L.gnnpp_policy_loss.restype = ci
-    L.gnnpp_adam_step.argtypes = [ctypes.POINTER(AdamTensors), vp, cf, cf, cf, cf, cf, ci, vp]
-    L.gnnpp_adam_step.restype = ci
-    L.gnnpp_policy_fwd.argtypes = [vp] * 9 + [ci] * 6 + [vp, vp]
-    L.gnnpp_filter_head_fwd.argtypes = [vp] * 7 + [ci] * 8 + [vp, vp]
-    L.gnnpp_filter_head_fwd.restype = ci
-    L.gnnpp_decode_actions.argtypes = [vp, vp, ci, ci, vp]
-    L.gnnpp_lsigf_team_workspace_bytes.argtypes = [ci] * 6
-    L.gnnpp_lsigf_team_workspace_bytes.restype = cs
-    L.gnnpp_lsigf_team_fwd.argtypes = [vp] * 6 + [cs] + [ci] * 11 + [vp]
-    L.gnnpp_lsigf_team_fwd.restype = ci
-    L.gnnpp_filter_head_team_fwd.argtypes = [vp] * 8 + [cs] + [ci] * 8 + [vp]
-    L.gnnpp_filter_head_team_fwd.restype = ci
-    L.gnnpp_policy_team_fwd.argtypes = [vp] * 9 + [ci] * 6 + [vp, vp, vp, cs]
-    L.gnnpp_policy_team_fwd.restype = ci
-    L.gnnpp_team_lists_bytes.argtypes = [ci, ci]
-    L.gnnpp_team_lists_bytes.restype = cs
-    L.gnnpp_team_lists_from_dense.argtypes = [vp, vp, cs, ci, ci, ci, vp]
-    L.gnnpp_team_lists_from_dense.restype = ci
-    L.gnnpp_rollout_lists.argtypes = [ctypes.POINTER(RolloutStruct), vp, cs, vp]
-    L.gnnpp_rollout_lists.restype = ci
-    L.gnnpp_lsigf_team_lists_fwd.argtypes = [vp] * 6 + [cs] + [ci] * 10 + [vp]
-    L.gnnpp_lsigf_team_lists_fwd.restype = ci
-    L.gnnpp_filter_head_team_lists_fwd.argtypes = [vp] * 8 + [cs] + [ci] * 7 + [vp]
-    L.gnnpp_filter_head_team_lists_fwd.restype = ci
-    L.gnnpp_policy_team_lists_fwd.argtypes = [vp] * 9 + [ci] * 5 + [vp, vp, vp, cs]
-    L.gnnpp_policy_team_lists_fwd.restype = ci
-    L.gnnpp_team_lists_transpose.argtypes = [vp, vp, cs, ci, ci, vp]
-    L.gnnpp_team_lists_transpose.restype = ci
-    L.gnnpp_lsigf_team_lists_fwd_save.argtypes = [vp] * 7 + [cs] + [ci] * 10 + [vp]
-    L.gnnpp_lsigf_team_lists_fwd_save.restype = ci
-    L.gnnpp_lsigf_team_lists_input_grad.argtypes = [vp] * 5 + [cs] + [ci] * 7 + [vp]
-    L.gnnpp_lsigf_team_lists_input_grad.restype = ci
-    L.gnnpp_filter_head_mode.argtypes = [ci, ci, ci, ci]
-    L.gnnpp_filter_head_mode.restype = ci
-    for f in ('gnnpp_rollout_observe', 'gnnpp_rollout_gso', 'gnnpp_rollout_move', 'gnnpp_rollout_gso_observe',
-              'gnnpp_rollout_step'):
-        getattr(L, f).argtypes = [ctypes.POINTER(RolloutStruct), vp]
-        getattr(L, f).restype = ci
-    L.gnnpp_rollout_policy_step.argtypes = [ctypes.POINTER(RolloutStruct)] + [vp] * 5 + [ci, ci, vp]
-    L.gnnpp_rollout_policy_step.restype = ci
-    L.gnnpp_rollout_policy_steps.argtypes = [ctypes.POINTER(RolloutStruct)] + [vp] * 5 + [ci, ci, ci, vp]
-    L.gnnpp_rollout_policy_steps.restype = ci
-    L.gnnpp_schedule_samples.argtypes = [ctypes.POINTER(ScheduleStruct), vp]
-    L.gnnpp_schedule_samples.restype = ci
-    L.gnnpp_schedule_team_workspace_bytes.argtypes = [ci, ci]
-    L.gnnpp_schedule_team_workspace_bytes.restype = cs
-    L.gnnpp_schedule_team_samples.argtypes = [ctypes.POINTER(ScheduleStruct), vp, cs, vp]
-    L.gnnpp_schedule_team_samples.restype = ci
-    L.gnnpp_schedule_team_plan.argtypes = [ctypes.POINTER(ScheduleStruct), vp, cs, vp, vp]
-    L.gnnpp_schedule_team_plan.restype = ci
-    L.gnnpp_schedule_team_fill_lists.argtypes = [ctypes.POINTER(ScheduleStruct), vp, cs, vp, vp, vp, ci, vp]
-    L.gnnpp_schedule_team_fill_lists.restype = ci
-    L.gnnpp_team_lists_gather.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, cs, ci, vp]
-    L.gnnpp_team_lists_gather.restype = ci
-    L.gnnpp_mapf_workspace_bytes.argtypes = [ci] * 4
-    L.gnnpp_mapf_workspace_bytes.restype = cs
-    L.gnnpp_mapf_solve.argtypes = [ctypes.POINTER(MapfStruct), vp]
-    L.gnnpp_mapf_solve.restype = ci
-    L.gnnpp_mapf_team_workspace_bytes.argtypes = [ci] * 5
-    L.gnnpp_mapf_team_workspace_bytes.restype = cs
-    L.gnnpp_mapf_team_solve.argtypes = [ctypes.POINTER(MapfStruct), vp]
-    L.gnnpp_mapf_team_solve.restype = ci
-    for f in ('gnnpp_filter_pack', 'gnnpp_lsigf_fwd', 'gnnpp_encoder_pack', 'gnnpp_encoder_fwd',
-              'gnnpp_policy_fwd', 'gnnpp_decode_actions', 'gnnpp_rollout_observe', 'gnnpp_rollout_gso',
-           'gnnpp_rollout_move'):
-        getattr(L, f).restype = ci
-    return L
 
 
 def lib():
@@ -360,7 +326,7 @@ def lib():
         raise GnnppError(
             'libgnnpp.so is missing (%s). Build it with `python -c "import __graft_entry__ as g; '
             'g.build()"` (hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
-    _lib = _bind(LIB_PATH)
+    _lib = bind(ctypes.CDLL(LIB_PATH))
     _apply_toolchain_policy(_lib)
     return _lib
 
@@ -383,8 +349,8 @@ def _apply_toolchain_policy(L):
                   'compiler-scheduled forms (GNNPP_TUNE_POLICY_CP = 0, GNNPP_TUNE_ENCODER_CP_TILE = 16; same results). Run '
                   '`pytest -m gpu -k column_packed` and set GNNPP_TRUST_TOOLCHAIN=1 (or update _native.VALIDATED_HIPCC) '
                   'to re-enable them.' % (ver, VALIDATED_HIPCC))
-    L.gnnpp_set_tuning(13, 0)
-    L.gnnpp_set_tuning(14, 16)
+    L.gnnpp_set_tuning(TUNE_POLICY_CP, 0)
+    L.gnnpp_set_tuning(TUNE_ENCODER_CP_TILE, 16)
 
 
 def measure_lib():
@@ -393,7 +359,7 @@ def measure_lib():
     modules never load it."""
     global _measure_lib
     if _measure_lib is None:
-        _measure_lib = _bind(build(measure=True))
+        _measure_lib = bind(ctypes.CDLL(build(measure=True)))
     return _measure_lib
 
 

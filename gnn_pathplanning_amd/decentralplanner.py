@@ -160,7 +160,7 @@ class _LinearFunction(torch.autograd.Function):
                 rc = _native.lib().gnnpp_linear_fwd(_ptr(xd), _ptr(Wd), _ptr(b.detach().contiguous()) if b is not None
                                                     else None, _ptr(y), R, I, O, int(relu != 0),
                                                     _native.stream_ptr(x.device))
-            if rc == -2:
+            if rc == _native.ERR_UNSUPPORTED:
                 y = None                                      # GNNPP_ERR_UNSUPPORTED (alignment): the library GEMM
             else:
                 _native.check(rc, 'gnnpp_linear_fwd')

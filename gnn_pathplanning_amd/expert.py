@@ -26,9 +26,8 @@ import torch
 
 from . import _native, formats
 
-MAX_AGENTS = 128                      # GNNPP_ROLLOUT_MAX_AGENTS
-MAX_TEAM = 1024                       # GNNPP_ROLLOUT_MAX_TEAM
-BAD_MOVE, BAD_STATE, NO_RADIUS = 1, 2, 4          # GNNPP_SCHEDULE_* status bits
+MAX_AGENTS, MAX_TEAM = _native.ROLLOUT_MAX_AGENTS, _native.ROLLOUT_MAX_TEAM
+BAD_MOVE, BAD_STATE, NO_RADIUS = _native.SCHEDULE_BAD_MOVE, _native.SCHEDULE_BAD_STATE, _native.SCHEDULE_NO_RADIUS
 
 
 class ScheduleSamples:

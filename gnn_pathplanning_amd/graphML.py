@@ -45,7 +45,7 @@ infiniteNumber = 1e12
 DEFAULT_PRECISION = 'fp32'
 
 _MAX_F_PER_LAUNCH = 128
-MAX_NODES = 112         # rows one workgroup holds in LDS (GNNPP_MAX_NODES=100 guaranteed at G=F=128)
+MAX_NODES = _native.MAX_ROWS     # rows one workgroup holds in LDS (_native.MAX_NODES = 100 guaranteed at G = F = 128)
 
 
 def _ptr(t):
@@ -94,7 +94,7 @@ def _fp32_arg(x):
 # 128, not split-f16).  The two round differently, which is why the default stays.  Training has a field of its own
 # (LARGE_GRAPH_TRAININGS below).
 LARGE_GRAPH_FILTERS = ('dense', 'lists')
-TEAM_MAX_NODES = 1024   # GNNPP_ROLLOUT_MAX_TEAM
+TEAM_MAX_NODES = _native.ROLLOUT_MAX_TEAM
 
 
 def large_graph_filter(name):
@@ -519,14 +519,14 @@ def _lsigf_device(h, S, x, b, batched, Nin, packed=None, relu=False, transposed=
             rc = L.gnnpp_lsigf_fwd(_ptr(xc), _ptr(Sc), _ptr(packed), _ptr(bias), _ptr(y),
                                    B, N, Nin, G, F_out, K, E, s64, int(batched), nm, nm, int(relu),
                                    per_node, int(precision), None, _native.stream_ptr(dev))
-    if rc == -2 and L.gnnpp_lsigf_fits(N, G, F_out, K, E) != 0:
+    if rc == _native.ERR_UNSUPPORTED and L.gnnpp_lsigf_fits(N, G, F_out, K, E) != 0:
         _native.check(rc, 'gnnpp_lsigf_fwd')     # GNNPP_ERR_UNSUPPORTED for another reason than LDS room: an error
-    if rc == -2 and not (transposed or save_taps):
+    if rc == _native.ERR_UNSUPPORTED and not (transposed or save_taps):
         # GNNPP_ERR_UNSUPPORTED below MAX_NODES, confirmed by gnnpp_lsigf_fits: the graph's rows do not fit the kernel's
         # LDS budget (wide input features, or 101..112 nodes at G = F = 128).  The reference has no such limit: the
         # dense exact-fp32 form.
         return _on_all_nodes(lambda xn: _lsigf_large(h, S, xn, b, batched, relu), x, N, node_major)
-    if rc == -2 and (transposed or save_taps):
+    if rc == _native.ERR_UNSUPPORTED and (transposed or save_taps):
         return None                                # the training driver (_LSIGFFunction) takes its dense path instead
     _native.check(rc, 'gnnpp_lsigf_fwd')
     return (y, zs) if save_taps else y

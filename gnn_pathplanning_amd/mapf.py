@@ -19,13 +19,10 @@ import torch
 
 from . import _native
 
-MAX_AGENTS = 128                      # GNNPP_ROLLOUT_MAX_AGENTS
-MAX_SIDE = 64                         # GNNPP_MAPF_MAX_SIDE
-MAX_STEPS = 1024                      # GNNPP_MAPF_MAX_STEPS
-MAX_TEAM = 1024                       # GNNPP_ROLLOUT_MAX_TEAM        (solve_team)
-MAX_TEAM_SIDE = 256                   # GNNPP_MAPF_TEAM_MAX_SIDE
-MAX_TEAM_STEPS = 2048                 # GNNPP_MAPF_TEAM_MAX_STEPS
-NO_PATH, BAD_CASE = 1, 2              # GNNPP_MAPF_* status bits
+MAX_AGENTS, MAX_SIDE, MAX_STEPS = _native.ROLLOUT_MAX_AGENTS, _native.MAPF_MAX_SIDE, _native.MAPF_MAX_STEPS
+MAX_TEAM, MAX_TEAM_SIDE, MAX_TEAM_STEPS = (_native.ROLLOUT_MAX_TEAM, _native.MAPF_TEAM_MAX_SIDE,      # (solve_team)
+                                           _native.MAPF_TEAM_MAX_STEPS)
+NO_PATH, BAD_CASE = _native.MAPF_NO_PATH, _native.MAPF_BAD_CASE
 
 
 class Solutions:

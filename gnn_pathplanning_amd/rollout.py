@@ -23,10 +23,11 @@ import torch
 
 from . import _native
 
-_TIE = {'lowest': 0, 'hashed': 1, 'replay': 2, 'mt19937': 3}
-MAX_AGENTS = 128            # GNNPP_ROLLOUT_MAX_AGENTS: the one-wave simulator kernels
-MAX_TEAM = 1024             # GNNPP_ROLLOUT_MAX_TEAM
-MAX_TEAM_CELLS = 65536      # GNNPP_ROLLOUT_TEAM_MAX_CELLS: map limit of the large-team kernels
+_TIE = {'lowest': _native.TIE_LOWEST, 'hashed': _native.TIE_HASHED, 'replay': _native.TIE_REPLAY,
+        'mt19937': _native.TIE_MT19937}
+MAX_AGENTS = _native.ROLLOUT_MAX_AGENTS             # the one-wave simulator kernels
+MAX_TEAM = _native.ROLLOUT_MAX_TEAM
+MAX_TEAM_CELLS = _native.ROLLOUT_TEAM_MAX_CELLS     # map limit of the large-team kernels
 GRAPHS = ('dense', 'lists')  # how a BatchedRollout hands the communication graph to the policy
 
 
@@ -229,7 +230,7 @@ class BatchedRollout:
         with _native.device_guard(self.device):
             rc = _native.lib().gnnpp_rollout_policy_steps(ctypes.byref(r), enc, taps, gb, aw, ab, K, nsteps, prec,
                                                           _native.stream_ptr(self.device))
-        if rc == -2:                                         # shape not supported by the fused kernel
+        if rc == _native.ERR_UNSUPPORTED:           # shape not supported by the fused kernel
             return False
         _native.check(rc, 'gnnpp_rollout_policy_steps')
         self.t += nsteps

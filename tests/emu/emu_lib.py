@@ -5,6 +5,8 @@ import subprocess
 
 import numpy as np
 
+from gnn_pathplanning_amd import _native
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 SRC = os.path.join(ROOT, 'gnn_pathplanning_amd', 'csrc')
@@ -24,18 +26,15 @@ def build():
     return LIB
 
 
-class EncParams(ctypes.Structure):
-    _fields_ = [('conv_w', ctypes.c_void_p * 5), ('conv_b', ctypes.c_void_p * 5),
-                ('bn_w', ctypes.c_void_p * 5), ('bn_b', ctypes.c_void_p * 5),
-                ('bn_mean', ctypes.c_void_p * 5), ('bn_var', ctypes.c_void_p * 5),
-                ('fc_w', ctypes.c_void_p), ('fc_b', ctypes.c_void_p), ('bn_eps', ctypes.c_float)]
+_lib = None
 
 
 def load():
-    lib = ctypes.CDLL(build())
-    lib.gnnpp_filter_packed_floats.restype = ctypes.c_size_t
-    lib.gnnpp_encoder_packed_floats.restype = ctypes.c_size_t
-    return lib
+    """The emulated library, bound with the package's own table of the C ABI (one handle per process)."""
+    global _lib
+    if _lib is None:
+        _lib = _native.bind(ctypes.CDLL(build()))
+    return _lib
 
 
 def ptr(a):
@@ -53,7 +52,7 @@ BN_KEYS = (1, 5, 8, 12, 15)
 def pack_encoder(lib, sd):
     """sd: dict name -> numpy array (reference state_dict layout)."""
     keep = []
-    p = EncParams()
+    p = _native.EncoderParams()
     for i in range(5):
         for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV_KEYS[i]),
                            ('conv_b', 'ConvLayers.%d.bias' % CONV_KEYS[i]),

@@ -22,8 +22,6 @@ from f64_yardstick import gap
 PRECS = (0, 1, 2)                 # GNNPP_PREC_FP32 (bf16x3) | GNNPP_PREC_FP32_MFMA | GNNPP_PREC_SPLIT_F16
 PREC_NAMES = {0: 'fp32', 1: 'fp32mfma', 2: 'splitf16'}
 SCALES = (1e-6, 1e-3, 1.0, 1e3)
-# knobs (include/gnnpp.h)
-GPW, WAVES, SPLIT, SMALL, SMALL_ROWS, PIPE_GRID, POLICY_FILTER, PLANE_ALIAS = 1, 2, 7, 10, 11, 12, 9, 16
 
 
 # ---- backends --------------------------------------------------------------------------------------------------------
@@ -37,8 +35,6 @@ class EmuBackend:
 
     def __init__(self, lib):
         self.lib, self.stream = lib, None
-        lib.gnnpp_set_tuning.argtypes = [ctypes.c_int, ctypes.c_int]
-        lib.gnnpp_get_tuning.argtypes = [ctypes.c_int]
 
     def put(self, a, offset=0):
         flat = np.zeros(a.size + offset, a.dtype)

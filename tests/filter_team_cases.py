@@ -6,27 +6,13 @@ Inputs, pack, statements, yardstick and backends are those of tests/filter_f64_c
 the float64 statement of the same call with the fp32 numpy statement as the measure (f64_yardstick.gap), never to
 anything the kernels produce.  The workspace is handed over filled with NaN bytes: a list entry or tap signal read
 before it was written shows."""
-import ctypes
 
 import numpy as np
 
 import filter_f64_cases as fc
+from gnn_pathplanning_amd._native import ERR_ARG, ERR_UNSUPPORTED  # noqa: F401 (the tests' names)
 
 PRECS = (0, 1)                    # GNNPP_PREC_FP32 (bf16x3) | GNNPP_PREC_FP32_MFMA   (split-f16: GNNPP_ERR_UNSUPPORTED)
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
-
-
-def bind(lib):
-    """ctypes prototypes of the team calls (size_t arguments) on a raw CDLL; resolves the symbols first."""
-    vp, ci, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    lib.gnnpp_lsigf_team_workspace_bytes.argtypes = [ci] * 6
-    lib.gnnpp_lsigf_team_workspace_bytes.restype = cs
-    lib.gnnpp_lsigf_team_fwd.argtypes = [vp] * 6 + [cs] + [ci] * 11 + [vp]
-    lib.gnnpp_lsigf_team_fwd.restype = ci
-    lib.gnnpp_filter_head_team_fwd.argtypes = [vp] * 8 + [cs] + [ci] * 8 + [vp]
-    lib.gnnpp_filter_head_team_fwd.restype = ci
-    lib.gnnpp_version.restype = ci
-    return lib
 
 
 def shape_s(S, kind, seed):

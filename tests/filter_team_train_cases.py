@@ -17,21 +17,9 @@ import filter_f64_cases as fc
 import filter_team_cases as tc
 import rollout_lists_cases as lc
 from f64_yardstick import MAX_K, RMS_K, gap
+from gnn_pathplanning_amd._native import ERR_ARG, ERR_UNSUPPORTED
 
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
 MIN_WEIGHT = 2.0 ** -10           # every non-zero weight is at least this: from_dense never drops an edge as a zero
-
-
-def bind(lib):
-    vp, ci, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    lc.bind(lib)
-    lib.gnnpp_team_lists_transpose.argtypes = [vp, vp, cs, ci, ci, vp]
-    lib.gnnpp_team_lists_transpose.restype = ci
-    lib.gnnpp_lsigf_team_lists_fwd_save.argtypes = [vp] * 7 + [cs] + [ci] * 10 + [vp]
-    lib.gnnpp_lsigf_team_lists_fwd_save.restype = ci
-    lib.gnnpp_lsigf_team_lists_input_grad.argtypes = [vp] * 5 + [cs] + [ci] * 7 + [vp]
-    lib.gnnpp_lsigf_team_lists_input_grad.restype = ci
-    return lib
 
 
 # ---- graphs ----------------------------------------------------------------------------------------------------------

@@ -29,28 +29,20 @@ import torch
 import torch.nn.functional as tF
 
 from f64_yardstick import MAX_K, ULP, ULPS, gap
-from filter_f64_cases import Knobs, TorchBackend
+from filter_f64_cases import Knobs
+from gnn_pathplanning_amd import _native
+from gnn_pathplanning_amd._native import TUNE_ENCODER_CP_TILE, TUNE_FUSED_POLICY, TUNE_POLICY_CP
 from oracle import policy_oracle as orc
 
 PRECS = (0, 1, 2)
 PREC_NAMES = {0: 'fp32', 1: 'fp32mfma', 2: 'splitf16'}
 EPS = orc.BN_EPS
 CONV, BN = orc.CONV_KEYS, orc.BN_KEYS
-# knobs (include/gnnpp.h)
-FUSED, POLICY_CP, ENC_CP = 6, 13, 14
 CP_MAX = 12                                                       # kCpMaxAgents
 # one residual pixel: 1 + 2^-8 (its m plane is 2^-8) and 1 + 2^-16 (a residual the size of the old 1e-5 bounds).  The
 # round-to-nearest split of gnnpp_common.h b3_split2 puts any non-zero residual into the m plane first (no fp32 value
 # has an l plane without an m plane), so both raise the tile's plane flag; dropping them costs 2^-8 / 2^-16 of the pixel
 RESID = {'m': 1.0 + 2.0 ** -8, 'l': 1.0 + 2.0 ** -16}
-
-
-class EncParams(ctypes.Structure):
-    """struct gnnpp_encoder_params (include/gnnpp.h), for the emulated library."""
-    _fields_ = [('conv_w', ctypes.c_void_p * 5), ('conv_b', ctypes.c_void_p * 5),
-                ('bn_w', ctypes.c_void_p * 5), ('bn_b', ctypes.c_void_p * 5),
-                ('bn_mean', ctypes.c_void_p * 5), ('bn_var', ctypes.c_void_p * 5),
-                ('fc_w', ctypes.c_void_p), ('fc_b', ctypes.c_void_p), ('bn_eps', ctypes.c_float)]
 
 
 # ---- the statements ------------------------------------------------------------------------------------------------
@@ -270,22 +262,18 @@ def fused_policy_applies(B, N, K, E, prec, fused_knob):
 
 
 def policy_kernels(B, N, K, E, prec, knobs):
-    """The instance(s) gnnpp_policy_fwd launches under `knobs` (the library's values of FUSED, POLICY_CP, ENC_CP)."""
-    if fused_policy_applies(B, N, K, E, prec, knobs[FUSED]):
+    """The instance(s) gnnpp_policy_fwd launches under `knobs` (the library's values of the three TUNE_* keys)."""
+    if fused_policy_applies(B, N, K, E, prec, knobs[TUNE_FUSED_POLICY]):
         if prec == 0:
-            return 'encoder_kernel_b3<true,%d,%s>' % (K, 'true' if N <= CP_MAX and knobs[POLICY_CP] else 'false')
+            return 'encoder_kernel_b3<true,%d,%s>' % (K, 'true' if N <= CP_MAX and knobs[TUNE_POLICY_CP] else 'false')
         return 'encoder_kernel_h2<true,%d>' % K
-    return encoder_kernel(B * N, prec, knobs[ENC_CP], knobs[POLICY_CP]) + '+filter'
+    return encoder_kernel(B * N, prec, knobs[TUNE_ENCODER_CP_TILE], knobs[TUNE_POLICY_CP]) + '+filter'
 
 
 # ---- the runner ----------------------------------------------------------------------------------------------------
 def _put_params(bk, sd):
     """(struct gnnpp_encoder_params on bk, the buffers it points to)."""
-    if isinstance(bk, TorchBackend):
-        from gnn_pathplanning_amd import _native
-        p = _native.EncoderParams()
-    else:
-        p = EncParams()
+    p = _native.EncoderParams()
     keep = []
     for i in range(5):
         bn = 'ConvLayers.%d.' % BN[i]
@@ -323,7 +311,7 @@ def pack_filter(bk, h):
 
 
 def knob_values(lib):
-    return {k: lib.gnnpp_get_tuning(k) for k in (FUSED, POLICY_CP, ENC_CP)}
+    return {k: lib.gnnpp_get_tuning(k) for k in (TUNE_FUSED_POLICY, TUNE_POLICY_CP, TUNE_ENCODER_CP_TILE)}
 
 
 def allowed_error(rep):
@@ -347,7 +335,7 @@ def run_encoder(bk, sd, obs, prec, knobs=None, expect=None, name=''):
     flag = bk.put(np.zeros(1, np.int32))
     with Knobs(bk.lib, knobs or {}):
         kv = knob_values(bk.lib)
-        kern = encoder_kernel(M, prec, kv[ENC_CP], kv[POLICY_CP])
+        kern = encoder_kernel(M, prec, kv[TUNE_ENCODER_CP_TILE], kv[TUNE_POLICY_CP])
         if expect is not None and prec in expect:
             assert expect[prec] in kern, (name, prec, kern, expect[prec])
         assert bk.lib.gnnpp_encoder_fwd(ob.ptr, packed.ptr, feat.ptr, M, prec, flag.ptr, bk.stream) == 0

@@ -16,32 +16,7 @@ import numpy as np
 
 import filter_f64_cases as fc
 import filter_team_cases as tc
-
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
-
-
-def bind(lib):
-    """ctypes prototypes of the lists calls on a raw CDLL (the emulated library); resolves the symbols first."""
-    from gnn_pathplanning_amd._native import RolloutStruct
-    vp, ci, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    tc.bind(lib)
-    lib.gnnpp_team_lists_bytes.argtypes = [ci, ci]
-    lib.gnnpp_team_lists_bytes.restype = cs
-    lib.gnnpp_team_lists_from_dense.argtypes = [vp, vp, cs, ci, ci, ci, vp]
-    lib.gnnpp_team_lists_from_dense.restype = ci
-    lib.gnnpp_rollout_lists.argtypes = [ctypes.POINTER(RolloutStruct), vp, cs, vp]
-    lib.gnnpp_rollout_lists.restype = ci
-    lib.gnnpp_rollout_gso.argtypes = [ctypes.POINTER(RolloutStruct), vp]
-    lib.gnnpp_rollout_gso.restype = ci
-    lib.gnnpp_lsigf_team_lists_fwd.argtypes = [vp] * 6 + [cs] + [ci] * 10 + [vp]
-    lib.gnnpp_lsigf_team_lists_fwd.restype = ci
-    lib.gnnpp_filter_head_team_lists_fwd.argtypes = [vp] * 8 + [cs] + [ci] * 7 + [vp]
-    lib.gnnpp_filter_head_team_lists_fwd.restype = ci
-    lib.gnnpp_policy_team_lists_fwd.argtypes = [vp] * 9 + [ci] * 5 + [vp, vp, vp, cs]
-    lib.gnnpp_policy_team_lists_fwd.restype = ci
-    lib.gnnpp_policy_team_fwd.argtypes = [vp] * 9 + [ci] * 6 + [vp, vp, vp, cs]
-    lib.gnnpp_policy_team_fwd.restype = ci
-    return lib
+from gnn_pathplanning_amd._native import ERR_ARG, ERR_UNSUPPORTED
 
 
 # ---- the block ---------------------------------------------------------------------------------------------------

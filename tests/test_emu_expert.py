@@ -12,31 +12,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import expert_cases as ec  # noqa: E402
+from gnn_pathplanning_amd._native import ERR_ARG, ERR_UNSUPPORTED, ScheduleStruct  # noqa: E402
+from gnn_pathplanning_amd._native import SCHEDULE_BAD_MOVE as BAD_MOVE, SCHEDULE_BAD_STATE as BAD_STATE  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
                                 reason='host clang++ from ROCm not present')
-
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
-BAD_MOVE, BAD_STATE = 1, 2
-
-
-class Schedules(ctypes.Structure):
-    """struct gnnpp_schedules (include/gnnpp.h)."""
-    _fields_ = [('grid', ctypes.c_void_p), ('grid_batched', ctypes.c_int), ('goal', ctypes.c_void_p),
-                ('pos', ctypes.c_void_p), ('case_start', ctypes.c_void_p), ('C', ctypes.c_int), ('N', ctypes.c_int),
-                ('H', ctypes.c_int), ('W', ctypes.c_int), ('T_total', ctypes.c_int), ('radius0', ctypes.c_double),
-                ('obs', ctypes.c_void_p), ('S', ctypes.c_void_p), ('S64', ctypes.c_void_p),
-                ('target', ctypes.c_void_p), ('radius', ctypes.c_void_p), ('growth', ctypes.c_void_p),
-                ('status', ctypes.c_void_p), ('step_info', ctypes.c_void_p)]
 
 
 @pytest.fixture(scope='module')
 def lib():
     import emu_lib
-    L = emu_lib.load()
-    L.gnnpp_schedule_samples.argtypes = [ctypes.POINTER(Schedules), ctypes.c_void_p]
-    L.gnnpp_schedule_samples.restype = ctypes.c_int
-    return L
+    return emu_lib.load()
 
 
 def call(lib, grids, goals, schedules, radius0=5.0, fp64=True, expect=0, poison=np.nan):
@@ -52,7 +38,7 @@ def call(lib, grids, goals, schedules, radius0=5.0, fp64=True, expect=0, poison=
            'S64': np.full((T, N, N), poison, np.float64), 'target': np.full((T, N, 5), poison, np.float32),
            'radius': np.full(C, poison, np.float64), 'growth': np.full(C, -1, np.int32),
            'status': np.full(C, -1, np.int32), 'step_info': np.full(T, -1, np.int32), 'start': start}
-    s = Schedules()
+    s = ScheduleStruct()
     s.grid, s.grid_batched, s.goal, s.pos = grid.ctypes.data, int(grid.ndim == 3), goal.ctypes.data, pos.ctypes.data
     s.case_start, s.C, s.N, s.H, s.W, s.T_total = start.ctypes.data, C, N, grid.shape[-2], grid.shape[-1], T
     s.radius0 = radius0
@@ -167,7 +153,7 @@ def test_argument_errors(lib):
     out = call(lib, expect=ERR_UNSUPPORTED, **huge)                            # the map does not fit the LDS grid
     assert np.isnan(out['obs']).all()
     assert lib.gnnpp_schedule_samples(None, None) == ERR_ARG
-    s = Schedules()
+    s = ScheduleStruct()
     assert lib.gnnpp_schedule_samples(ctypes.byref(s), None) == ERR_ARG        # NULL pointers
     assert lib.gnnpp_version() == 330
 

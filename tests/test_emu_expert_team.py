@@ -15,23 +15,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import expert_cases as ec  # noqa: E402
+from gnn_pathplanning_amd._native import ERR_ARG, ERR_UNSUPPORTED, ScheduleStruct  # noqa: E402
+from gnn_pathplanning_amd._native import SCHEDULE_BAD_MOVE as BAD_MOVE, SCHEDULE_BAD_STATE as BAD_STATE  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
                                 reason='host clang++ from ROCm not present')
 
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
-BAD_MOVE, BAD_STATE = 1, 2
 OUTPUTS = ('obs', 'S', 'S64', 'target', 'radius', 'growth', 'status', 'step_info')
-
-
-class Schedules(ctypes.Structure):
-    """struct gnnpp_schedules (include/gnnpp.h)."""
-    _fields_ = [('grid', ctypes.c_void_p), ('grid_batched', ctypes.c_int), ('goal', ctypes.c_void_p),
-                ('pos', ctypes.c_void_p), ('case_start', ctypes.c_void_p), ('C', ctypes.c_int), ('N', ctypes.c_int),
-                ('H', ctypes.c_int), ('W', ctypes.c_int), ('T_total', ctypes.c_int), ('radius0', ctypes.c_double),
-                ('obs', ctypes.c_void_p), ('S', ctypes.c_void_p), ('S64', ctypes.c_void_p),
-                ('target', ctypes.c_void_p), ('radius', ctypes.c_void_p), ('growth', ctypes.c_void_p),
-                ('status', ctypes.c_void_p), ('step_info', ctypes.c_void_p)]
 
 
 def load_team_golden():
@@ -45,14 +35,7 @@ def load_team_golden():
 @pytest.fixture(scope='module')
 def lib():
     import emu_lib
-    L = emu_lib.load()
-    L.gnnpp_schedule_samples.argtypes = [ctypes.POINTER(Schedules), ctypes.c_void_p]
-    L.gnnpp_schedule_samples.restype = ctypes.c_int
-    L.gnnpp_schedule_team_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.gnnpp_schedule_team_workspace_bytes.restype = ctypes.c_size_t
-    L.gnnpp_schedule_team_samples.argtypes = [ctypes.POINTER(Schedules), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    L.gnnpp_schedule_team_samples.restype = ctypes.c_int
-    return L
+    return emu_lib.load()
 
 
 def call(lib, grids, goals, schedules, radius0=5.0, fp64=True, expect=0, poison=np.nan, team=True, workspace='exact',
@@ -78,7 +61,7 @@ def call(lib, grids, goals, schedules, radius0=5.0, fp64=True, expect=0, poison=
            'radius': np.full(C, poison, np.float64), 'growth': np.full(C, -1, np.int32),
            'status': np.full(C, -1, np.int32), 'step_info': np.full(T, -1, np.int32), 'start': start}
     assert (out['S'].ctypes.data % 16 != 0) == misalign and (out['S64'].ctypes.data % 16 != 0) == misalign
-    s = Schedules()
+    s = ScheduleStruct()
     s.grid, s.grid_batched, s.goal, s.pos = grid.ctypes.data, int(grid.ndim == 3), goal.ctypes.data, pos.ctypes.data
     s.case_start, s.C, s.N, s.H, s.W, s.T_total = start.ctypes.data, C, N, grid.shape[-2], grid.shape[-1], T
     s.radius0 = radius0
@@ -247,7 +230,7 @@ def test_argument_errors(lib):
     huge = dict(grids=np.zeros((256, 257), np.uint8), goals=g['goal'][None], schedules=[g['schedule']])
     nothing_written(call(lib, expect=ERR_UNSUPPORTED, **huge))                 # the map does not fit the LDS grid
     more_cases = dict(grids=g['grid'], goals=np.stack([g['goal']] * 2), schedules=[g['schedule'][:1]])
-    s = Schedules()
+    s = ScheduleStruct()
     ws = np.zeros(64, np.float64)
     assert lib.gnnpp_schedule_team_samples(None, ws.ctypes.data, 512, None) == ERR_ARG
     assert lib.gnnpp_schedule_team_samples(ctypes.byref(s), ws.ctypes.data, 512, None) == ERR_ARG      # NULL pointers

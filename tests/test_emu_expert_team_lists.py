@@ -27,7 +27,7 @@ GOLD = lc.load_team_golden()
 @pytest.fixture(scope='module')
 def lib():
     import emu_lib
-    return lc.bind(emu_lib.load())
+    return emu_lib.load()
 
 
 assert_plan_outputs_equal_dense = lc.assert_plan_outputs_equal_dense

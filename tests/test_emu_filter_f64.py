@@ -10,6 +10,8 @@ import pytest
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu'))
 
 import filter_f64_cases as fc  # noqa: E402
+from gnn_pathplanning_amd._native import (TUNE_FILTER_GPW, TUNE_FILTER_PIPE_GRID, TUNE_FILTER_SMALL,
+                                          TUNE_FILTER_SMALL_ROWS, TUNE_FILTER_SPLIT)  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
                                 reason='host clang++ from ROCm not present')
@@ -26,13 +28,13 @@ LSIGF = [
     dict(name='lsigf<rtw1,nw8,ng8>/B2N12K3', seed=1, B=2, N=12, G=128, F=128, K=3, E=1, bias='feat'),
     # <RTW 2, NW 16>: two graphs of 12 per workgroup; node-major x and y, ReLU, fp64 S
     dict(name='lsigf<rtw2,nw16,ng8>/gpw2/nodemajor/relu/f64S', seed=2, B=3, N=12, G=128, F=128, K=2, E=1,
-         bias='feat', x_nm=1, y_nm=1, relu=1, f64=1, knobs={fc.GPW: 2}),
+         bias='feat', x_nm=1, y_nm=1, relu=1, f64=1, knobs={TUNE_FILTER_GPW: 2}),
     # run-time NG (G = 33), F = 129 in two chunks with a per-node bias, Nin < N, shared S, E = 2
     dict(name='lsigf<ng-runtime>/G33F129/pernode/Nin<N/sharedS/E2', seed=3, B=2, N=9, Nin=6, G=33, F=129, K=2, E=2,
          bias='node', batched=False),
     # nsplit = 2 forced over a 40-node graph (3 row tiles), S view offset by one float (s_vec4 off), K = 5
     dict(name='lsigf<nsplit2>/N40K5/s_offset', seed=4, B=3, N=40, G=128, F=128, K=5, E=1, s_offset=1,
-         knobs={fc.SPLIT: 2}),
+         knobs={TUNE_FILTER_SPLIT: 2}),
     # the training form: tap signals kept (gnnpp_lsigf_fwd_save), E = 2, F = 64 (MTP 4)
     dict(name='lsigf_save<rtw1,nw8,ng8>/E2F64', seed=5, B=2, N=10, G=128, F=64, K=3, E=2, bias='feat', save=True),
     # taps spread over 1e-3 .. 1e2
@@ -41,10 +43,10 @@ LSIGF = [
     dict(name='lsigf<rtw1,nw8,ng8>/N1K1', seed=7, B=5, N=1, G=128, F=128, K=1, E=1, bias='feat'),
     # lsigf_small_b3_kernel (FILTER_SMALL = 2, 32-row workgroups; other precisions: lsigf_kernel), ragged last group
     dict(name='small_b3<rows32>/N5/ragged', seed=8, B=9, N=5, G=128, F=128, K=3, E=1, bias='feat', x_nm=1, y_nm=1,
-         knobs={fc.SMALL: 2, fc.SMALL_ROWS: 32}),
+         knobs={TUNE_FILTER_SMALL: 2, TUNE_FILTER_SMALL_ROWS: 32}),
     # lsigf_pipe_b3_kernel (FILTER_SMALL = 3, persistent grid of 7)
     dict(name='pipe_b3<grid7>/N4', seed=9, B=40, N=4, G=128, F=128, K=2, E=1, bias='feat', x_nm=1, y_nm=1,
-         knobs={fc.SMALL: 3, fc.PIPE_GRID: 7}),
+         knobs={TUNE_FILTER_SMALL: 3, TUNE_FILTER_PIPE_GRID: 7}),
 ]
 
 

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang
 @pytest.fixture(scope='module')
 def bk():
     import emu_lib
-    return fc.EmuBackend(tc.bind(emu_lib.load()))
+    return fc.EmuBackend(emu_lib.load())
 
 
 TEAM = [

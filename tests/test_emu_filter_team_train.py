@@ -21,7 +21,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang
 @pytest.fixture(scope='module')
 def bk():
     import emu_lib
-    return fc.EmuBackend(tt.bind(emu_lib.load()))
+    return fc.EmuBackend(emu_lib.load())
 
 
 @pytest.mark.parametrize('case', tt.TRANSPOSE_CASES, ids=lambda c: c['name'])

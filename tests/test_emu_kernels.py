@@ -13,6 +13,8 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu'))
 
+from gnn_pathplanning_amd import _native  # noqa: E402
+
 pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
                                 reason='host clang++ from ROCm not present')
 
@@ -128,7 +130,7 @@ def test_emu_non_finite_observations_are_flushed(emu, prec):
     aw, ab = el.f32(sd['actionsMLP.0.weight']), el.f32(sd['actionsMLP.0.bias'])
     try:
         for fused in (1, 0):
-            lib.gnnpp_set_tuning(6, fused)
+            lib.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, fused)
             obs, Sn = el.f32(obs_t.numpy()), el.f32(S.numpy())
             logits = np.full((N, B, 5), np.nan, dtype=np.float32)
             ws = np.zeros((B * N, 128), dtype=np.float32)
@@ -139,7 +141,7 @@ def test_emu_non_finite_observations_are_flushed(emu, prec):
             assert np.abs(got[[0, 3]] - want[[0, 3]]).max() <= TOL
             assert np.isfinite(got).all(), (prec, fused)
     finally:
-        lib.gnnpp_set_tuning(6, 1)
+        lib.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 1)
 
 
 def test_emu_encoder_negative_and_zero_batchnorm_scales(emu):
@@ -189,7 +191,7 @@ def test_emu_fused_policy_kernel_equals_two_kernels(emu, policy_golden, prec):
             S = np.ascontiguousarray(z['p%d_S' % i])
             outs = []
             for mode in (1, 0):
-                assert lib.gnnpp_set_tuning(6, mode) == 0
+                assert lib.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, mode) == 0
                 logits = np.full((N, B, 5), np.nan, dtype=np.float32)
                 ws = np.zeros((B * N, 128), dtype=np.float32)
                 assert lib.gnnpp_policy_fwd(el.ptr(obs), el.ptr(S), el.ptr(enc), el.ptr(filt), el.ptr(gb),
@@ -203,7 +205,7 @@ def test_emu_fused_policy_kernel_equals_two_kernels(emu, policy_golden, prec):
             assert np.abs(outs[0].transpose(1, 0, 2) - z['p%d_logits' % i]).max() <= TOL
             ran += 1
     finally:
-        lib.gnnpp_set_tuning(6, 1)
+        lib.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 1)
     assert ran >= 2
 
 
@@ -228,7 +230,7 @@ def test_emu_fused_policy_kernel_other_tap_counts(emu, K, prec):
     outs = []
     try:
         for mode in (1, 0):
-            assert lib.gnnpp_set_tuning(6, mode) == 0
+            assert lib.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, mode) == 0
             logits = np.full((N, B, 5), np.nan, dtype=np.float32)
             ws = np.zeros((B * N, 128), dtype=np.float32)
             assert lib.gnnpp_policy_fwd(el.ptr(obs), el.ptr(S), el.ptr(enc), el.ptr(filt), el.ptr(gb), el.ptr(aw),
@@ -237,7 +239,7 @@ def test_emu_fused_policy_kernel_other_tap_counts(emu, K, prec):
             if mode == 1:
                 assert not ws.any()                          # one kernel: the feature workspace is not written
     finally:
-        lib.gnnpp_set_tuning(6, 1)
+        lib.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 1)
     if prec == 2:
         assert np.array_equal(outs[0], outs[1]), np.abs(outs[0] - outs[1]).max()
     else:
@@ -257,17 +259,18 @@ def test_emu_filter_forced_gpw(emu, lsigf_golden):
     b = z['c%d_b' % i] if meta[i]['has_bias'] else None
     try:
         for gpw, waves in ((1, 8), (2, 16), (2, 8), (1, 16)):
-            assert lib.gnnpp_set_tuning(1, gpw) == 0 and lib.gnnpp_set_tuning(2, waves) == 0
+            assert (lib.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, gpw) == 0
+                    and lib.gnnpp_set_tuning(_native.TUNE_FILTER_WAVES, waves) == 0)
             y = el.lsigf(lib, h, S, x, b, True)
             assert np.abs(y - want).max() <= TOL, (gpw, waves)
     finally:
-        lib.gnnpp_set_tuning(1, 0)
-        lib.gnnpp_set_tuning(2, 0)
-    assert lib.gnnpp_set_tuning(8, 0) == -1
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_WAVES, 0)
     # the arithmetic is a per-call argument since ABI 300: the former precision knobs (0: encoder schedule, 5: filter
-    # f16) and the measurement-only knobs (csrc/gnnpp_measure.h) are not part of the ABI
-    assert lib.gnnpp_set_tuning(0, 7) == -1 and lib.gnnpp_set_tuning(5, 1) == -1 and lib.gnnpp_get_tuning(0) == -1
-    assert lib.gnnpp_set_tuning(3, 1) == -1 and lib.gnnpp_set_tuning(4, 1) == -1
+    # f16), the retired key 8 and the measurement-only knobs (csrc/gnnpp_measure.h) are not part of the ABI
+    for retired_key, value in ((8, 0), (0, 7), (5, 1), (_native.TUNE_FILTER_ABLATE, 1), (_native.TUNE_ENCODER_STOP, 1)):
+        assert lib.gnnpp_set_tuning(retired_key, value) == -1
+        assert lib.gnnpp_get_tuning(retired_key) == -1
     assert lib.gnnpp_version() == 330
 
 
@@ -421,7 +424,8 @@ def test_emu_filter_two_workgroups_per_graph(emu, lsigf_golden):
             batched = m['kind'] in ('BatchLSIGF', 'GraphFilterBatch')
             outs = []
             for split in (1, 2, 7):
-                assert lib.gnnpp_set_tuning(7, split) == 0 and lib.gnnpp_set_tuning(1, 1) == 0
+                assert (lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, split) == 0
+                        and lib.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 1) == 0)
                 outs.append(el.lsigf(lib, h, S, x, b, batched, Nin=m.get('Nin')))
             assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2]), (i, m)
             assert np.abs(outs[1] - z['c%d_y' % i]).max() <= TOL * max(1.0, np.abs(z['c%d_y' % i]).max())
@@ -435,7 +439,7 @@ def test_emu_filter_two_workgroups_per_graph(emu, lsigf_golden):
         packed = el.pack_filter(lib, h)
         res = []
         for split in (1, 3):
-            assert lib.gnnpp_set_tuning(7, split) == 0
+            assert lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, split) == 0
             y = np.full((B, N, F_out), np.nan, np.float32)
             zs = np.full((E * K, B * N, G), np.nan, np.float32)
             rc = lib.gnnpp_lsigf_fwd_save(el.ptr(x), el.ptr(S), el.ptr(packed), None, el.ptr(y), el.ptr(zs),
@@ -447,8 +451,8 @@ def test_emu_filter_two_workgroups_per_graph(emu, lsigf_golden):
         ref = np.maximum(orc.lsigf_f64(h, S, x.transpose(0, 2, 1)), 0).transpose(0, 2, 1)
         assert np.abs(res[1][0] - ref).max() <= TOL * max(1.0, np.abs(ref).max())
     finally:
-        lib.gnnpp_set_tuning(7, 0)
-        lib.gnnpp_set_tuning(1, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 0)
     assert picked >= 4
 
 
@@ -475,11 +479,12 @@ def test_emu_policy_filter_kernel(emu, N, K, f64, split, B, prec):
     ab = g.standard_normal(5).astype(np.float32)
     packed = el.pack_filter(lib, h)
     outs = []
-    lib.gnnpp_set_tuning(2, 0)
+    lib.gnnpp_set_tuning(_native.TUNE_FILTER_WAVES, 0)
     try:
-        assert lib.gnnpp_set_tuning(7, split) == 0 and lib.gnnpp_set_tuning(1, 1) == 0
+        assert lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, split) == 0 and lib.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 1) == 0
         for mode in (1, 0):
-            assert lib.gnnpp_set_tuning(9, mode) == 0 and lib.gnnpp_get_tuning(9) == mode
+            assert (lib.gnnpp_set_tuning(_native.TUNE_POLICY_FILTER, mode) == 0
+                    and lib.gnnpp_get_tuning(_native.TUNE_POLICY_FILTER) == mode)
             logits = np.full((N, B, 5), np.nan, dtype=np.float32)
             flag = np.zeros(1, np.int32)
             assert lib.gnnpp_filter_head_fwd(el.ptr(x), el.ptr(S), el.ptr(packed), el.ptr(bias), el.ptr(aw),
@@ -488,7 +493,9 @@ def test_emu_policy_filter_kernel(emu, N, K, f64, split, B, prec):
             assert flag[0] == 0
             outs.append(logits)
     finally:
-        lib.gnnpp_set_tuning(9, 1); lib.gnnpp_set_tuning(7, 0); lib.gnnpp_set_tuning(1, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_POLICY_FILTER, 1)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 0)
     # fp64 restatement: z_k[b, n, :] = sum_m S[b, m, n] z_{k-1}[b, m, :]
     z = x.astype(np.float64)
     y = np.zeros((B, N, 128))
@@ -522,9 +529,10 @@ def test_emu_small_graph_throughput_kernel(emu, N, K, B, f64, head):
         # (mode 3: the producer / consumer pipeline kernel -- persistent 8-wave workgroups, 64-row groups; no head form)
         # (pipeline grid 2 / 1: a persistent workgroup takes several groups -- staging of the next group beside the taps)
         for mode, rows, pgrid in ((2, 32, 0), (2, 48, 0), (0, 0, 0)) + (() if head else ((3, 0, 0), (3, 0, 2), (3, 0, 1))):
-            assert lib.gnnpp_set_tuning(12, pgrid) == 0
-            assert lib.gnnpp_set_tuning(10, mode) == 0 and lib.gnnpp_get_tuning(10) == mode
-            assert lib.gnnpp_set_tuning(11, rows) == 0
+            assert lib.gnnpp_set_tuning(_native.TUNE_FILTER_PIPE_GRID, pgrid) == 0
+            assert (lib.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, mode) == 0
+                    and lib.gnnpp_get_tuning(_native.TUNE_FILTER_SMALL) == mode)
+            assert lib.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL_ROWS, rows) == 0
             if head:
                 out = np.full((N, B, 5), np.nan, dtype=np.float32)
                 assert lib.gnnpp_filter_head_fwd(el.ptr(x), el.ptr(S), el.ptr(packed), el.ptr(bias), el.ptr(aw),
@@ -535,9 +543,9 @@ def test_emu_small_graph_throughput_kernel(emu, N, K, B, f64, head):
                                            128, 128, K, 1, f64, 1, 1, 1, 1, 0, 0, None, None) == 0
             outs.append(out)
     finally:
-        lib.gnnpp_set_tuning(10, 1)
-        lib.gnnpp_set_tuning(11, 0)
-        lib.gnnpp_set_tuning(12, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, 1)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL_ROWS, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_PIPE_GRID, 0)
     z = x.astype(np.float64)
     y = np.zeros((B, N, 128))
     for k in range(K):
@@ -551,7 +559,8 @@ def test_emu_small_graph_throughput_kernel(emu, N, K, B, f64, head):
     if not head:
         assert all(np.array_equal(outs[0], o) for o in outs[3:])   # ... and the pipeline kernel's, however the groups are dealt
     assert np.abs(outs[0] - outs[2]).max() <= 4e-6 * scale
-    assert lib.gnnpp_set_tuning(10, 4) == -1 and lib.gnnpp_set_tuning(11, 40) == -1
+    assert (lib.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, 4) == -1
+            and lib.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL_ROWS, 40) == -1)
 
 
 @pytest.mark.parametrize('N,K,B,real_obs', [(10, 3, 2, False), (12, 3, 1, False), (1, 2, 2, False), (5, 4, 1, False),
@@ -579,7 +588,7 @@ def test_emu_column_packed_policy_kernel_is_bit_identical(emu, N, K, B, real_obs
     outs = []
     try:
         for cp in (1, 0):
-            assert lib.gnnpp_set_tuning(13, cp) == 0 and lib.gnnpp_get_tuning(13) == cp
+            assert lib.gnnpp_set_tuning(_native.TUNE_POLICY_CP, cp) == 0 and lib.gnnpp_get_tuning(_native.TUNE_POLICY_CP) == cp
             logits = np.full((N, B, 5), np.nan, dtype=np.float32)
             ws = np.zeros((B * N, 128), dtype=np.float32)
             assert lib.gnnpp_policy_fwd(el.ptr(obs), el.ptr(S), el.ptr(enc), el.ptr(filt), el.ptr(gb), el.ptr(aw),
@@ -587,13 +596,13 @@ def test_emu_column_packed_policy_kernel_is_bit_identical(emu, N, K, B, real_obs
             assert not ws.any()                              # the one-launch kernel ran (both times)
             outs.append(logits)
     finally:
-        lib.gnnpp_set_tuning(13, 1)
+        lib.gnnpp_set_tuning(_native.TUNE_POLICY_CP, 1)
     assert np.isfinite(outs[0]).all()
     assert np.array_equal(outs[0], outs[1]), np.abs(outs[0] - outs[1]).max()
     with torch.no_grad():
         want = torch.stack(orc.policy_forward(sd_t, S_t, obs_t), 0).numpy()
     assert np.abs(outs[0] - want).max() <= TOL
-    assert lib.gnnpp_set_tuning(13, 2) == -1
+    assert lib.gnnpp_set_tuning(_native.TUNE_POLICY_CP, 2) == -1
 
 
 @pytest.mark.parametrize('M,tile', [(23, 7), (16, 12), (5, 1), (30, 4), (37, 0), (25, 10)])
@@ -613,16 +622,17 @@ def test_emu_column_packed_encoder_tiles_are_bit_identical(emu, M, tile):
     feats = []
     try:
         for knob in (tile, 16):
-            assert lib.gnnpp_set_tuning(14, knob) == 0 and lib.gnnpp_get_tuning(14) == knob
+            assert (lib.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, knob) == 0
+                    and lib.gnnpp_get_tuning(_native.TUNE_ENCODER_CP_TILE) == knob)
             feat = np.full((M, 128), np.nan, np.float32)
             assert lib.gnnpp_encoder_fwd(el.ptr(obs), el.ptr(enc), el.ptr(feat), M, 0, None, None) == 0
             feats.append(feat)
     finally:
-        lib.gnnpp_set_tuning(14, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, 0)
     assert np.isfinite(feats[0]).all() and np.array_equal(feats[0], feats[1]), np.abs(feats[0] - feats[1]).max()
     want = orc.policy_features(sd_t, obs_t).permute(0, 2, 1).reshape(M, 128).numpy()
     assert np.abs(feats[0] - want).max() <= 1e-5 * max(1.0, np.abs(want).max())
-    assert lib.gnnpp_set_tuning(14, 13) == -1
+    assert lib.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, 13) == -1
 
 
 @pytest.mark.parametrize('N,K,f64,B', [(100, 3, 0, 2), (100, 2, 1, 1), (100, 4, 0, 1), (72, 3, 0, 2), (50, 4, 1, 1), (33, 3, 0, 9)])
@@ -651,25 +661,26 @@ def test_emu_policy_filter_kernel_n_way_split(emu, N, K, f64, B):
     rt = (N + 15) // 16
     splits = sorted({1, 2, 3, rt, 7})                        # (values above the row tiles are clamped to them)
     outs, modes = {}, {}
-    lib.gnnpp_set_tuning(2, 0)
+    lib.gnnpp_set_tuning(_native.TUNE_FILTER_WAVES, 0)
     try:
-        assert lib.gnnpp_set_tuning(1, 1) == 0
+        assert lib.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 1) == 0
         for prec in (1, 0):
             for split in splits:
-                assert lib.gnnpp_set_tuning(7, split) == 0
+                assert lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, split) == 0
                 logits = np.full((N, B, 5), np.nan, dtype=np.float32)
                 assert lib.gnnpp_filter_head_fwd(el.ptr(x), el.ptr(S), el.ptr(packed), el.ptr(bias), el.ptr(aw),
                                                  el.ptr(ab), el.ptr(logits), B, N, 128, 128, K, 1, f64, prec, None,
                                                  None) == 0
                 outs[prec, split] = logits
                 modes[prec, split] = lib.gnnpp_filter_head_mode(B, N, K, prec)
-        assert lib.gnnpp_set_tuning(7, 8) == -1
+        assert lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 8) == -1
         # r06: the default arithmetic of a SPLIT team of 65 .. 100 agents keeps its bf16x3 planes in the dead z buffer
         # (mode 3) instead of falling back to the exact fp32 MFMA (mode 1: what one workgroup per graph still runs);
         # GNNPP_TUNE_FILTER_PLANE_ALIAS = 0 restores the fallback, whose logits are those of precision 1 bit for bit
         if N == 100:
             assert modes[0, 1] == 1 and modes[0, 2] == 3 and modes[0, 3] == 3 and modes[0, 7] == 3, modes
-            assert lib.gnnpp_set_tuning(16, 0) == 0 and lib.gnnpp_set_tuning(7, 2) == 0
+            assert (lib.gnnpp_set_tuning(_native.TUNE_FILTER_PLANE_ALIAS, 0) == 0
+                    and lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 2) == 0)
             assert lib.gnnpp_filter_head_mode(B, N, K, 0) == 1
             logits = np.full((N, B, 5), np.nan, dtype=np.float32)
             assert lib.gnnpp_filter_head_fwd(el.ptr(x), el.ptr(S), el.ptr(packed), el.ptr(bias), el.ptr(aw),
@@ -679,7 +690,9 @@ def test_emu_policy_filter_kernel_n_way_split(emu, N, K, f64, B):
             assert modes[0, 1] == 1 and modes[0, 2] == 3 and modes[0, 3] == 2, modes
         assert all(modes[1, sp] == 1 for sp in splits)
     finally:
-        lib.gnnpp_set_tuning(7, 0); lib.gnnpp_set_tuning(1, 0); lib.gnnpp_set_tuning(16, 1)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 0)
+        lib.gnnpp_set_tuning(_native.TUNE_FILTER_PLANE_ALIAS, 1)
     z = x.astype(np.float64)
     y = np.zeros((B, N, 128))
     for k in range(K):

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu
 pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
                                 reason='host clang++ from ROCm not present')
 
-ONE_PLANE, ENC_CP_TILE, POLICY_CP = 20, 14, 13
+from gnn_pathplanning_amd._native import TUNE_ENCODER_CP_TILE as ENC_CP_TILE, TUNE_ENCODER_ONE_PLANE as ONE_PLANE  # noqa: E402
 
 
 @pytest.fixture(scope='module')

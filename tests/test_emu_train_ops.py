@@ -22,7 +22,7 @@ by_name = lambda c: c['name']                                               # no
 @pytest.fixture(scope='module')
 def bk():
     import emu_lib
-    return fc.EmuBackend(to.bind(emu_lib.load()))
+    return fc.EmuBackend(emu_lib.load())
 
 
 def test_emu_gemm_plan_is_the_library_s(bk):

@@ -12,16 +12,14 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu'))
 
+from gnn_pathplanning_amd import _native  # noqa: E402
+from gnn_pathplanning_amd._native import AdamTensors, EncoderGrads, EncoderParams, GemmDesc  # noqa: E402
+
 pytestmark = pytest.mark.skipif(not os.path.exists('/opt/rocm/lib/llvm/bin/clang++'),
                                 reason='host clang++ from ROCm not present')
 
 CONV = (0, 4, 7, 11, 14)
 BN = (1, 5, 8, 12, 15)
-
-
-class Grads(ctypes.Structure):
-    _fields_ = [('conv_w', ctypes.c_void_p * 5), ('conv_b', ctypes.c_void_p * 5),
-                ('bn_w', ctypes.c_void_p * 5), ('bn_b', ctypes.c_void_p * 5)]
 
 
 def reference(sd, obs, cot):
@@ -53,7 +51,6 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
     import emu_lib as el
     from oracle import policy_oracle as orc
     lib = el.load()
-    lib.gnnpp_encoder_train_workspace_floats.restype = ctypes.c_size_t
     sd = orc.init_state_dict(3, seed=40 + seed)
     g = torch.Generator().manual_seed(seed)
     obs = (torch.rand(B, N, 3, 11, 11, generator=g) < 0.25).float() + 0.1 * torch.randn(B, N, 3, 11, 11, generator=g)
@@ -61,7 +58,7 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
     want_feat, p_ref, run_ref = reference(sd, obs, cot)
 
     keep = []
-    P = el.EncParams()
+    P = EncoderParams()
     arrs = {}
     for i in range(5):
         for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
@@ -81,7 +78,6 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
     # graph filter's taps) instead of the pack the forward call builds in its workspace
     tp = None
     if ext_pack:
-        lib.gnnpp_train_pack_floats.restype = ctypes.c_size_t
         tp = np.full(lib.gnnpp_train_pack_floats(), np.nan, np.float32)
         assert tp.ctypes.data % 16 == 0
         assert lib.gnnpp_train_pack(ctypes.byref(P), el.ptr(tp), None, None, None, 0, 0, 0, 0, None) == 0
@@ -91,11 +87,12 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
     assert rc == 0
     assert all(int(a[0]) == 7 + N for a in nbt)
     # r06b: the running-statistics update rides in the forward's last BatchNorm launch (GNNPP_TUNE_TRAIN_RUNNING_FUSED,
-    # default); the launch of its own (knob 19 = 0) gives the same bits
-    assert lib.gnnpp_get_tuning(19) == 1 and lib.gnnpp_set_tuning(19, 0) == 0
+    # default); the launch of its own (knob = 0) gives the same bits
+    assert (lib.gnnpp_get_tuning(_native.TUNE_TRAIN_RUNNING_FUSED) == 1
+            and lib.gnnpp_set_tuning(_native.TUNE_TRAIN_RUNNING_FUSED, 0) == 0)
     try:
         arrs2 = {k: el.f32(sd[k].numpy().copy()) for k in arrs if 'running' in k}
-        P2 = el.EncParams()
+        P2 = EncoderParams()
         ctypes.memmove(ctypes.byref(P2), ctypes.byref(P), ctypes.sizeof(P))
         for i in range(5):
             P2.bn_mean[i] = arrs2['ConvLayers.%d.running_mean' % BN[i]].ctypes.data
@@ -110,7 +107,7 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
             assert np.array_equal(a2, arrs[k]), k
         # update_running = 0 (BatchNorm2d(track_running_stats=False)): the running-statistic pointers arrive as NULL -- the
         # fused update must stay off (r06c fix: it dereferenced them) and the features are the same
-        assert lib.gnnpp_set_tuning(19, 1) == 0
+        assert lib.gnnpp_set_tuning(_native.TUNE_TRAIN_RUNNING_FUSED, 1) == 0
         ws3, feat3 = np.zeros_like(ws), np.full((N, B, 128), np.nan, np.float32)
         rc = lib.gnnpp_encoder_train_fwd(ctypes.byref(P2), el.ptr(obs_np), el.ptr(ws3), el.ptr(feat3), B, N,
                                          ctypes.c_float(0.1), 0, None, fbn, el.ptr(tp) if tp is not None else None, None)
@@ -118,7 +115,7 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
         for k, a2 in arrs2.items():
             assert np.array_equal(a2, arrs[k]), k            # (untouched by that call)
     finally:
-        assert lib.gnnpp_set_tuning(19, 1) == 0
+        assert lib.gnnpp_set_tuning(_native.TUNE_TRAIN_RUNNING_FUSED, 1) == 0
     if fbn:                                                  # feat_sample_major: the same rows as [B,N,128]
         feat = np.ascontiguousarray(feat.reshape(B, N, 128).transpose(1, 0, 2))
     assert np.abs(feat - want_feat.numpy()).max() <= 2e-5 * max(1.0, want_feat.abs().max().item())
@@ -130,7 +127,7 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
             ok, rep = f64_gap(arrs[key], run64[key], run_ref[key])    # and at fp32 level against float64
             assert ok, (key, rep)
 
-    G = Grads()
+    G = EncoderGrads()
     outs = {}
     for i in range(5):
         for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
@@ -143,9 +140,10 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
     assert rc == 0
     # r06b: the weight gradients of all five layers come from ONE launch behind the chain (GNNPP_TUNE_TRAIN_WGRAD_MERGED,
     # default); the per-layer launches of r05 (knob 18 = 0) give the same bits
-    assert lib.gnnpp_get_tuning(18) == 1 and lib.gnnpp_set_tuning(18, 0) == 0
+    assert (lib.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_MERGED) == 1
+            and lib.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 0) == 0)
     try:
-        G2, outs2 = Grads(), {}
+        G2, outs2 = EncoderGrads(), {}
         for i in range(5):
             for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
                                ('bn_w', 'ConvLayers.%d.weight' % BN[i]), ('bn_b', 'ConvLayers.%d.bias' % BN[i])):
@@ -157,7 +155,7 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
         for key in outs:
             assert np.array_equal(outs[key], outs2[key]), key
     finally:
-        assert lib.gnnpp_set_tuning(18, 1) == 0
+        assert lib.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 1) == 0
     for key, o in outs.items():
         want = p_ref[key].grad.numpy()
         scale = np.abs(want).max()
@@ -166,18 +164,12 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
         assert np.isfinite(o).all() and np.abs(o - want).max() <= tol, (key, np.abs(o - want).max(), scale)
 
 
-class AdamTensors(ctypes.Structure):
-    _fields_ = [('p', ctypes.c_void_p * 32), ('g', ctypes.c_void_p * 32), ('m', ctypes.c_void_p * 32),
-                ('v', ctypes.c_void_p * 32), ('numel', ctypes.c_longlong * 32), ('count', ctypes.c_int)]
-
-
 @pytest.mark.parametrize('batch,M,N,K', [(3, 128, 128, 70), (1, 5, 128, 33), (1, 1, 40, 57), (2, 70, 20, 300)])
 def test_emu_gemm_kmajor(batch, M, N, K):
     """gnnpp_gemm_kmajor (split contraction, ordered partial sums) against numpy, strided operands included:
     the first case is the graph filter's tap gradient written straight into the [F,E,K,G] layout."""
     import emu_lib as el
     lib = el.load()
-    lib.gnnpp_gemm_workspace_floats.restype = ctypes.c_size_t
     ll = ctypes.c_longlong
     rng = np.random.default_rng(batch * 1000 + M)
     A = rng.standard_normal((M, K)).astype(np.float32)              # shared by every batch entry (a_sb = 0)
@@ -257,20 +249,11 @@ def test_emu_adam_matches_torch():
             np.testing.assert_allclose(a, p.detach().numpy(), rtol=0, atol=3e-7)
 
 
-class GemmDesc(ctypes.Structure):
-    _fields_ = [('A', ctypes.c_void_p), ('a_sb', ctypes.c_longlong), ('a_sm', ctypes.c_longlong),
-                ('a_sk', ctypes.c_longlong), ('B', ctypes.c_void_p), ('b_sb', ctypes.c_longlong),
-                ('b_sk', ctypes.c_longlong), ('C', ctypes.c_void_p), ('c_sb', ctypes.c_longlong),
-                ('c_sm', ctypes.c_longlong), ('batch', ctypes.c_int), ('M', ctypes.c_int), ('N', ctypes.c_int),
-                ('K', ctypes.c_int), ('mask', ctypes.c_void_p)]
-
-
 def test_emu_gemm_multi_linear_backward():
     """gnnpp_gemm_kmajor_multi: the three products of a Linear layer's backward pass (dx = dY W, dW = dY^T X,
     db = 1^T dY) in one call, against numpy -- one of them split over the contraction, one not."""
     import emu_lib as el
     lib = el.load()
-    lib.gnnpp_gemm_multi_workspace_floats.restype = ctypes.c_size_t
     rng = np.random.default_rng(5)
     R, I, O = 90, 128, 5
     dY = rng.standard_normal((R, O)).astype(np.float32)
@@ -394,9 +377,8 @@ def run_emu_encoder(lib, sd, obs, cot):
     """gnnpp_encoder_train_fwd + _bwd (one call each, default knobs) -> feat [N,B,128], running statistics,
     num_batches_tracked increments, parameter gradients."""
     import emu_lib as el
-    lib.gnnpp_encoder_train_workspace_floats.restype = ctypes.c_size_t
     B, N = obs.shape[0], obs.shape[1]
-    P, arrs = el.EncParams(), {}
+    P, arrs = EncoderParams(), {}
     for i in range(5):
         for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
                            ('bn_w', 'ConvLayers.%d.weight' % BN[i]), ('bn_b', 'ConvLayers.%d.bias' % BN[i]),
@@ -412,7 +394,7 @@ def run_emu_encoder(lib, sd, obs, cot):
     assert lib.gnnpp_encoder_train_fwd(ctypes.byref(P), el.ptr(obs_np), el.ptr(ws), el.ptr(feat), B, N,
                                        ctypes.c_float(0.1), 1, (ctypes.c_void_p * 5)(*[a.ctypes.data for a in nbt]),
                                        0, None, None) == 0
-    G, grads = Grads(), {}
+    G, grads = EncoderGrads(), {}
     for i in range(5):
         for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
                            ('bn_w', 'ConvLayers.%d.weight' % BN[i]), ('bn_b', 'ConvLayers.%d.bias' % BN[i])):

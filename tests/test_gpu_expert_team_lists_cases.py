@@ -4,7 +4,6 @@ gnnpp_schedule_team_plan, gnnpp_schedule_team_fill_lists and gnnpp_team_lists_ga
 same assertions: every array, poisoned with 0xFF bytes (NaN, -1) and set between sentinel margins, has a twin in device
 memory for the length of a call; the lists equal those of the sequential restatement's dense S and of the dense call,
 the margins keep their bytes, and what a call must not write stays poison."""
-import ctypes
 import os
 import sys
 
@@ -22,8 +21,7 @@ pytestmark = pytest.mark.gpu
 def lib():
     assert torch.cuda.is_available(), 'needs the MI355X'
     from gnn_pathplanning_amd import _native
-    _native.lib()
-    return lc.bind(ctypes.CDLL(_native.LIB_PATH))       # (a handle of its own: the package's prototypes stay as they are)
+    return _native.lib()
 
 
 @pytest.fixture(scope='module')

@@ -19,6 +19,10 @@ import torch
 
 import filter_f64_cases as fc
 from f64_yardstick import gap
+from gnn_pathplanning_amd._native import (TUNE_FILTER_GPW, TUNE_FILTER_PIPE_GRID,
+                                          TUNE_FILTER_PLANE_ALIAS, TUNE_FILTER_SMALL,
+                                          TUNE_FILTER_SMALL_ROWS, TUNE_FILTER_SPLIT,
+                                          TUNE_FILTER_WAVES)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,13 +44,14 @@ def _cases():
     # ---- lsigf_kernel <RTW, NW, NG 8>: N = 16 graphs, gpw forced: rt_total = gpw row tiles; B = 2 gpw + 1 (ragged)
     for r in range(1, 8):
         C.append(dict(name='lsigf<rtw%d,nw8,ng8>/gpw%d' % (r, r), seed=100 + r, B=2 * r + 1, N=16, G=128, F=128, K=3,
-                      E=1, bias='feat', knobs={fc.GPW: r, fc.WAVES: 8}, expect=(8, r)))
+                      E=1, bias='feat', knobs={TUNE_FILTER_GPW: r, TUNE_FILTER_WAVES: 8}, expect=(8, r)))
     for g, r in ((2, 1), (4, 2), (6, 3), (7, 4)):
         C.append(dict(name='lsigf<rtw%d,nw16,ng8>/gpw%d' % (r, g), seed=110 + g, B=2 * g + 3, N=16, G=128, F=128,
-                      K=2, E=1, bias='feat', x_nm=1, y_nm=1, relu=1, knobs={fc.GPW: g, fc.WAVES: 16}, expect=(16, r)))
+                      K=2, E=1, bias='feat', x_nm=1, y_nm=1, relu=1, knobs={TUNE_FILTER_GPW: g, TUNE_FILTER_WAVES: 16},
+                      expect=(16, r)))
     # F <= 64 (4 output tiles: two row-tile chunks per 8 waves)
     C.append(dict(name='lsigf<rtw3,nw8,ng8>/F33/gpw6', seed=120, B=13, N=16, G=128, F=33, K=3, E=1, bias='feat',
-                  knobs={fc.GPW: 6, fc.WAVES: 8}, expect=(8, 3)))
+                  knobs={TUNE_FILTER_GPW: 6, TUNE_FILTER_WAVES: 8}, expect=(8, 3)))
     # ---- G, F, E, K sweep (run-time NG for G != 128; F > 128: chunks)
     for i, (G, F, E, K, bias) in enumerate(((1, 5, 1, 2, 'feat'), (17, 1, 2, 3, None), (100, 33, 3, 1, 'feat'),
                                             (128, 129, 1, 4, 'node'), (128, 257, 2, 2, 'node'),
@@ -75,7 +80,7 @@ def _cases():
                   x_nm=1, y_nm=1, relu=1))
     for s in range(2, 8):
         C.append(dict(name='lsigf<nsplit%d>/N100' % s, seed=180 + s, B=13, N=100, G=128, F=128, K=3, E=1,
-                      bias='feat', knobs={fc.SPLIT: s}))
+                      bias='feat', knobs={TUNE_FILTER_SPLIT: s}))
     # ---- the training form: tap signals (chunk 0 of F = 257 included)
     C.append(dict(name='lsigf_save<auto>/E2K3', seed=190, B=17, N=12, G=128, F=128, K=3, E=2, bias='feat',
                   save=True))
@@ -86,11 +91,11 @@ def _cases():
         rows = (32, 48)[i % 2]
         C.append(dict(name='small_b3<rows%d>/N%d' % (rows, N), seed=200 + i, B=37, N=N, G=128, F=128, K=3, E=1,
                       bias='feat', x_nm=1, y_nm=1, relu=i % 2, f64=i % 3 == 0,
-                      knobs={fc.SMALL: 2, fc.SMALL_ROWS: rows}))
+                      knobs={TUNE_FILTER_SMALL: 2, TUNE_FILTER_SMALL_ROWS: rows}))
     # ---- lsigf_pipe_b3_kernel (FILTER_SMALL = 3): every graph checked
     for i, (N, pg) in enumerate(((10, 0), (10, 7), (3, 7), (16, 0))):
         C.append(dict(name='pipe_b3<grid%d>/N%d' % (pg, N), seed=220 + i, B=1037, N=N, G=128, F=128, K=3 - i % 2,
-                      E=1, bias='feat', x_nm=1, y_nm=1, knobs={fc.SMALL: 3, fc.PIPE_GRID: pg}))
+                      E=1, bias='feat', x_nm=1, y_nm=1, knobs={TUNE_FILTER_SMALL: 3, TUNE_FILTER_PIPE_GRID: pg}))
     return C
 
 
@@ -101,8 +106,8 @@ LSIGF = _cases()
 def test_plan_restatement_names_the_template(case):
     c = case
     k = c['knobs']
-    _, _, nw, rtw = fc.plan(c['B'], c['N'], c['G'], c['F'], c['K'], k.get(fc.GPW, 0), k.get(fc.WAVES, 0),
-                            k.get(fc.SPLIT, 0))
+    _, _, nw, rtw = fc.plan(c['B'], c['N'], c['G'], c['F'], c['K'], k.get(TUNE_FILTER_GPW, 0), k.get(TUNE_FILTER_WAVES, 0),
+                            k.get(TUNE_FILTER_SPLIT, 0))
     assert (nw, rtw) == c['expect']
 
 
@@ -123,10 +128,10 @@ for _i, _N in enumerate((17, 33, 64, 65, 100)):
     for _alias in (1, 0):
         HEAD.append(dict(name='policy_filter/N%d/alias%d' % (_N, _alias), seed=300 + 2 * _i + _alias, B=3 + _i % 2,
                          N=_N, K=(3, 2, 4, 3, 1)[_i], f64=_i % 2, s_offset=_alias and _i == 2,
-                         knobs={fc.PLANE_ALIAS: _alias}))
+                         knobs={TUNE_FILTER_PLANE_ALIAS: _alias}))
 # two workgroups per graph of 100: the bf16x3 planes only fit aliased onto the dead z buffer (mode 3)
 HEAD.append(dict(name='policy_filter/N100/alias1/nsplit2', seed=320, B=3, N=100, K=3,
-                 knobs={fc.PLANE_ALIAS: 1, fc.SPLIT: 2}, modes={0: 3, 1: 1, 2: 0}))
+                 knobs={TUNE_FILTER_PLANE_ALIAS: 1, TUNE_FILTER_SPLIT: 2}, modes={0: 3, 1: 1, 2: 0}))
 
 
 @pytest.mark.parametrize('scale', fc.SCALES)
@@ -136,7 +141,7 @@ def test_filter_head_f64(bk, case, prec, scale):
     mode, _ = fc.run_head(bk, case, prec, scale)
     # split-f16 -> mode 0, fp32 MFMA -> 1, bf16x3 -> 2 (own plane buffer) or 3 (planes on the dead z buffer: only with
     # PLANE_ALIAS), or 1 where neither fits
-    allowed = {2: {0}, 1: {1}, 0: {1, 2, 3} if case['knobs'][fc.PLANE_ALIAS] else {1, 2}}[prec]
+    allowed = {2: {0}, 1: {1}, 0: {1, 2, 3} if case['knobs'][TUNE_FILTER_PLANE_ALIAS] else {1, 2}}[prec]
     assert mode in allowed, (case['name'], prec, mode)
 
 

@@ -6,7 +6,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-ONE_PLANE = 20
+from gnn_pathplanning_amd._native import TUNE_ENCODER_ONE_PLANE as ONE_PLANE  # noqa: E402
 
 
 def _pixels(kind, B, N, seed):

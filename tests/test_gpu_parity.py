@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import golden_state_dict
+from gnn_pathplanning_amd import _native
 from oracle import policy_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -172,14 +173,14 @@ def test_policy_large_teams_golden(dev, policy_golden, policy_large_golden, enc_
             want = z['q%d_logits' % i]
             net.addGSO(S)
             for mode in (1, 0):
-                assert L.gnnpp_set_tuning(9, mode) == 0
+                assert L.gnnpp_set_tuning(_native.TUNE_POLICY_FILTER, mode) == 0
                 got = torch.stack(net(obs), 1).cpu().numpy()
                 assert np.abs(got - want).max() <= TOL, (i, m, mode, np.abs(got - want).max())
                 srt = np.sort(want, -1)
                 clear = srt[..., -1] - srt[..., -2] > 1e-5
                 assert (got.argmax(-1)[clear] == want.argmax(-1)[clear]).all()
     finally:
-        L.gnnpp_set_tuning(9, 1)
+        L.gnnpp_set_tuning(_native.TUNE_POLICY_FILTER, 1)
 
 
 @pytest.mark.parametrize('B,N,K,W', [(1, 10, 3, 20), (512, 10, 3, 20), (256, 50, 3, 50),
@@ -355,7 +356,7 @@ def test_fused_policy_kernel_equals_two_kernels(dev, B, N, W, K, prec):
             net.addGSO(S)
             outs = []
             for mode in (1, 0, 1):
-                assert L.gnnpp_set_tuning(6, mode) == 0
+                assert L.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, mode) == 0
                 outs.append(net.forward_logits(obs).clone())
             assert torch.equal(outs[0], outs[2])
             if prec == 'split_f16':
@@ -363,7 +364,7 @@ def test_fused_policy_kernel_equals_two_kernels(dev, B, N, W, K, prec):
             else:
                 assert (outs[0] - outs[1]).abs().max().item() <= 2e-6 * max(1.0, outs[1].abs().max().item())
     finally:
-        L.gnnpp_set_tuning(6, 1)
+        L.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 1)
     want = torch.stack(orc.policy_forward(sd, S64.float(), obs.cpu()), 0)
     assert (outs[0].cpu() - want).abs().max().item() <= TOL
 
@@ -391,12 +392,12 @@ def test_column_packed_policy_kernel_is_bit_identical(dev, B, N, K, real_obs):
             net.addGSO(S)
             outs = []
             for cp in (1, 0, 1):
-                assert L.gnnpp_set_tuning(13, cp) == 0 and L.gnnpp_get_tuning(13) == cp
+                assert L.gnnpp_set_tuning(_native.TUNE_POLICY_CP, cp) == 0 and L.gnnpp_get_tuning(_native.TUNE_POLICY_CP) == cp
                 outs.append(net.forward_logits(obs_d).clone())
             assert torch.isfinite(outs[0]).all()
             assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]), (outs[0] - outs[1]).abs().max().item()
     finally:
-        L.gnnpp_set_tuning(13, 1)
+        L.gnnpp_set_tuning(_native.TUNE_POLICY_CP, 1)
     want = torch.stack(orc.policy_forward(sd, S64.float(), obs), 0)
     assert (outs[0].cpu() - want).abs().max().item() <= TOL * max(1.0, want.abs().max().item())
 
@@ -421,12 +422,12 @@ def test_column_packed_encoder_tiles_are_bit_identical(dev, M, tile):
     feats = []
     try:
         for knob in (tile, 16, tile):
-            assert L.gnnpp_set_tuning(14, knob) == 0
+            assert L.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, knob) == 0
             feat = torch.full((M, 128), float('nan'), device=dev)
             assert L.gnnpp_encoder_fwd(vp(obs_d), vp(enc), vp(feat), M, 0, None, _native.stream_ptr(dev)) == 0
             feats.append(feat)
     finally:
-        L.gnnpp_set_tuning(14, 0)
+        L.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, 0)
     assert torch.isfinite(feats[0]).all()
     assert torch.equal(feats[0], feats[1]) and torch.equal(feats[0], feats[2]), (feats[0] - feats[1]).abs().max().item()
     want = orc.policy_features(sd, obs).permute(0, 2, 1).reshape(M, 128)
@@ -945,14 +946,14 @@ def test_policy_filter_n_way_split(dev, B, N, K, f64):
     try:
         for prec in (1, 0):
             for split in (0, 1, 2, 3, 4, 5, 6, 7):           # 0 = the heuristic
-                assert L.gnnpp_set_tuning(7, split) == 0
+                assert L.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, split) == 0
                 outs[prec, split] = run(prec)
             outs[prec, 'again'] = run(prec)                  # (a repeated launch: the same bits)
-        assert L.gnnpp_set_tuning(7, 0) == 0 and L.gnnpp_set_tuning(9, 0) == 0
+        assert L.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 0) == 0 and L.gnnpp_set_tuning(_native.TUNE_POLICY_FILTER, 0) == 0
         general = run(0)                                     # the general filter kernel, its own n-way split
     finally:
-        L.gnnpp_set_tuning(9, 1)
-        L.gnnpp_set_tuning(7, 0)
+        L.gnnpp_set_tuning(_native.TUNE_POLICY_FILTER, 1)
+        L.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 0)
     z = x.double()
     y = torch.zeros(B, N, 128, dtype=torch.float64)
     Sf = S.float().double()
@@ -999,7 +1000,7 @@ def test_policy_filter_kernel_vs_general_filter(dev, B, N, K, f64, prec):
     outs = []
     try:
         for mode in (1, 0, 1):
-            assert L.gnnpp_set_tuning(9, mode) == 0
+            assert L.gnnpp_set_tuning(_native.TUNE_POLICY_FILTER, mode) == 0
             lg = torch.full((N, B, 5), float('nan'), device=dev)
             assert L.gnnpp_filter_head_fwd(xd.data_ptr(), Sd.data_ptr(), packed.data_ptr(), bd.data_ptr(),
                                            awd.data_ptr(), abd.data_ptr(), lg.data_ptr(), B, N, 128, 128, K, 1, f64,
@@ -1007,7 +1008,7 @@ def test_policy_filter_kernel_vs_general_filter(dev, B, N, K, f64, prec):
             torch.cuda.synchronize()
             outs.append(lg.cpu())
     finally:
-        L.gnnpp_set_tuning(9, 1)
+        L.gnnpp_set_tuning(_native.TUNE_POLICY_FILTER, 1)
     assert flag.item() == 0
     assert torch.equal(outs[0], outs[2])                                  # deterministic
     z = x.double()
@@ -1090,7 +1091,8 @@ def test_pipeline_filter_kernel_equals_the_small_graph_kernel(dev, N, K, B):
     outs = []
     try:
         for mode, pgrid in ((2, 0), (3, 0), (3, 7)):
-            assert L.gnnpp_set_tuning(10, mode) == 0 and L.gnnpp_set_tuning(12, pgrid) == 0
+            assert (L.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, mode) == 0
+                    and L.gnnpp_set_tuning(_native.TUNE_FILTER_PIPE_GRID, pgrid) == 0)
             y = torch.full_like(x, float('nan'))
             rc = L.gnnpp_lsigf_fwd(x.data_ptr(), S.data_ptr(), taps.data_ptr(), bias.data_ptr(), y.data_ptr(), B, N, N,
                                    128, 128, K, 1, int(S.dtype is torch.float64), 1, 1, 1, 1, 0, 0, None,
@@ -1098,8 +1100,8 @@ def test_pipeline_filter_kernel_equals_the_small_graph_kernel(dev, N, K, B):
             assert rc == 0
             outs.append(y)
     finally:
-        L.gnnpp_set_tuning(10, 1)
-        L.gnnpp_set_tuning(12, 0)
+        L.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, 1)
+        L.gnnpp_set_tuning(_native.TUNE_FILTER_PIPE_GRID, 0)
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     want = orc.lsigf_f64(h.numpy(), S64.float().unsqueeze(1).numpy()[:64], x.cpu().reshape(B, N, 128)[:64].permute(0, 2, 1).numpy(),
                          bias.cpu().numpy().reshape(128, 1))
@@ -1200,14 +1202,14 @@ def test_non_finite_observations_flush_is_pinned(dev, enc_variant, fused):
     net = _net(10, 3, dev, sd_t)
     net.range_policy = 'flag'
     L = _native.lib()
-    old = L.gnnpp_get_tuning(6)
-    L.gnnpp_set_tuning(6, fused)
+    old = L.gnnpp_get_tuning(_native.TUNE_FUSED_POLICY)
+    L.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, fused)
     try:
         with torch.no_grad():
             net.addGSO(S.to(dev))
             got = torch.stack([g.cpu() for g in net(obs_t.to(dev))], 1).numpy()
     finally:
-        L.gnnpp_set_tuning(6, old)
+        L.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, old)
     assert np.abs(got[[0, 3]] - want[[0, 3]]).max() <= TOL
     assert np.isfinite(got).all()
 
@@ -1231,7 +1233,7 @@ def test_general_filter_n_way_split_is_bit_identical(dev, B, N, G, F_out, K, E):
     outs = {}
     try:
         for split in (1, 0, 2, 3, 5, 7):
-            assert L.gnnpp_set_tuning(7, split) == 0 and L.gnnpp_set_tuning(1, 1) == 0
+            assert L.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, split) == 0 and L.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 1) == 0
             y = torch.full((B, N, F_out), float('nan'), device=dev)
             zs = torch.full((E * K, B * N, G), float('nan'), device=dev)
             rc = L.gnnpp_lsigf_fwd_save(xd.data_ptr(), Sd.data_ptr(), packed.data_ptr(), bd.data_ptr(), y.data_ptr(),
@@ -1242,8 +1244,8 @@ def test_general_filter_n_way_split_is_bit_identical(dev, B, N, G, F_out, K, E):
             torch.cuda.synchronize()
             outs[split] = (y.cpu(), zs.cpu(), yf.cpu())
     finally:
-        L.gnnpp_set_tuning(7, 0)
-        L.gnnpp_set_tuning(1, 0)
+        L.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 0)
+        L.gnnpp_set_tuning(_native.TUNE_FILTER_GPW, 0)
     for split, (y, zs, yf) in outs.items():
         assert torch.equal(y, outs[1][0]) and torch.equal(zs, outs[1][1]) and torch.equal(yf, outs[1][2]), split
     want = np.maximum(orc.lsigf_f64(h.numpy(), S.numpy(), x.permute(0, 2, 1).numpy(), bias.numpy().reshape(F_out, 1)), 0)

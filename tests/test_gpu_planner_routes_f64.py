@@ -17,6 +17,7 @@ import torch
 
 import planner_route_cases as prc
 import policy_f64_cases as pc
+from gnn_pathplanning_amd._native import TUNE_FUSED_POLICY
 
 pytestmark = pytest.mark.gpu
 
@@ -79,7 +80,7 @@ def test_planner_routes_f64(dev, case, prec, lgf):
           % (name, rep['max'], rep['max32'], rep['rms'], rep['rms32'], pc.allowed_error(rep), rep['scale']))
     # the observable half of the path: who writes the planner's feature workspace
     fused = pc.fused_policy_applies(B, N, case['taps'][0], E, _native.precision_code(prec),
-                                    lib.gnnpp_get_tuning(pc.FUSED))
+                                    lib.gnnpp_get_tuning(TUNE_FUSED_POLICY))
     if rt == 'lists_one_call' or (rt == 'policy_fwd' and not fused):
         assert np.isfinite(ws).all(), name
     else:

@@ -33,6 +33,7 @@ import torch
 
 import filter_f64_cases as fc
 import policy_f64_cases as pc
+from gnn_pathplanning_amd._native import TUNE_ENCODER_CP_TILE, TUNE_FUSED_POLICY, TUNE_POLICY_CP
 
 pytestmark = pytest.mark.gpu
 
@@ -100,11 +101,11 @@ def _enc_cases():
         kern = B3 if knob == 16 else '%s[tile%d]' % (B3CP, knob)
         for M in (17, 257):
             C.append(dict(name='%s/M%d/cp_knob%d' % (kern, M, knob), M=M, seed=M, obs='real',
-                          knobs={pc.ENC_CP: knob}, expect={0: kern, 1: F32, 2: H2}))
-    C.append(dict(name='%s/M257/policy_cp0' % B3, M=257, seed=257, obs='real', knobs={pc.POLICY_CP: 0},
+                          knobs={TUNE_ENCODER_CP_TILE: knob}, expect={0: kern, 1: F32, 2: H2}))
+    C.append(dict(name='%s/M257/policy_cp0' % B3, M=257, seed=257, obs='real', knobs={TUNE_POLICY_CP: 0},
                   expect={0: B3, 1: F32, 2: H2}))
     C.append(dict(name='%s[tile1]/M40/bf16obs' % B3CP, M=40, seed=40, obs='bf16', expect={0: B3CP + '[tile1]'}))
-    C.append(dict(name='%s/M40/bf16obs' % B3, M=40, seed=40, obs='bf16', knobs={pc.ENC_CP: 16}, expect={0: B3}))
+    C.append(dict(name='%s/M40/bf16obs' % B3, M=40, seed=40, obs='bf16', knobs={TUNE_ENCODER_CP_TILE: 16}, expect={0: B3}))
     # one residual pixel in an otherwise binary tile: 16-agent tiles (M = 4099: 256 full tiles + a ragged one of 3)
     # and CP tiles (M = 2047: tiles of 8, a ragged last one of 7).  The plane flag is a ballot per wave of the staging
     # loop (four waves, 1024 consecutive pixels of the tile per round): agent 0's centre pixel is staged by wave 0,
@@ -182,9 +183,9 @@ def _policy_cases():
                               f64=(B + K) % 2 == 0,
                               expect={0: _fused_name(N, K), 1: F32, 2: _fused_name(N, K, True)}))
     C.append(dict(name='%s/B600N10K3/fused2' % _fused_name(10, 3), B=600, N=10, K=3, seed=2001, obs='real',
-                  knobs={pc.FUSED: 2}, expect={0: _fused_name(10, 3), 1: F32, 2: _fused_name(10, 3, True)}))
+                  knobs={TUNE_FUSED_POLICY: 2}, expect={0: _fused_name(10, 3), 1: F32, 2: _fused_name(10, 3, True)}))
     C.append(dict(name='encoder_kernel_b3<true,3,false>/B16N10K3/policy_cp0', B=16, N=10, K=3, seed=2002,
-                  obs='real', knobs={pc.POLICY_CP: 0}, expect={0: 'encoder_kernel_b3<true,3,false>'}))
+                  obs='real', knobs={TUNE_POLICY_CP: 0}, expect={0: 'encoder_kernel_b3<true,3,false>'}))
     C.append(dict(name='%s/B600N10K3' % unfused(600, 10), B=600, N=10, K=3, seed=2003, obs='binary',
                   expect={0: unfused(600, 10), 1: F32, 2: H2}))
     for N, B, K in ((17, 5, 3), (50, 3, 2), (100, 2, 4)):
@@ -194,7 +195,7 @@ def _policy_cases():
         C.append(dict(name='%s/B9N10K%d' % (unfused(9, 10), K), B=9, N=10, K=K, seed=2020 + K, obs='real',
                       f64=K == 5, expect={0: unfused(9, 10), 1: F32, 2: H2}))
     C.append(dict(name='%s/B9N10K3/fused0' % unfused(9, 10), B=9, N=10, K=3, seed=2030, obs='real',
-                  knobs={pc.FUSED: 0}, expect={0: unfused(9, 10), 1: F32, 2: H2}))
+                  knobs={TUNE_FUSED_POLICY: 0}, expect={0: unfused(9, 10), 1: F32, 2: H2}))
     # a residual pixel through the fused kernels' L0 (last agent of the team, last pixel)
     for N in (10, 16):
         for kind in ('m', 'l'):

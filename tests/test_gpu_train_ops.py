@@ -23,12 +23,8 @@ def dev():
 
 @pytest.fixture(scope='module')
 def bk(dev):
-    import ctypes
     from gnn_pathplanning_amd import _native
-    _native.lib()
-    # a handle of its own on the same library: the runners' signatures (their own descriptor classes) must not replace
-    # the ones the package has bound on its handle
-    return fc.TorchBackend(to.bind(ctypes.CDLL(_native.LIB_PATH)), dev)
+    return fc.TorchBackend(_native.lib(), dev)
 
 
 def test_gemm_plan_is_the_library_s(bk):

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import golden_state_dict
+from gnn_pathplanning_amd import _native
 from oracle import policy_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -276,8 +277,9 @@ def test_backward_weight_gradient_fork_is_bit_identical(dev, B):
     def run(fork, graphed, merged=0):
         # merged (r06b, GNNPP_TUNE_TRAIN_WGRAD_MERGED, the default): all five weight gradients as ONE launch behind the
         # chain -- the fork rule only applies to the per-layer launches (merged = 0)
-        assert L.gnnpp_set_tuning(18, merged) == 0 and L.gnnpp_get_tuning(18) == merged
-        assert L.gnnpp_set_tuning(15, fork) == 0 and L.gnnpp_get_tuning(15) == fork
+        assert (L.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, merged) == 0
+                and L.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_MERGED) == merged)
+        assert L.gnnpp_set_tuning(_native.TUNE_TRAIN_FORK, fork) == 0 and L.gnnpp_get_tuning(_native.TUNE_TRAIN_FORK) == fork
         net = DecentralPlannerNet(Cfg()).to(dev).train()
         net.load_state_dict(sd0)
         opt = FusedAdam(net.parameters(), lr=1e-3, weight_decay=1e-5)
@@ -302,10 +304,10 @@ def test_backward_weight_gradient_fork_is_bit_identical(dev, B):
             assert all(torch.equal(a, b) for a, b in zip(got[2], ref[2])), (fork, graphed)
             if got[1] is not None:
                 assert all(torch.equal(a, b) for a, b in zip(got[1], ref[1])), (fork, graphed)
-        assert L.gnnpp_set_tuning(15, 3) == -1 and L.gnnpp_set_tuning(18, 2) == -1
+        assert L.gnnpp_set_tuning(_native.TUNE_TRAIN_FORK, 3) == -1 and L.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 2) == -1
     finally:
-        L.gnnpp_set_tuning(15, 1)
-        L.gnnpp_set_tuning(18, 1)
+        L.gnnpp_set_tuning(_native.TUNE_TRAIN_FORK, 1)
+        L.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 1)
 
 
 def test_small_cotangents_keep_relative_accuracy(dev):
@@ -484,7 +486,8 @@ def test_running_statistics_inside_the_last_batchnorm_launch(dev, B, N):
     S = torch.from_numpy(orc.synth_gso_geometric(B, N, 20 if N <= 10 else 50, seed=1)).float().to(dev)
 
     def run(fused, reps):
-        assert L.gnnpp_set_tuning(19, fused) == 0 and L.gnnpp_get_tuning(19) == fused
+        assert (L.gnnpp_set_tuning(_native.TUNE_TRAIN_RUNNING_FUSED, fused) == 0
+                and L.gnnpp_get_tuning(_native.TUNE_TRAIN_RUNNING_FUSED) == fused)
         net = DecentralPlannerNet(C()).to(dev)
         net.load_state_dict(sd0)
         net.train()
@@ -503,7 +506,7 @@ def test_running_statistics_inside_the_last_batchnorm_launch(dev, B, N):
                 assert torch.equal(got[k], ref[k]), k
         one = run(1, 1)
     finally:
-        L.gnnpp_set_tuning(19, 1)
+        L.gnnpp_set_tuning(_native.TUNE_TRAIN_RUNNING_FUSED, 1)
     sd2 = {k: v.clone() for k, v in sd0.items()}
     with torch.no_grad():
         orc.policy_forward(sd2, S.cpu(), obs[0].cpu(), training=True)

@@ -43,16 +43,123 @@ def test_cabi_exports_every_declared_symbol(built_lib):
     # argument validation happens before any HIP call, so it is checkable without a GPU
     assert lib.gnnpp_encoder_fwd(None, None, None, 16, 0, None, None) == -1
     assert lib.gnnpp_version() == 330                        # ABI 300: per-call `precision`; 320: n-way graph split; 330: one-launch training packs, folded masks
-    assert lib.gnnpp_set_tuning(0, 7) == -1 and lib.gnnpp_set_tuning(5, 0) == -1
+    for removed_key, value in ((0, 7), (5, 0)):            # the precision knobs ABI 300 replaced by the per-call argument
+        assert lib.gnnpp_set_tuning(removed_key, value) == -1
     assert lib.gnnpp_decode_actions(None, None, 1, 1, None) == -1
     # gnnpp_lsigf_fits: 1 = the LDS-resident kernels take the graph, 0 = take the dense form (F > 8192 too)
     assert lib.gnnpp_lsigf_fits(10, 128, 128, 3, 1) == 1 and lib.gnnpp_lsigf_fits(100, 128, 8192, 3, 1) == 1
     assert lib.gnnpp_lsigf_fits(10, 128, 8193, 3, 1) == 0 and lib.gnnpp_lsigf_fits(113, 128, 128, 3, 1) == 0
     assert lib.gnnpp_lsigf_fits(0, 128, 128, 3, 1) == -1
     # tuning keys: n-way graph split (v320), the removed MODE 3 value of GNNPP_TUNE_POLICY_FILTER
-    assert lib.gnnpp_set_tuning(7, 7) == 0 and lib.gnnpp_set_tuning(7, 8) == -1 and lib.gnnpp_set_tuning(7, 0) == 0
-    assert lib.gnnpp_set_tuning(9, 2) == -1 and lib.gnnpp_get_tuning(9) == 1
+    assert (lib.gnnpp_set_tuning(built_lib.TUNE_FILTER_SPLIT, 7) == 0
+            and lib.gnnpp_set_tuning(built_lib.TUNE_FILTER_SPLIT, 8) == -1
+            and lib.gnnpp_set_tuning(built_lib.TUNE_FILTER_SPLIT, 0) == 0)
+    assert lib.gnnpp_set_tuning(built_lib.TUNE_POLICY_FILTER, 2) == -1 and lib.gnnpp_get_tuning(built_lib.TUNE_POLICY_FILTER) == 1
 
+
+# ---- the Python statement of the C ABI (_native.SIGNATURES, the struct classes, the constants) against the header ----
+_C_KINDS = {'int': 'int', 'unsigned': 'int', 'size_t': 'size_t', 'long long': 'long long', 'float': 'float',
+            'double': 'double'}
+_CTYPES_KINDS = {ctypes.c_int: 'int', ctypes.c_uint: 'int', ctypes.c_size_t: 'size_t', ctypes.c_longlong: 'long long',
+                 ctypes.c_float: 'float', ctypes.c_double: 'double', ctypes.c_void_p: 'pointer',
+                 ctypes.c_char_p: 'pointer'}
+_STRUCT_CLASSES = {'gnnpp_encoder_params': 'EncoderParams', 'gnnpp_encoder_grads': 'EncoderGrads',
+                   'gnnpp_gemm_desc': 'GemmDesc', 'gnnpp_adam_tensors': 'AdamTensors', 'gnnpp_rollout': 'RolloutStruct',
+                   'gnnpp_schedules': 'ScheduleStruct', 'gnnpp_mapf': 'MapfStruct'}
+
+
+def _c_kind(decl):
+    """Kind of a C type (the declared name already removed): 'pointer' for any pointer, else the scalar's kind."""
+    if '*' in decl:
+        return 'pointer'
+    return _C_KINDS[' '.join(w for w in decl.split() if w != 'const')]
+
+
+def _ctypes_kind(t):
+    if isinstance(t, type) and issubclass(t, ctypes._Pointer):
+        return 'pointer'
+    return _CTYPES_KINDS[t]
+
+
+def _parse_header(text):
+    """(prototypes, structs, defines) of include/gnnpp.h, comments stripped: name -> (return kind, [parameter kinds]);
+    typedef name -> [(field, kind, array length or None)]; NAME -> value of every `#define GNNPP_NAME <integer>`."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    defines = {m.group(1): int(m.group(2)) for m in
+               re.finditer(r'^[ \t]*#define[ \t]+GNNPP_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$', text, flags=re.M)}
+    struct_re = r'typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;'
+    structs = {}
+    for m in re.finditer(struct_re, text, flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(';'))):
+            first, *more = [d.strip() for d in decl.split(',')]                # `int B, N, H, W`: one type, four names
+            ctype, first = re.match(r'(.*?)(\w+(?:\[\d+\])?)$', first).groups()
+            for declarator in [first] + more:
+                name, length = re.match(r'(\w+)(?:\[(\d+)\])?$', declarator).groups()
+                fields.append((name, _c_kind(ctype), int(length) if length else None))
+        structs[m.group(2)] = fields
+    protos = {}
+    for m in re.finditer(r'([\w \t*]+?)\b(gnnpp_\w+)\s*\(([^()]*)\)\s*;', re.sub(struct_re, ' ', text, flags=re.S)):
+        params = [p.strip() for p in m.group(3).split(',')]
+        params = [] if params == ['void'] else [re.sub(r'\w+$', '', p) for p in params]
+        protos[m.group(2)] = (_c_kind(m.group(1)), [_c_kind(p) for p in params])
+    return protos, structs, defines
+
+
+def _abi_mismatches(header, signatures, struct_fields, constants):
+    """Every difference between the parsed header and a Python statement of it, one message each."""
+    protos, structs, defines = header
+    bad = []
+    if set(protos) != set(signatures):
+        bad.append('prototype set: %s' % sorted(set(protos) ^ set(signatures)))
+    for name in sorted(set(protos) & set(signatures)):
+        restype, argtypes = signatures[name]
+        got = (_ctypes_kind(restype), [_ctypes_kind(a) for a in argtypes])
+        if got != protos[name]:
+            bad.append('%s: header %s, table %s' % (name, protos[name], got))
+    if set(structs) != set(struct_fields):
+        bad.append('struct set: %s' % sorted(set(structs) ^ set(struct_fields)))
+    for name in sorted(set(structs) & set(struct_fields)):
+        got = []
+        for field, t in struct_fields[name]:
+            length = t._length_ if issubclass(t, ctypes.Array) else None
+            got.append((field, _ctypes_kind(t._type_ if length else t), length))
+        if got != structs[name]:
+            bad.append('struct %s: header %s, class %s' % (name, structs[name], got))
+    for name, value in sorted(defines.items()):
+        if constants.get(name) != value:
+            bad.append('GNNPP_%s: header %d, _native %r' % (name, value, constants.get(name)))
+    return bad
+
+
+def test_python_abi_matches_header():
+    """include/gnnpp.h is the contract and _native states it once for Python.  Every prototype (return kind and ordered
+    parameter kinds: pointer, int / unsigned, size_t, long long, float, double), every struct (ordered field names, kinds
+    and array lengths) and every integer #define must agree; no library and no compiler needed.  The same comparison
+    must report one c_int turned c_size_t in one call and two swapped struct fields, or it would prove nothing."""
+    from gnn_pathplanning_amd import _native
+    header = _parse_header(open(os.path.join(ROOT, 'include', 'gnnpp.h')).read())
+    protos, structs, defines = header
+    assert len(protos) == 59 and len(structs) == 7 and len(defines) == 46, (len(protos), len(structs), len(defines))
+    assert list(protos) == list(_native.SIGNATURES) and _native.EXPORTS == tuple(_native.SIGNATURES)    # header order
+    assert not set(_native.MEASURE_SIGNATURES) & set(_native.EXPORTS)
+    fields = {c: getattr(_native, py)._fields_ for c, py in _STRUCT_CLASSES.items()}
+    constants = {k: v for k, v in vars(_native).items() if isinstance(v, int)}
+    assert _abi_mismatches(header, _native.SIGNATURES, fields, constants) == []
+
+    restype, argtypes = _native.SIGNATURES['gnnpp_team_lists_gather']
+    assert argtypes[3] is ctypes.c_int
+    wrong = dict(_native.SIGNATURES, gnnpp_team_lists_gather=(restype, argtypes[:3] + [ctypes.c_size_t] + argtypes[4:]))
+    found = _abi_mismatches(header, wrong, fields, constants)
+    assert len(found) == 1 and found[0].startswith('gnnpp_team_lists_gather:'), found
+    f = list(fields['gnnpp_schedules'])
+    i = [name for name, _ in f].index('S')
+    f[i], f[i + 1] = f[i + 1], f[i]                                           # S <-> S64: the same kind, another order
+    found = _abi_mismatches(header, _native.SIGNATURES, dict(fields, gnnpp_schedules=f), constants)
+    assert len(found) == 1 and found[0].startswith('struct gnnpp_schedules:'), found
+    assert _abi_mismatches(header, _native.SIGNATURES, fields, dict(constants, ERR_RANGE=4)) == \
+        ['GNNPP_ERR_RANGE: header -4, _native 4']
 
 def test_unvalidated_toolchain_switches_the_asm_scheduled_layers_off(built_lib, tmp_path, monkeypatch):
     """the column-packed layers rest on hand-placed MFMA wait states; a library built by another hipcc than
@@ -60,7 +167,7 @@ def test_unvalidated_toolchain_switches_the_asm_scheduled_layers_off(built_lib, 
     import warnings
     L = built_lib.lib()
     assert built_lib.built_with() in (None, built_lib.VALIDATED_HIPCC)           # this container IS the validated toolchain
-    assert L.gnnpp_get_tuning(13) == 1 and L.gnnpp_get_tuning(14) == 0
+    assert L.gnnpp_get_tuning(built_lib.TUNE_POLICY_CP) == 1 and L.gnnpp_get_tuning(built_lib.TUNE_ENCODER_CP_TILE) == 0
     stamp = tmp_path / 'toolchain.txt'
     stamp.write_text('HIP version: 9.9.99999-deadbeef\n')
     monkeypatch.setattr(built_lib, 'TOOLCHAIN_STAMP', str(stamp))
@@ -69,13 +176,13 @@ def test_unvalidated_toolchain_switches_the_asm_scheduled_layers_off(built_lib, 
             warnings.simplefilter('always')
             built_lib._apply_toolchain_policy(L)
         assert sum('column-packed' in str(x.message) for x in w) == 1
-        assert L.gnnpp_get_tuning(13) == 0 and L.gnnpp_get_tuning(14) == 16
-        L.gnnpp_set_tuning(13, 1); L.gnnpp_set_tuning(14, 0)
+        assert L.gnnpp_get_tuning(built_lib.TUNE_POLICY_CP) == 0 and L.gnnpp_get_tuning(built_lib.TUNE_ENCODER_CP_TILE) == 16
+        L.gnnpp_set_tuning(built_lib.TUNE_POLICY_CP, 1); L.gnnpp_set_tuning(built_lib.TUNE_ENCODER_CP_TILE, 0)
         monkeypatch.setenv('GNNPP_TRUST_TOOLCHAIN', '1')
         built_lib._apply_toolchain_policy(L)
-        assert L.gnnpp_get_tuning(13) == 1 and L.gnnpp_get_tuning(14) == 0
+        assert L.gnnpp_get_tuning(built_lib.TUNE_POLICY_CP) == 1 and L.gnnpp_get_tuning(built_lib.TUNE_ENCODER_CP_TILE) == 0
     finally:
-        L.gnnpp_set_tuning(13, 1); L.gnnpp_set_tuning(14, 0)
+        L.gnnpp_set_tuning(built_lib.TUNE_POLICY_CP, 1); L.gnnpp_set_tuning(built_lib.TUNE_ENCODER_CP_TILE, 0)
 
 
 def test_split_f16_is_refused_when_its_isa_check_failed(built_lib, tmp_path, monkeypatch):

@@ -19,42 +19,11 @@ import ctypes
 import numpy as np
 
 from f64_yardstick import ULP, gap
+from gnn_pathplanning_amd._native import ERR_ARG, ERR_UNSUPPORTED, AdamTensors, GemmDesc
 
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
 MARGIN = 64                                   # floats on either side of every output (a multiple of 4: 16-byte alignment)
 SENT_BITS = 0x7FC5A5A5                        # a quiet NaN with a payload no arithmetic produces
 SENT = np.array([SENT_BITS], np.uint32).view(np.float32)[0]
-ll, cf = ctypes.c_longlong, ctypes.c_float
-
-
-class GemmDesc(ctypes.Structure):
-    _fields_ = [('A', ctypes.c_void_p), ('a_sb', ll), ('a_sm', ll), ('a_sk', ll), ('B', ctypes.c_void_p), ('b_sb', ll),
-                ('b_sk', ll), ('C', ctypes.c_void_p), ('c_sb', ll), ('c_sm', ll), ('batch', ctypes.c_int),
-                ('M', ctypes.c_int), ('N', ctypes.c_int), ('K', ctypes.c_int), ('mask', ctypes.c_void_p)]
-
-
-class AdamTensors(ctypes.Structure):
-    _fields_ = [('p', ctypes.c_void_p * 32), ('g', ctypes.c_void_p * 32), ('m', ctypes.c_void_p * 32),
-                ('v', ctypes.c_void_p * 32), ('numel', ll * 32), ('count', ctypes.c_int)]
-
-
-def bind(lib):
-    vp, ci, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    lib.gnnpp_gemm_workspace_floats.argtypes = [ci] * 4
-    lib.gnnpp_gemm_workspace_floats.restype = cs
-    lib.gnnpp_gemm_kmajor.argtypes = [vp, ll, ll, ll, vp, ll, ll, vp, ll, ll, ci, ci, ci, ci, vp, vp]
-    lib.gnnpp_gemm_kmajor.restype = ci
-    lib.gnnpp_gemm_multi_workspace_floats.argtypes = [ctypes.POINTER(GemmDesc), ci]
-    lib.gnnpp_gemm_multi_workspace_floats.restype = cs
-    lib.gnnpp_gemm_kmajor_multi.argtypes = [ctypes.POINTER(GemmDesc), ci, vp, vp]
-    lib.gnnpp_gemm_kmajor_multi.restype = ci
-    lib.gnnpp_linear_fwd.argtypes = [vp] * 4 + [ci] * 4 + [vp]
-    lib.gnnpp_linear_fwd.restype = ci
-    lib.gnnpp_policy_loss.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp]
-    lib.gnnpp_policy_loss.restype = ci
-    lib.gnnpp_adam_step.argtypes = [ctypes.POINTER(AdamTensors), vp, cf, cf, cf, cf, cf, ci, vp]
-    lib.gnnpp_adam_step.restype = ci
-    return lib
 
 
 # ---- guarded buffers ---------------------------------------------------------------------------------------------
@@ -628,8 +597,8 @@ def adam_kernel_run(bk, c, p0, m0, v0, grads):
                 tb.p[i - i0], tb.g[i - i0], tb.m[i - i0], tb.v[i - i0] = P[i].ptr, G[i].ptr, M[i].ptr, V[i].ptr
                 tb.numel[i - i0] = p0[i].size
             tb.count = min(count, i0 + 32) - i0
-            assert bk.lib.gnnpp_adam_step(ctypes.byref(tb), state.ptr, cf(LR), cf(betas[0]), cf(betas[1]), cf(c['eps']),
-                                          cf(c['wd']), int(k == 0), bk.stream) == 0, c['name']
+            assert bk.lib.gnnpp_adam_step(ctypes.byref(tb), state.ptr, LR, betas[0], betas[1], c['eps'],
+                                          c['wd'], int(k == 0), bk.stream) == 0, c['name']
             bk.sync()
             stv = state.read(c['name'] + '/state')
             assert stv[0] == c['start'] + s + 1 and stv.view(np.uint32)[3] == 0, (c['name'], s, k, stv)
@@ -680,8 +649,8 @@ def run_adam_errors(bk):
             getattr(tb, null)[1] = None
         tb.numel[1] = numel
         tb.count = count
-        rc = bk.lib.gnnpp_adam_step(ctypes.byref(tb) if table else None, state.ptr if st else None, cf(LR), cf(0.9),
-                                    cf(0.999), cf(1e-8), cf(0.0), 1, bk.stream)
+        rc = bk.lib.gnnpp_adam_step(ctypes.byref(tb) if table else None, state.ptr if st else None, LR, 0.9,
+                                    0.999, 1e-8, 0.0, 1, bk.stream)
         bk.sync()
         return rc
 

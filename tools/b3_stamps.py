@@ -1,7 +1,6 @@
 """Where the time goes INSIDE the policy kernels, per arithmetic (precision 0 = bf16x3 default, 2 = split-f16):
 phase time stamps of the -DGNNPP_MEASURE build (csrc/gnnpp_common.h GNNPP_STAMP: 100 MHz wall clock + shader cycle
 counter), median over the workgroups of one launch.  Prints one JSON line per (kernel, shape, precision)."""
-import ctypes
 import json
 import os
 import sys
@@ -15,7 +14,6 @@ from gnn_pathplanning_amd.decentralplanner import DecentralPlannerNet   # noqa: 
 from oracle import policy_oracle as orc                       # noqa: E402  (inputs only)
 
 M = _native.measure_lib()
-M.gnnpp_measure_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
 dev = torch.device('cuda:0')
 st = _native.stream_ptr(dev)
 
@@ -91,12 +89,12 @@ if 'filter' in which:
         enc, taps, gb, aw, ab, K = net.policy_pointers()
         lg = torch.empty(N, B, 5, device=dev)
         for prec in (0, 1, 2):
-            M.gnnpp_set_tuning(7, split)
+            M.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, split)
             for _ in range(8):
                 assert M.gnnpp_filter_head_fwd(x.data_ptr(), S.data_ptr(), taps, gb, aw, ab, lg.data_ptr(), B, N, 128,
                                                128, 3, 1, 0, prec, None, st) == 0
                 torch.cuda.synchronize()
-            M.gnnpp_set_tuning(7, 0)
+            M.gnnpp_set_tuning(_native.TUNE_FILTER_SPLIT, 0)
             if prec == 2:
                 order = [('entry', 0), ('staged', 1), ('lists', 2), ('tap0', 3), ('barrier1', 4), ('shift1', 5),
                          ('barrier2', 6), ('shift2', 7), ('split1', 8), ('tap1', 9), ('tap2', 12), ('partial', 13),
@@ -120,12 +118,12 @@ if 'small' in which:
         S = torch.from_numpy(orc.synth_gso_geometric(512, N, 20, seed=1337)).float().to(dev).repeat(B // 512, 1, 1).contiguous()
         x = torch.relu(torch.randn(B * N, 128, device=dev))
         y = torch.empty_like(x)
-        M.gnnpp_set_tuning(10, 2)
+        M.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, 2)
         for _ in range(6):
             assert M.gnnpp_lsigf_fwd(x.data_ptr(), S.data_ptr(), taps.data_ptr(), bias.data_ptr(), y.data_ptr(), B, N, N,
                                      128, 128, K, 1, 0, 1, 1, 1, 1, 0, 0, None, st) == 0
             torch.cuda.synchronize()
-        M.gnnpp_set_tuning(10, 1)
+        M.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, 1)
         report('lsigf_small_b3_kernel B=%d N=10 K=3 (%d workgroups; stamps of the first 1024)' % (B, (B + 3) // 4),
                min(1024, (B + 3) // 4),
                [('entry', 0), ('staged', 1), ('tap0', 2), ('barrier', 3), ('shift1', 4), ('tap1', 5), ('barrier', 6),
@@ -141,12 +139,12 @@ if 'pipe' in which:
         S = torch.from_numpy(orc.synth_gso_geometric(512, N, 20, seed=1337)).float().to(dev).repeat(B // 512, 1, 1).contiguous()
         x = torch.relu(torch.randn(B * N, 128, device=dev))
         y = torch.empty_like(x)
-        M.gnnpp_set_tuning(10, 3)
+        M.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, 3)
         for _ in range(6):
             assert M.gnnpp_lsigf_fwd(x.data_ptr(), S.data_ptr(), taps.data_ptr(), bias.data_ptr(), y.data_ptr(), B, N, N,
                                      128, 128, K, 1, 0, 1, 1, 1, 1, 0, 0, None, st) == 0
             torch.cuda.synchronize()
-        M.gnnpp_set_tuning(10, 1)
+        M.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, 1)
         report('lsigf_pipe_b3_kernel B=%d N=10 K=3, a SHIFT stage (tap 0 of the last group): producer start -> shift done | '
                'consumer contraction done | barrier passed' % B, 256,
                [('stage start', 0), ('producer done', 1), ('barrier', 3)])

@@ -3,7 +3,6 @@ agents-on-columns schedule (= 0) on the same inputs: launch time from HIP events
 regions of `reps` back-to-back launches of gnnpp_policy_fwd), bit-identity of the logits, and -- with `stamps` -- the
 phase time stamps of the -DGNNPP_MEASURE build.  One JSON line per shape.
     python tools/cp_ab.py [stamps]"""
-import ctypes
 import json
 import os
 import sys
@@ -45,7 +44,6 @@ def main():
     M = None
     if want_stamps:
         M = _native.measure_lib()
-        M.gnnpp_measure_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
     if 'tiles' in sys.argv[1:]:
         return encoder_tiles(M)
     for (B, N, K) in SHAPES:
@@ -63,7 +61,7 @@ def main():
             lg = torch.full((N, B, 5), float('nan'), device=dev)
             args = (obs.data_ptr(), S.data_ptr(), enc, taps, gb, aw, ab, ws.data_ptr(), lg.data_ptr(), B, N, K, 1, 0, 0,
                     None, st)
-            assert L.gnnpp_set_tuning(6, 2) == 0 and L.gnnpp_set_tuning(13, cp) == 0
+            assert L.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 2) == 0 and L.gnnpp_set_tuning(_native.TUNE_POLICY_CP, cp) == 0
             # (knob 6 = 2: the one-launch kernel whatever the batch size -- the default rule sends B > 512 at N < 13 to
             # the two-kernel path)
             us = time_launches(L, args, 200 if B <= 1024 else 60)
@@ -75,7 +73,7 @@ def main():
         row['M_agent_steps_per_s_cp1'] = round(B * N / min(row['cp1_us']), 2)
         if M is not None and B <= 1024:
             for cp in (0, 1):
-                assert M.gnnpp_set_tuning(13, cp) == 0 and M.gnnpp_set_tuning(6, 2) == 0
+                assert M.gnnpp_set_tuning(_native.TUNE_POLICY_CP, cp) == 0 and M.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 2) == 0
                 lg = torch.empty(N, B, 5, device=dev)
                 args = (obs.data_ptr(), S.data_ptr(), enc, taps, gb, aw, ab, ws.data_ptr(), lg.data_ptr(), B, N, K, 1, 0,
                         0, None, st)
@@ -103,10 +101,10 @@ def main():
                     ph['L1_epilogue'] = round(float(np.median(us_[:, 2] - us_[:, 9])), 2)
                     ph['L2_addr'] = round(float(np.median(us_[:, 15] - us_[:, 2])), 2)
                 row['stamps_cp%d' % cp] = ph
-            M.gnnpp_set_tuning(13, 1)
+            M.gnnpp_set_tuning(_native.TUNE_POLICY_CP, 1)
         print(json.dumps(row), flush=True)
-    L.gnnpp_set_tuning(13, 1)
-    L.gnnpp_set_tuning(6, 1)
+    L.gnnpp_set_tuning(_native.TUNE_POLICY_CP, 1)
+    L.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 1)
 
 
 M = None
@@ -126,7 +124,7 @@ def encoder_tiles(M):
         row = {'encoder_M': Mag}
         ref = None
         for tile in (16, 0, 4, 7, 10, 12):
-            assert L.gnnpp_set_tuning(14, tile) == 0
+            assert L.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, tile) == 0
             args = (obs.data_ptr(), enc.data_ptr(), feat.data_ptr(), Mag, 0, None, st)
             for _ in range(20):
                 assert L.gnnpp_encoder_fwd(*args) == 0
@@ -146,7 +144,7 @@ def encoder_tiles(M):
             else:
                 row['tile%d_bit_identical' % tile] = bool(torch.equal(ref, feat))
             if M is not None:
-                assert M.gnnpp_set_tuning(14, tile) == 0
+                assert M.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, tile) == 0
                 for _ in range(6):
                     assert M.gnnpp_encoder_fwd(*args) == 0
                     torch.cuda.synchronize()
@@ -161,8 +159,8 @@ def encoder_tiles(M):
                 ph['total_median'] = round(float(np.median(us_[:, 6] - us_[:, 11])), 2)
                 ph['span'] = round(float(us_[:, 6].max() - us_[:, 11].min()), 2)
                 row['stamps_tile%d' % tile] = ph
-                M.gnnpp_set_tuning(14, 0)
-        L.gnnpp_set_tuning(14, 0)
+                M.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, 0)
+        L.gnnpp_set_tuning(_native.TUNE_ENCODER_CP_TILE, 0)
         print(json.dumps(row), flush=True)
 
 

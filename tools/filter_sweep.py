@@ -30,7 +30,8 @@ def run(B, mode, reps, rows=0):
     S = S0.repeat((B + 511) // 512, 1, 1)[:B].contiguous()
     x = torch.relu(torch.randn(B * N, 128, generator=torch.Generator().manual_seed(B))).to(dev)
     y = torch.empty_like(x)
-    assert L.gnnpp_set_tuning(10, mode) == 0 and L.gnnpp_set_tuning(11, rows) == 0
+    assert L.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, mode) == 0
+    assert L.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL_ROWS, rows) == 0
     call = lambda: L.gnnpp_lsigf_fwd(x.data_ptr(), S.data_ptr(), taps.data_ptr(), bias.data_ptr(), y.data_ptr(), B, N, N,  # noqa: E731
                                      128, 128, K, 1, 0, 1, 1, 1, 1, 0, 0, None, st)
     for _ in range(5):
@@ -45,8 +46,8 @@ def run(B, mode, reps, rows=0):
         e1.record()
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e-3 / reps)
-    L.gnnpp_set_tuning(10, 1)
-    L.gnnpp_set_tuning(11, 0)
+    L.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL, 1)
+    L.gnnpp_set_tuning(_native.TUNE_FILTER_SMALL_ROWS, 0)
     return sorted(ts)[2], y
 
 
@@ -54,7 +55,7 @@ if len(sys.argv) > 2 and sys.argv[1] == '--pmc-target':
     rows = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     if len(sys.argv) > 4:                                 # access-ablation mask of the pipeline kernel (measure build)
         L = _native.measure_lib()
-        assert L.gnnpp_set_tuning(3, int(sys.argv[4], 0)) == 0
+        assert L.gnnpp_set_tuning(_native.TUNE_FILTER_ABLATE, int(sys.argv[4], 0)) == 0
     run(int(sys.argv[2]), (3 if rows == 64 else 2) if rows else 1, 4, 0 if rows == 64 else rows)
     sys.exit(0)
 if len(sys.argv) > 2 and sys.argv[1] == '--ablate-times':
@@ -64,11 +65,11 @@ if len(sys.argv) > 2 and sys.argv[1] == '--ablate-times':
     L = _native.measure_lib()
     B = int(sys.argv[2])
     for mask in (0, 0x10, 0x20, 0x40, 0x80, 0x100, 0x200, 0x30, 0x70, 0x3f0):
-        assert L.gnnpp_set_tuning(3, mask) == 0
+        assert L.gnnpp_set_tuning(_native.TUNE_FILTER_ABLATE, mask) == 0
         t, _ = run(B, 3, 20)
         print(json.dumps({'batch': B, 'kernel': 'lsigf_pipe_b3_kernel (measure build)', 'ablate_mask': hex(mask),
                           'us': round(t * 1e6, 2)}), flush=True)
-    L.gnnpp_set_tuning(3, 0)
+    L.gnnpp_set_tuning(_native.TUNE_FILTER_ABLATE, 0)
     sys.exit(0)
 for B in (512, 2048, 8192, 32768, 131072):
     ref = None

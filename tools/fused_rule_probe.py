@@ -35,7 +35,7 @@ def main():
         args = (obs.data_ptr(), S.data_ptr(), enc, taps, gb, aw, ab, ws.data_ptr(), lg.data_ptr(), B, N, K, 1, 0, 0, None, st)
         row = {'B': B, 'N': N}
         for knob, name in ((0, 'two_kernels_us'), (2, 'one_launch_us'), (1, 'default_rule_us')):
-            assert L.gnnpp_set_tuning(6, knob) == 0
+            assert L.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, knob) == 0
             for _ in range(10):
                 assert L.gnnpp_policy_fwd(*args) == 0
             ts = []
@@ -49,7 +49,7 @@ def main():
                 torch.cuda.synchronize()
                 ts.append(e0.elapsed_time(e1) * 10.0)
             row[name] = round(sorted(ts)[2], 2)
-        L.gnnpp_set_tuning(6, 1)
+        L.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 1)
         row['M_agent_steps_per_s_best'] = round(B * N / min(row['two_kernels_us'], row['one_launch_us']), 1)
         print(json.dumps(row), flush=True)
 

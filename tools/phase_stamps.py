@@ -16,7 +16,6 @@ from gnn_pathplanning_amd.rollout import BatchedRollout       # noqa: E402
 from oracle import policy_oracle as orc                       # noqa: E402  (inputs only)
 
 M = _native.measure_lib()
-M.gnnpp_measure_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
 dev = torch.device('cuda:0')
 SLOTS = {'move:entry': 0, 'move:state_loaded': 1, 'move:proposed': 2, 'move:pass1': 3, 'move:passes': 4,
          'move:final_pass': 5, 'move:stored': 6, 'sim:move_done': 7, 'sim:gso_done': 8, 'sim:observe_done': 9,   # gso_done = graph built + goal cells marked
@@ -74,8 +73,6 @@ for (N, B, W) in ((10, 512, 20), (16, 512, 20), (100, 128, 100)):
         continue
     ptrs = net.policy_pointers()
     enc, taps, gb, aw, ab, K = ptrs
-    M.gnnpp_rollout_policy_step.argtypes = [ctypes.POINTER(_native.RolloutStruct)] + [ctypes.c_void_p] * 5 + \
-        [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     for _ in range(3):
         r.currentstep += 1
         assert M.gnnpp_rollout_policy_step(ctypes.byref(r), enc, taps, gb, aw, ab, K, 0, st_ptr) == 0
@@ -91,7 +88,6 @@ class Cfg2:
     num_agents, nGraphFilterTaps, device = 10, 3, dev
 net = DecentralPlannerNet(Cfg2()).to(dev).eval()
 net.load_state_dict(orc.init_state_dict(3))
-M.gnnpp_policy_fwd.argtypes = [ctypes.c_void_p] * 9 + [ctypes.c_int] * 6 + [ctypes.c_void_p, ctypes.c_void_p]
 SLOTS.update({'enc:staged': 0, 'enc:L0': 1, 'enc:L1': 2, 'enc:L2': 3, 'enc:L3': 4, 'enc:L4': 5, 'enc:FC(z0)': 12,
               'filter:shifts': 13, 'filter:contraction': 14})
 N = 10

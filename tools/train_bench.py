@@ -166,11 +166,11 @@ def main():
     from gnn_pathplanning_amd.sharding import gather_rank_devices
     from gnn_pathplanning_amd import _native
     if args.wgrad_per_layer:
-        assert _native.lib().gnnpp_set_tuning(18, 0) == 0
+        assert _native.lib().gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 0) == 0
     if args.wgrad_wgs:
-        assert _native.lib().gnnpp_set_tuning(17, args.wgrad_wgs) == 0
+        assert _native.lib().gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_WGS, args.wgrad_wgs) == 0
     if args.no_fork or args.fork:
-        assert _native.lib().gnnpp_set_tuning(15, 0 if args.no_fork else 2) == 0
+        assert _native.lib().gnnpp_set_tuning(_native.TUNE_TRAIN_FORK, 0 if args.no_fork else 2) == 0
     B, N = args.batch, 10
     per_step, loss = measure(dev, B, args.steps, args.warmup, args.graph, args.adam, rank, world)
     rank_devices = gather_rank_devices(dev)
@@ -181,8 +181,9 @@ def main():
                 'backend': dist.get_backend() if world > 1 else None,
                 'batch_per_gpu': B, 'ms_per_step': 1e3 * per_step,
                 'final_loss': loss, 'hip_graph': bool(args.graph), 'adam': args.adam,
-                'wgrad_wgs': _native.lib().gnnpp_get_tuning(17), 'wgrad_merged': _native.lib().gnnpp_get_tuning(18),
-                'backward_fork_knob': _native.lib().gnnpp_get_tuning(15)}
+                'wgrad_wgs': _native.lib().gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS),
+                'wgrad_merged': _native.lib().gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_MERGED),
+                'backward_fork_knob': _native.lib().gnnpp_get_tuning(_native.TUNE_TRAIN_FORK)}
         if args.cpu_seconds > 0 and world == 1:
             cb = cpu_baseline(B, args.cpu_seconds)
             cb['speedup_gpu_over_cpu'] = line['value'] / cb['value']

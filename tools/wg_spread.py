@@ -1,5 +1,5 @@
 """Per-workgroup start / duration structure of one launch of the fused policy kernel (measure build stamps)."""
-import ctypes, json, os, sys
+import json, os, sys
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -7,7 +7,6 @@ from gnn_pathplanning_amd import _native
 from gnn_pathplanning_amd.decentralplanner import DecentralPlannerNet
 from oracle import policy_oracle as orc
 M = _native.measure_lib()
-M.gnnpp_measure_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
 dev = torch.device('cuda:0'); st = _native.stream_ptr(dev)
 class Cfg2:
     num_agents, nGraphFilterTaps, device = 10, 3, dev

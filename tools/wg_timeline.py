@@ -1,7 +1,6 @@
 """When do the workgroups of one C2 launch of the one-launch policy kernel start and end?  (measure build, stamps 11 = entry,
 14 = last phase done.)  Prints percentiles of start / end times relative to the earliest start, for the first and second
 half of the grid (the second half takes the CUs' second slots)."""
-import ctypes
 import json
 import os
 import sys
@@ -17,7 +16,6 @@ from oracle import policy_oracle as orc                       # noqa: E402  (inp
 dev = torch.device('cuda:0')
 st = _native.stream_ptr(dev)
 M = _native.measure_lib()
-M.gnnpp_measure_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
 for (B, N, K) in [(512, 10, 3), (256, 10, 3), (1024, 10, 3)]:
     class Cfg:
         num_agents, nGraphFilterTaps, device = N, K, dev
@@ -28,7 +26,7 @@ for (B, N, K) in [(512, 10, 3), (256, 10, 3), (1024, 10, 3)]:
     enc, taps, gb, aw, ab, _ = net.policy_pointers()
     ws = torch.empty(B * N, 128, device=dev)
     lg = torch.empty(N, B, 5, device=dev)
-    assert M.gnnpp_set_tuning(6, 2) == 0
+    assert M.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 2) == 0
     args = (obs.data_ptr(), S.data_ptr(), enc, taps, gb, aw, ab, ws.data_ptr(), lg.data_ptr(), B, N, K, 1, 0, 0, None, st)
     for _ in range(8):
         assert M.gnnpp_policy_fwd(*args) == 0
@@ -46,4 +44,4 @@ for (B, N, K) in [(512, 10, 3), (256, 10, 3), (1024, 10, 3)]:
         rec['first_half'] = {'start': pct(start[:h]), 'end': pct(end[:h]), 'duration': pct((end - start)[:h])}
         rec['second_half'] = {'start': pct(start[h:]), 'end': pct(end[h:]), 'duration': pct((end - start)[h:])}
     print(json.dumps(rec), flush=True)
-M.gnnpp_set_tuning(6, 1)
+M.gnnpp_set_tuning(_native.TUNE_FUSED_POLICY, 1)
