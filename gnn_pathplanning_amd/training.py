@@ -209,7 +209,12 @@ class GraphedTrainStep:
 
     dp (FlatBucketDP): the one flat-bucket gradient all-reduce is enqueued on the capture stream between
     backward and the optimizer like every other launch, so RCCL's collective becomes a node of the graph
-    (RCCL, like NCCL, supports stream capture); every rank must build and replay its graph in step."""
+    (RCCL, like NCCL, supports stream capture); every rank must build and replay its graph in step.
+
+    The graph holds ADDRESSES: of the parameters, the running statistics, the gradients and the optimizer's state.
+    model.load_state_dict() copies into the parameters and is seen by the next replay; optimizer.load_state_dict()
+    REPLACES the state tensors, so a checkpoint's optimizer state goes through load_optimizer_state(), which copies
+    into the tensors the graph reads.  After a replay `p.grad` is whatever the last EAGER step left."""
 
     def __init__(self, model, optimizer, batch_input, batch_target, batch_GSO, warmup=3, dp=None):
         self.inp = batch_input.clone()
@@ -221,9 +226,23 @@ class GraphedTrainStep:
             for _ in range(warmup):                                 # warm allocator, packs, MIOpen
                 train_step(model, optimizer, self.inp, self.tgt, self.gso, dp)
         torch.cuda.current_stream().wait_stream(side)
+        self.optimizer = optimizer
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss = train_step(model, optimizer, self.inp, self.tgt, self.gso, dp)
+
+    def load_optimizer_state(self, state_dict):
+        """optimizer.load_state_dict(state_dict) for the captured step: the loaded values are copied INTO the state
+        tensors whose addresses the graph holds (same parameters, same groups; hyperparameters are baked into the
+        graph and are not touched)."""
+        own = self.optimizer.state_dict()['state']                 # (references to the live state tensors)
+        if set(own) != set(state_dict['state']):
+            raise ValueError('load_optimizer_state: the state dict holds other entries than the captured optimizer')
+        with torch.no_grad():
+            for k, entry in state_dict['state'].items():
+                for name, v in entry.items():
+                    if torch.is_tensor(own[k].get(name)):
+                        own[k][name].copy_(v)
 
     def __call__(self, batch_input, batch_target, batch_GSO):
         self.inp.copy_(batch_input)
