@@ -892,24 +892,47 @@ __global__ __launch_bounds__(256) void rollout_gso_observe_kernel(const RolloutA
 }
 
 // ---- launchers -----------------------------------------------------------------------------------
+// Every one-wave call serves maps of up to kOneWaveMaxCells cells (include/gnnpp.h, "Map sizes"; the occupancy grid is one
+// byte per cell of LDS, rounded up to 16), whatever the team size.  The largest maps ask for more dynamic LDS than the
+// 64 KB a kernel gets by default, so each launcher raises its kernel's limit once per device (set_lds_attr_once) -- to
+// the FIXED largest request it can compute for an accepted map, never to the call's own size: the attribute is set on
+// the first call only, and a small map first would pin a small limit.
+//   observe, gso_observe   goal_l + occ                                  1 024 + 65 536          = 66 560
+//   step                   spos/red/goal_l + graph + occ + cell map      7 200 + 65 536 (+ 0)    = 72 736
+//                          (a cell map exists up to kCellMapMaxCells = half the limit, where occ + map = 65 536 again)
+//   move                   red + cell map                                2 048 + 32 768          = 34 816
+// The `staged` decisions below stay at the 64 KB line: the stage is a speed choice (same bytes out), and a request
+// that includes it never exceeds 64 KB.
+constexpr size_t kOneWaveMaxCells = 64 * 1024;
+constexpr size_t kObserveMaxSmem = 2 * kMaxAgents * sizeof(int) + kOneWaveMaxCells;
+constexpr size_t kStepMaxSmem = 8 * kMaxAgents * sizeof(int) + kGsoSmemBytes + kOneWaveMaxCells;
+constexpr size_t kMoveMaxSmem = 4 * kMaxAgents * sizeof(int) + kCellMapMaxCells;
+static_assert(kOneWaveMaxCells % 16 == 0 && 2 * kCellMapMaxCells <= kOneWaveMaxCells, "occ + cell map <= the map limit");
+static_assert(kObserveMaxSmem >= 64 * 1024 && kObserveMaxSmem >= (size_t)kGsoSmemBytes && kStepMaxSmem >= 64 * 1024 &&
+              kStepMaxSmem <= (size_t)kLdsBytes, "one-wave simulator LDS");
+
 int rollout_gso_observe_launch(const RolloutArgs& a, hipStream_t st) {
     const size_t occ = ((size_t)a.H * a.W + 15) & ~(size_t)15;
-    if (occ > 64 * 1024) return -2;
+    if (occ > kOneWaveMaxCells) return -2;
     size_t smem = occ + 2 * kMaxAgents * sizeof(int);
     const int staged = smem + kObsStageBytes <= 64 * 1024;      // the output stage, while the default LDS limit allows
     if (staged) smem += kObsStageBytes;
     if (smem < (size_t)kGsoSmemBytes) smem = kGsoSmemBytes;
     const int groups = (a.N + kObsAgentsPerWg - 1) / kObsAgentsPerWg;
+    static LdsAttrOnce once;
+    set_lds_attr_once(once, reinterpret_cast<const void*>(&rollout_gso_observe_kernel), (int)kObserveMaxSmem);
     hipLaunchKernelGGL(rollout_gso_observe_kernel, dim3(a.B * (groups + 1)), dim3(256), smem, st, a, groups, staged);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 int rollout_observe_launch(const RolloutArgs& a, hipStream_t st) {
     const size_t occ = ((size_t)a.H * a.W + 15) & ~(size_t)15;
-    if (occ > 64 * 1024) return -2;
+    if (occ > kOneWaveMaxCells) return -2;
     size_t smem = occ + 2 * kMaxAgents * sizeof(int);
     const int staged = smem + kObsStageBytes <= 64 * 1024;
     if (staged) smem += kObsStageBytes;
+    static LdsAttrOnce once;
+    set_lds_attr_once(once, reinterpret_cast<const void*>(&rollout_observe_kernel), (int)kObserveMaxSmem);
     hipLaunchKernelGGL(rollout_observe_kernel,
                        dim3((a.N + kObsAgentsPerWg - 1) / kObsAgentsPerWg, a.B), dim3(256), smem, st,
                        a, staged);
@@ -923,6 +946,8 @@ int rollout_gso_launch(const RolloutArgs& a, hipStream_t st) {
 }
 
 int rollout_move_launch(const RolloutArgs& a, hipStream_t st) {
+    static LdsAttrOnce once;                             // (below 64 KB: set for symmetry with the other launchers)
+    set_lds_attr_once(once, reinterpret_cast<const void*>(&rollout_move_kernel), (int)kMoveMaxSmem);
     hipLaunchKernelGGL(rollout_move_kernel, dim3(a.B), dim3(64),
                        4 * kMaxAgents * sizeof(int) + cell_map_bytes(a.N, a.H, a.W), st, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
@@ -930,12 +955,14 @@ int rollout_move_launch(const RolloutArgs& a, hipStream_t st) {
 
 int rollout_step_launch(const RolloutArgs& a, hipStream_t st) {
     const size_t occ = ((size_t)a.H * a.W + 15) & ~(size_t)15;
-    if (occ > 64 * 1024) return -2;
+    if (occ > kOneWaveMaxCells) return -2;
     size_t smem = 8 * kMaxAgents * sizeof(int) + kGsoSmemBytes + occ + cell_map_bytes(a.N, a.H, a.W);
     const size_t stage_bytes = (size_t)a.N * 363 * sizeof(float);
     const int staged = smem + stage_bytes <= 64 * 1024;  // the observations' output stage, while the LDS limit allows
     if (staged) smem += stage_bytes;
     const int nt = a.N > 32 ? 1024 : 256;               // enough threads for N * 363 observation cells
+    static LdsAttrOnce once;
+    set_lds_attr_once(once, reinterpret_cast<const void*>(&rollout_step_kernel), (int)kStepMaxSmem);
     hipLaunchKernelGGL(rollout_step_kernel, dim3(a.B), dim3(nt), smem, st, a, staged);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

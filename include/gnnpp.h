@@ -540,7 +540,14 @@ int gnnpp_lsigf_team_lists_input_grad(const float* dy, const void* lists_t, cons
  * one thread per agent per episode for move and gso; step and gso_observe enqueue the separate launches), with the
  * same results.  Those need H * W <= GNNPP_ROLLOUT_TEAM_MAX_CELLS (the occupancy maps live in LDS); a larger map
  * returns GNNPP_ERR_UNSUPPORTED with nothing enqueued.  N > GNNPP_ROLLOUT_MAX_TEAM: GNNPP_ERR_ARG.  (v330: the
- * large-team range widens what the existing entry points accept and adds no symbol.) */
+ * large-team range widens what the existing entry points accept and adds no symbol.)
+ * Map sizes.  The one-wave calls keep the occupancy grid in LDS too, one byte per cell: observe / gso_observe / step
+ * serve every map with H * W rounded up to 16 <= 65 536 cells (the same count as GNNPP_ROLLOUT_TEAM_MAX_CELLS; 256 x 256
+ * is the largest square) at every team size, and answer GNNPP_ERR_UNSUPPORTED with nothing enqueued beyond it.  Up to
+ * that limit no accepted call answers GNNPP_ERR_LAUNCH for its LDS: the launchers raise their kernels' dynamic LDS
+ * limit above the default 64 KB (66 560 bytes for observe / gso_observe, 72 736 for step).  gnnpp_rollout_move and
+ * gnnpp_rollout_gso have no map limit of their own (move reads the map from memory; cells are compared as
+ * row * 65 536 + column, so H, W <= 32 767), and gnnpp_rollout_policy_step(s) has a smaller one, stated below. */
 #define GNNPP_ROLLOUT_MAX_AGENTS 128
 #define GNNPP_ROLLOUT_MAX_TEAM 1024
 #define GNNPP_ROLLOUT_TEAM_MAX_CELLS 65536
