@@ -47,8 +47,8 @@ MAX_NODES, MAX_ROWS = 100, 112
 # GNNPP_TUNE_*: keys of gnnpp_set_tuning / gnnpp_get_tuning
 TUNE_FILTER_GPW, TUNE_FILTER_WAVES, TUNE_FUSED_POLICY, TUNE_FILTER_SPLIT, TUNE_POLICY_FILTER = 1, 2, 6, 7, 9
 TUNE_FILTER_SMALL, TUNE_FILTER_SMALL_ROWS, TUNE_FILTER_PIPE_GRID = 10, 11, 12
-TUNE_POLICY_CP, TUNE_ENCODER_CP_TILE, TUNE_TRAIN_FORK, TUNE_FILTER_PLANE_ALIAS = 13, 14, 15, 16
-TUNE_TRAIN_WGRAD_WGS, TUNE_TRAIN_WGRAD_MERGED, TUNE_TRAIN_RUNNING_FUSED, TUNE_ENCODER_ONE_PLANE = 17, 18, 19, 20
+TUNE_POLICY_CP, TUNE_ENCODER_CP_TILE, TUNE_FILTER_PLANE_ALIAS = 13, 14, 16        # (15 and 18: removed, not reused)
+TUNE_TRAIN_WGRAD_WGS, TUNE_TRAIN_RUNNING_FUSED, TUNE_ENCODER_ONE_PLANE = 17, 19, 20
 ROLLOUT_MAX_AGENTS, ROLLOUT_MAX_TEAM, ROLLOUT_TEAM_MAX_CELLS = 128, 1024, 65536
 TIE_LOWEST, TIE_HASHED, TIE_REPLAY, TIE_MT19937 = 0, 1, 2, 3
 SCHEDULE_BAD_MOVE, SCHEDULE_BAD_STATE, SCHEDULE_NO_RADIUS = 1, 2, 4

@@ -569,10 +569,8 @@ int gnnpp_get_tuning(int key) {
         case GNNPP_TUNE_FILTER_PIPE_GRID: return g_filter_pipe_grid.load();
         case GNNPP_TUNE_POLICY_CP: return g_policy_column_packing.load();
         case GNNPP_TUNE_ENCODER_CP_TILE: return g_encoder_cp_tile.load();
-        case GNNPP_TUNE_TRAIN_FORK: return g_train_fork.load();
         case GNNPP_TUNE_FILTER_PLANE_ALIAS: return g_filter_plane_alias.load();
         case GNNPP_TUNE_TRAIN_WGRAD_WGS: return g_train_wgrad_wgs.load();
-        case GNNPP_TUNE_TRAIN_WGRAD_MERGED: return g_train_wgrad_merged.load();
         case GNNPP_TUNE_TRAIN_RUNNING_FUSED: return g_train_running_fused.load();
         case GNNPP_TUNE_ENCODER_ONE_PLANE: return g_encoder_one_plane.load();
 #ifdef GNNPP_MEASURE
@@ -621,17 +619,9 @@ int gnnpp_set_tuning(int key, int value) {
             if (value != 0 && value != 16 && (value < 1 || value > 12)) return GNNPP_ERR_ARG;
             g_encoder_cp_tile.store(value);
             return GNNPP_OK;
-        case GNNPP_TUNE_TRAIN_FORK:
-            if (value < 0 || value > 2) return GNNPP_ERR_ARG;
-            g_train_fork.store(value);
-            return GNNPP_OK;
         case GNNPP_TUNE_FILTER_PLANE_ALIAS:
             if (value < 0 || value > 1) return GNNPP_ERR_ARG;
             g_filter_plane_alias.store(value);
-            return GNNPP_OK;
-        case GNNPP_TUNE_TRAIN_WGRAD_MERGED:
-            if (value < 0 || value > 1) return GNNPP_ERR_ARG;
-            g_train_wgrad_merged.store(value);
             return GNNPP_OK;
         case GNNPP_TUNE_TRAIN_RUNNING_FUSED:
             if (value < 0 || value > 1) return GNNPP_ERR_ARG;

@@ -24,21 +24,20 @@
 //                             the running statistics) in the workgroup's prologue, then
 //                             x_{l+1} = maxpool2x2?( relu( (y - mean) * invstd * gamma + beta ) )
 //   then bn_running_kernel    the N sequential momentum updates of every layer's running statistics
-//   backward, per layer from the last to the first
+//   backward, per layer from the last to the first (every layer keeps its dy in a buffer of its own)
 //     bn_bwd_reduce_kernel    dz = relu'(a) * unpool(d x_{l+1})  (a and the pool's arg-max recomputed from y:
 //                             first maximum in scan order, as torch's max_pool2d backward), written out,
 //                             with per-wave partial sums of dz and dz * yhat
 //     bn_bwd_apply_kernel     partials -> per (agent, channel) coefficients in the workgroup's prologue, then
 //                             dy = gamma * invstd * (dz - mean(dz) - yhat * mean(dz * yhat)), in place
-//     (after the first layer: ONE conv_wgrad_reduce_kernel launch sums the splits of all five layers, and d gamma / d beta)
-//     conv_wgrad_kernel       dW[co][ci][tap] (and d bias) = sum over all columns of dy x patch(x): a GEMM with
-//                             the columns as the contraction index, on the fp32 MFMA 16x16x4, operands staged
-//                             through LDS, split over image ranges; conv_wgrad_reduce_kernel sums the splits in order
 //     conv_mfma_kernel        dx = conv3x3(dy) with the transposed, flipped kernel (skipped for layer 0)
+//   then, behind the chain, one launch each for all five layers
+//     conv_wgrad_all_kernel   dW[co][ci][tap] (and d bias) = sum over all columns of dy x patch(x): a GEMM with
+//                             the columns as the contraction index, on the fp32 MFMA 16x16x4, operands staged
+//                             through LDS, split over image ranges
+//     conv_wgrad_reduce_kernel  sums the splits in order, and d gamma / d beta from bn_bwd_apply_kernel's per-agent sums
 // The 128 -> 128 compress MLP, the graph filter and the action head are not in here: the MLP is one library
 // GEMM each way (torch), the graph filter runs on lsigf_kernel (graphML._LSIGFFunction).
-#include <mutex>
-
 #include "gnnpp_common.h"
 
 namespace gnnpp {
@@ -669,7 +668,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 // pass 2: dz -> dy in place,  dy = k1 * (dz - k2 - yhat * k3),  k1 = gamma * invstd, k2 = mean(dz),
 // k3 = mean(dz * yhat) over the m = B * P values of (agent, channel).  Same workgroup shape as
 // bn_relu_pool_kernel: the workgroup sums pass 1's partial pairs of its channels itself; the workgroups of the
-// first image range leave the per-agent sums in pn[(n*C + c)*2] for bn_bwd_dparam_kernel.
+// first image range leave the per-agent sums in pn[(n*C + c)*2] for conv_wgrad_reduce_kernel (d gamma, d beta).
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ y,
                                                            const float* __restrict__ stat,
                                                            const float* __restrict__ part,
@@ -708,30 +707,12 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
-// d gamma[c] = sum_n sum(dz * yhat), d beta[c] = sum_n sum(dz): agents in order, one thread per channel;
-// all five layers in one launch at the end of the backward pass (blockIdx.y = layer; a = pn of the layer,
-// b = d gamma, c = d beta)
-__global__ void bn_bwd_dparam_kernel(const TrainPtrs5 p, int N) {
-    const int l = blockIdx.y;
-    const int C = train_layer(l).Cout;
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const float* pn = p.a[l];
-    double tb = 0.0, tg = 0.0;
-    for (int n = 0; n < N; ++n) {
-        tb += (double)pn[((long)n * C + c) * 2];
-        tg += (double)pn[((long)n * C + c) * 2 + 1];
-    }
-    p.b[l][c] = (float)tg;
-    p.c[l][c] = (float)tb;
-}
-
 // ---- weight gradient: dW[co][j], j = ci*9 + tap (j = Cin*9: the bias column) -------------------------------
 //   dW[co][j] = sum over columns (n, b, p) of dy[n,b,co,p] * X[j][(n,b,p)],  X = x[n,b,ci,p + off(tap)] or 1
 // A GEMM with the columns as the contraction index on v_mfma_f32_16x16x4_f32 (A[i][k] = dy[co0+i][col k],
 // B[k][j] = X[j0+j][col k], four columns per MFMA), operands staged through LDS:
-//   grid = (Cout / 16, splits), block = 256.  A workgroup owns one tile of 16 output channels and a range of
-//   images, which it walks IB images at a time: the raw x images go to LDS once, ZERO-BORDERED
+//   block = 256.  A workgroup owns one tile of 16 output channels (bx) and a range of images (split by), which
+//   it walks IB images at a time: the raw x images go to LDS once, ZERO-BORDERED
 //   ([ci][img][(H+2)*(W+2)]), so the im2col operand of ANY (ci, tap) is the same per-lane position offset plus
 //   a per-j constant -- no bounds tests, no address arithmetic in the loop; dy goes to LDS as [16][img][P
 //   rounded up to 4] (zero tail: a short last step contributes nothing).  Global reads are contiguous runs
@@ -739,10 +720,16 @@ __global__ void bn_bwd_dparam_kernel(const TrainPtrs5 p, int N) {
 //   Wave w holds the accumulators of j tiles  (w % JW) + JW*t, t < TJ  at once: one A read feeds TJ MFMAs.
 //   KW > 1 (layer 0: only two j tiles): the waves also split the images of a batch KW ways, each K group
 //   writing its own partial.  Partials -> wpart[split*KW + kgroup][Cout][J16], summed by conv_wgrad_reduce_kernel.
+//   A __device__ body: conv_wgrad_all_kernel runs the workgroups of all five layers in ONE launch.
 __host__ __device__ constexpr int wgrad_ib(int H) { return H == 11 ? 4 : H == 5 ? 6 : 8; }   // images per LDS batch
+// LDS of a workgroup of layer l (xs [Cin][RS] + dys [16][dstride] of conv_wgrad_body), bytes; <= 64 KB
+inline size_t wgrad_smem_bytes(int l) {
+    const TrainLayerDims d = train_layer(l);
+    const int P = d.H * d.W, PP = (d.H + 2) * (d.W + 2), P4 = (P + 3) / 4 * 4;
+    const int IB = wgrad_ib(d.H), dstride = ((IB * P4 + 63) / 64) * 64 + 4;
+    return ((size_t)d.Cin * ((IB * PP) | 1) + 16 * (size_t)dstride) * sizeof(float);
+}
 
-// (a __device__ body: one layer per launch -- conv_wgrad_kernel -- or all five layers in ONE launch --
-// conv_wgrad_all_kernel; bx = output-channel tile, by = image split of the workgroup)
 template <int H, int W, int Cin, int TJ, int KW>
 __device__ __forceinline__ void conv_wgrad_body(const float* __restrict__ x, const float* __restrict__ dy,
                                                 float* __restrict__ wpart, int NB, int Cout, long x_sn, long x_sb,
@@ -889,20 +876,13 @@ __device__ __forceinline__ void conv_wgrad_body(const float* __restrict__ x, con
     }
 }
 
-template <int H, int W, int Cin, int TJ, int KW>
-__global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict__ x,
-                                                         const float* __restrict__ dy,
-                                                         float* __restrict__ wpart, int NB, int Cout,
-                                                         long x_sn, long x_sb, int B, int imgs_per_split, int JT) {
-    conv_wgrad_body<H, W, Cin, TJ, KW>(x, dy, wpart, NB, Cout, x_sn, x_sb, B, imgs_per_split, JT, blockIdx.x, blockIdx.y);
-}
-
 // The weight gradients of ALL five layers in one launch (r06b).  Nothing downstream of a layer's weight gradient is
-// needed before the optimizer, and at the reference's batch (64 x 10) each per-layer launch is ~256 workgroups of 9 .. 19 us
+// needed before the optimizer, and at the reference's batch (64 x 10) a launch per layer is ~256 workgroups of 9 .. 19 us
 // of latency that fill a fraction of the chip: run one after the other inside the backward chain they cost 65 us, the fp32
-// MFMAs of all five together are 14 us of the pipe.  So the backward chain only runs R -> A -> D per layer (every layer
-// keeps its dy in a buffer of its own) and the five weight gradients run as ONE grid behind it: workgroup w belongs to
-// layer l with first[l] <= w < first[l + 1], its (output-channel tile, image split) = ((w - first[l]) % nx[l], / nx[l]).
+// MFMAs of all five together are 14 us of the pipe.  So the backward chain only runs R (bn_bwd_reduce) -> A (bn_bwd_apply)
+// -> D (input gradient) per layer (every layer keeps its dy in a buffer of its own) and the five weight gradients run as
+// ONE grid behind it: the workgroups of slot sl are first[sl] <= w < first[sl + 1], layer l = order[sl], (output-channel
+// tile, image split) = ((w - first[sl]) % nx[l], / nx[l]).
 struct WgradAllTable {
     const float* x[kTrainLayers];
     const float* dy[kTrainLayers];
@@ -1005,8 +985,8 @@ struct TrainWs {
     size_t y[kTrainLayers], xn[kTrainLayers], stat[kTrainLayers], wt[kTrainLayers], wtb[kTrainLayers];
     size_t part, dz[kTrainLayers], dxa, dxb, coef, wpart[kTrainLayers], tick, total;
     int chunks[kTrainLayers];
-    // conv_wgrad_kernel: image splits, images per split, images per LDS batch, j tiles, K groups per workgroup
-    int nsplit[kTrainLayers], ips[kTrainLayers], ib[kTrainLayers], jt[kTrainLayers], kw[kTrainLayers];
+    // conv_wgrad_body: image splits, images per split, j tiles, K groups per workgroup
+    int nsplit[kTrainLayers], ips[kTrainLayers], jt[kTrainLayers], kw[kTrainLayers];
 };
 
 // GNNPP_TUNE_TRAIN_WGRAD_WGS: workgroups per layer of the weight-gradient kernel (image splits x output-channel tiles).
@@ -1014,7 +994,7 @@ struct TrainWs {
 // batch: 128 up to 1 280 agent-samples, 256 beyond -- with the five layers in ONE launch the parallelism comes from
 // the layers (r06b, graphed step, `profiles/r06_train_wgrad_sweep.jsonl`: 64 x 10: 64: 0.370, 96: 0.358, 128: 0.350,
 // 192: 0.354, 256: 0.359, 320: 0.363, 448: 0.373 ms; 512 x 10: 128: 1.335, 256: 1.317, 512: 1.332, 1024: 1.377 ms;
-// per-layer launches, r06a: 256 was best at 64 x 10).  Set it BEFORE a forward call: the workspace size depends on it.
+// one launch per layer, r06a: 256 was best at 64 x 10).  Set it BEFORE a forward call: the workspace size depends on it.
 std::atomic<int> g_train_wgrad_wgs{0};
 std::atomic<int> g_train_running_fused{1};      // GNNPP_TUNE_TRAIN_RUNNING_FUSED
 
@@ -1043,7 +1023,7 @@ inline TrainWs train_ws_layout(int N, int B) {
         const size_t pp = (size_t)N * cmax * d.Cout * 2;
         max_part = max_part > pp ? max_part : pp;
         max_x = max_x > NB * d.Cin * P ? max_x : NB * d.Cin * P;
-        // weight-gradient splits: ~320 workgroups per layer (one per 16 output channels and image range)
+        // weight-gradient splits: GNNPP_TUNE_TRAIN_WGRAD_WGS workgroups per layer (one per 16 output channels and image range)
         w.jt[l] = (d.Cin * 9 + 1 + 15) / 16;
         w.kw[l] = w.jt[l] <= 2 ? 2 : 1;
         const int knob = g_train_wgrad_wgs.load(std::memory_order_relaxed);
@@ -1052,7 +1032,6 @@ inline TrainWs train_ws_layout(int N, int B) {
         if ((size_t)ns > NB) ns = (int)NB;
         w.ips[l] = (int)((NB + ns - 1) / ns);
         w.nsplit[l] = (int)((NB + w.ips[l] - 1) / w.ips[l]);
-        w.ib[l] = wgrad_ib(d.H);                           // LDS: [Cin][IB][(H+2)(W+2)] + [16][IB*P4] floats <= 64 KB
         wp[l] = (size_t)w.nsplit[l] * w.kw[l] * d.Cout * w.jt[l] * 16;
     }
     w.part = take(max_part);
@@ -1092,22 +1071,6 @@ static void conv_launch(int l, bool input_grad, const float* x, const float* wpa
     else if (g.H == 5) GNNPP_CONV(5, 5);
     else GNNPP_CONV(1, 1);
 #undef GNNPP_CONV
-}
-
-static void wgrad_launch(int l, const TrainWs& L, const float* x, const float* dy, float* wpart, int NB, long sn,
-                         long sb, int B, hipStream_t st) {
-    const TrainLayerDims d = train_layer(l);
-    const int P = d.H * d.W, PP = (d.H + 2) * (d.W + 2), P4 = (P + 3) / 4 * 4;
-    const int IB = L.ib[l], dstride = ((IB * P4 + 63) / 64) * 64 + 4;
-    const size_t smem = ((size_t)d.Cin * ((IB * PP) | 1) + 16 * (size_t)dstride) * sizeof(float);
-    const dim3 grid(d.Cout / 16, L.nsplit[l]);
-#define GNNPP_WGRAD(HH, WW, CI, TJ, KW)                                                                       \
-    hipLaunchKernelGGL((conv_wgrad_kernel<HH, WW, CI, TJ, KW>), grid, dim3(256), smem, st, x, dy, wpart, NB,    \
-                       d.Cout, sn, sb, B, L.ips[l], L.jt[l])
-    if (l == 0) GNNPP_WGRAD(11, 11, 3, 1, 2);
-    else if (d.H == 5) GNNPP_WGRAD(5, 5, 32, 5, 1);
-    else GNNPP_WGRAD(2, 2, 64, 10, 1);
-#undef GNNPP_WGRAD
 }
 
 // obs: [B][N][3][11][11] (the reference's inputTensor, decentralplanner.py:278-286); feat = x_5 [N][B][128], or
@@ -1183,64 +1146,6 @@ int train_encoder_fwd(const EncRawParams& rp, float* const* rmean, float* const*
     return launched_ok() ? 0 : -3;
 }
 
-// ---- the weight-gradient branch of the backward pass on a second stream (r05) ------------------------------------
-// Per layer the backward chain is  R (bn_bwd_reduce) -> A (bn_bwd_apply) -> { D: input gradient -> layer l - 1 }
-//                                                                          { W: weight gradient -> Wr: its reduction }
-// and nothing downstream of W / Wr is needed before the optimizer.  On one stream the ~20 launches run back to back
-// (257 us at 64 x 10, most of them 5 .. 20 us kernels that fill a fraction of the chip for a fraction of their time:
-// profiles/r05_train_kernel_stats.csv); here W / Wr of every layer go to a SIDE stream that forks behind A(l) and
-// joins in front of the parameter-gradient kernel -- also inside a stream capture, where the fork / join events
-// become edges of the HIP graph.  dz is double-buffered so that R(l - 1) does not wait for W(l); R(l - 2), which
-// re-uses W(l)'s buffer, waits for W(l)'s event.  Measured (profiles/r05_train_fork_ab.jsonl, same kernels, bit-identical
-// gradients): 512 x 10: eager 1.626 -> 1.514 ms, graphed 1.633 -> 1.612 ms; 64 x 10 (the per-GPU shard of config 4): graphed
-// 0.486 -> 0.566 ms, eager 1.158 -> 1.270 ms -- eleven cross-stream edges cost more than the overlap of 5 .. 20 us kernels
-// buys.  GNNPP_TUNE_TRAIN_FORK: 1 (default) = fork from kTrainForkMinRows agent-samples on, 0 = never, 2 = always.
-std::atomic<int> g_train_fork{1};
-std::atomic<int> g_train_wgrad_merged{1};       // GNNPP_TUNE_TRAIN_WGRAD_MERGED
-constexpr long kTrainForkMinRows = 4096;
-
-struct BwdFork {
-    hipStream_t side = nullptr;
-    hipEvent_t dz_ready[kTrainLayers] = {}, w_done[kTrainLayers] = {}, join = nullptr;
-    bool ok = false;
-    // The side stream and its events are ONE set per device.  Two backward calls enqueued at the same time from two
-    // host threads (two models training on two streams) would interleave their record / wait pairs on the shared
-    // events -- a wait would bind to the other call's record --, so a call holds this lock while it ENQUEUES (host
-    // side only: microseconds); the calls' side work then simply queues up on the one side stream.
-    std::mutex enqueue;
-};
-
-// one per device, created on first use OUTSIDE a stream capture (resource creation is not a capturable operation);
-// a call that arrives while `st` is capturing before any eager call has run stays on one stream
-static BwdFork* bwd_fork(hipStream_t st, long rows) {
-    static std::mutex mu;
-    static BwdFork forks[16];
-    const int knob = g_train_fork.load(std::memory_order_relaxed);
-    if (knob == 0 || (knob == 1 && rows < kTrainForkMinRows)) return nullptr;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-    {   // the side stream / events are per DEVICE: they must be the ones of the device `st` belongs to; a
-        // stream of another device than the current one stays on one stream
-        hipDevice_t sdev;
-        if (st != nullptr && hipStreamGetDevice(st, &sdev) == hipSuccess && (int)sdev != dev) return nullptr;
-        (void)hipGetLastError();
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    BwdFork& f = forks[dev];
-    if (!f.ok) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
-        bool good = hipStreamCreateWithFlags(&f.side, hipStreamNonBlocking) == hipSuccess;
-        for (int l = 0; l < kTrainLayers && good; ++l)
-            good = hipEventCreateWithFlags(&f.dz_ready[l], hipEventDisableTiming) == hipSuccess &&
-                   hipEventCreateWithFlags(&f.w_done[l], hipEventDisableTiming) == hipSuccess;
-        good = good && hipEventCreateWithFlags(&f.join, hipEventDisableTiming) == hipSuccess;
-        if (!good) { (void)hipGetLastError(); return nullptr; }
-        f.ok = true;
-    }
-    return &f;
-}
-
 // dfeat: gradient w.r.t. x_5 [N][B][128]; writes d conv_w / d conv_b / d bn_w / d bn_b of every layer
 int train_encoder_bwd(const EncRawParams& rp, const float* obs, float* ws, const float* dfeat,
                       float* const* dconv_w, float* const* dconv_b, float* const* dbn_w, float* const* dbn_b,
@@ -1250,18 +1155,8 @@ int train_encoder_bwd(const EncRawParams& rp, const float* obs, float* ws, const
     const long NB = (long)N * B;
     const float* dxn = dfeat;
     float* dx_buf[2] = {ws + L.dxa, ws + L.dxb};
-    TrainPtrs5 dp = {};
-    // GNNPP_TUNE_TRAIN_WGRAD_MERGED (default 1): the weight gradients of all five layers as ONE launch behind the chain
-    // (conv_wgrad_all_kernel); 0: one launch per layer inside the chain, where the fork rule below can put them on a
-    // side stream (r05).  Same kernels' bodies, same partial layout, same reduction: bit-identical gradients.
-    const bool merged = g_train_wgrad_merged.load(std::memory_order_relaxed) != 0;
-    BwdFork* const fk = merged ? nullptr : bwd_fork(st, NB);
-    bool fork_ok = true;
     WgradReduceTable rt = {};
     WgradAllTable wa = {};
-    hipStream_t const sw = fk ? fk->side : st;              // where the weight-gradient branch runs
-    std::unique_lock<std::mutex> enqueue_lock;
-    if (fk) enqueue_lock = std::unique_lock<std::mutex>(fk->enqueue);
     for (int l = kTrainLayers - 1; l >= 0; --l) {
         const TrainLayerDims d = train_layer(l);
         const int P = d.H * d.W;
@@ -1281,20 +1176,11 @@ int train_encoder_bwd(const EncRawParams& rp, const float* obs, float* ws, const
         hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(d.Cout / t.CG, (B + t.BR - 1) / t.BR, N), dim3(256), kBnSmem, st,
                            ws + L.y[l], ws + L.stat[l], ws + L.part, rp.bn_w[l], dz, pn, B, d.Cout, P, L.chunks[l],
                            t.CG, t.BR);
-        dp.a[l] = pn; dp.b[l] = dbn_w[l]; dp.c[l] = dbn_b[l];
         const float* xin = l == 0 ? obs : ws + L.xn[l - 1];
         const long sn = l == 0 ? (long)d.Cin * P : (long)B * d.Cin * P;
         const long sb = l == 0 ? (long)N * d.Cin * P : (long)d.Cin * P;
-        if (fk) {                                            // fork: the side stream waits for dz of this layer
-            fork_ok &= hipEventRecord(fk->dz_ready[l], st) == hipSuccess;
-            fork_ok &= hipStreamWaitEvent(sw, fk->dz_ready[l], 0) == hipSuccess;
-        }
-        if (merged) {
-            wa.x[l] = xin; wa.dy[l] = dz; wa.wpart[l] = ws + L.wpart[l]; wa.x_sn[l] = sn; wa.x_sb[l] = sb;
-            wa.ips[l] = L.ips[l]; wa.jt[l] = L.jt[l]; wa.nx[l] = d.Cout / 16;
-        } else {
-            wgrad_launch(l, L, xin, dz, ws + L.wpart[l], (int)NB, sn, sb, B, sw);
-        }
+        wa.x[l] = xin; wa.dy[l] = dz; wa.wpart[l] = ws + L.wpart[l]; wa.x_sn[l] = sn; wa.x_sb[l] = sb;
+        wa.ips[l] = L.ips[l]; wa.jt[l] = L.jt[l]; wa.nx[l] = d.Cout / 16;
         rt.wpart[l] = ws + L.wpart[l]; rt.dw[l] = dconv_w[l]; rt.db[l] = dconv_b[l];
         rt.pn[l] = pn; rt.dgamma[l] = dbn_w[l]; rt.dbeta[l] = dbn_b[l];
         rt.nsplit[l] = L.nsplit[l] * L.kw[l]; rt.J16[l] = L.jt[l] * 16;
@@ -1307,19 +1193,16 @@ int train_encoder_bwd(const EncRawParams& rp, const float* obs, float* ws, const
             dxn = dx;
         }
     }
-    if (merged) {                                            // the five weight gradients: ONE grid
+    {   // the five weight gradients: ONE grid
         int blocks = 0;
         size_t smem = 0;
-        // slots in the order of the workgroups' durations, longest first (measured per-layer launches at 64 x 10: layer 2
+        // slots in the order of the workgroups' durations, longest first (measured one launch per layer at 64 x 10: layer 2
         // 19 us, 4: 13, 1: 12, 0: 11, 3: 9): the grid is ~2 rounds of the chip and the dispatcher hands out workgroups in
         // index order -- short workgroups at the end fill the tail instead of long ones starting last
         const int order[kTrainLayers] = {2, 4, 1, 0, 3};
         for (int sl = 0; sl < kTrainLayers; ++sl) {
             const int l = order[sl];
-            const TrainLayerDims d = train_layer(l);
-            const int P = d.H * d.W, PP = (d.H + 2) * (d.W + 2), P4 = (P + 3) / 4 * 4;
-            const int IB = L.ib[l], dstride = ((IB * P4 + 63) / 64) * 64 + 4;
-            const size_t sm = ((size_t)d.Cin * ((IB * PP) | 1) + 16 * (size_t)dstride) * sizeof(float);
+            const size_t sm = wgrad_smem_bytes(l);
             smem = smem > sm ? smem : sm;
             wa.order[sl] = l;
             wa.first[sl] = blocks;
@@ -1338,16 +1221,8 @@ int train_encoder_bwd(const EncRawParams& rp, const float* obs, float* ws, const
         }
         rt.first[kTrainLayers] = blocks;
         rt.N = N;
-        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(blocks), dim3(256), 256 * sizeof(float), sw, rt);
+        hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(blocks), dim3(256), 256 * sizeof(float), st, rt);
     }
-    if (fk) {                                                // join: everything behind this call sees every gradient
-        fork_ok &= hipEventRecord(fk->join, sw) == hipSuccess;
-        fork_ok &= hipStreamWaitEvent(st, fk->join, 0) == hipSuccess;
-        // a failed record / wait (a capture-mode restriction, a stream of another device) would silently drop
-        // the dz_ready / w_done ordering the ping-pong dz buffers rely on: the call fails instead of racing
-        if (!fork_ok) { (void)hipGetLastError(); return -3; }
-    }
-    (void)dp;                                                // (d gamma / d beta: inside conv_wgrad_reduce_kernel since r06)
     return launched_ok() ? 0 : -3;
 }
 

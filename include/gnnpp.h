@@ -114,27 +114,20 @@ const char* gnnpp_error_string(int code);
                                          = heuristic -- M <= 2048 agents: tiles of ceil(M / 256) agents, one per CU
                                          (latency regime), else 16-agent tiles --, 1 .. 12 = that tile size for every
                                          M, 16 = always 16-agent tiles.  Same features to the bit (v310)                */
-#define GNNPP_TUNE_TRAIN_FORK        15  /* gnnpp_encoder_train_bwd can run the weight-gradient kernels of every layer
-                                         on a second HIP stream that forks behind the layer's BatchNorm backward and
-                                         joins before the call hands the stream back (graph edges under capture):
-                                         1 (default) = from 4096 agent-samples (N x B) on -- measured + 7 % eager at
-                                         512 x 10, - 16 % at 64 x 10 --, 0 = never, 2 = always.  Same gradients to the
-                                         bit (v320)                                                                  */
+/* (keys 15 and 18 -- v320's GNNPP_TUNE_TRAIN_FORK, the weight-gradient kernels of gnnpp_encoder_train_bwd on a second
+ * stream, and v330's GNNPP_TUNE_TRAIN_WGRAD_MERGED = 0, one weight-gradient launch per layer; both measured slower than
+ * the one launch for all five layers behind the backward chain -- were removed: that launch is the only schedule, the
+ * numbers are not reused, and gnnpp_set_tuning / gnnpp_get_tuning answer GNNPP_ERR_ARG)                             */
 #define GNNPP_TUNE_FILTER_PLANE_ALIAS 16 /* 1 (default): the filter + head launch of teams whose bf16x3 operand planes do
                                          not fit the LDS beside the graph (65 .. 100 agents) keeps the planes in the z buffer
                                          that is dead while a tap is contracted -- possible whenever the graph is split
                                          over >= 2 workgroups -- instead of contracting on the exact fp32 MFMA (2.7x the
                                          matrix-pipe time); 0 = r05's behaviour.  Same accuracy class (v330)              */
-#define GNNPP_TUNE_TRAIN_WGRAD_WGS   17  /* workgroups per layer of the training step's weight-gradient kernel (image splits x
-                                         output-channel tiles): 0 (default) = by the batch (128 up to 1 280 agent-samples, 256
+#define GNNPP_TUNE_TRAIN_WGRAD_WGS   17  /* workgroups per layer of the training step's weight-gradient kernel (ONE launch for all
+                                         five layers behind the backward chain; image splits x output-channel tiles): 0 (default) = by the batch (128 up to 1 280 agent-samples, 256
                                          beyond), or 16 .. 2048: more splits = shorter workgroups, more partial sums to add.
                                          Set before gnnpp_encoder_train_workspace_floats / _train_fwd: the workspace size
                                          depends on it.  Same gradients to rounding (v330)                              */
-#define GNNPP_TUNE_TRAIN_WGRAD_MERGED 18 /* 1 (default): gnnpp_encoder_train_bwd computes the weight gradients of all five
-                                         layers in ONE launch behind the backward chain (nothing downstream needs them before
-                                         the optimizer; at 64 x 10 the five per-layer launches are 65 us of latency, their
-                                         MFMAs 14 us); 0: one launch per layer inside the chain, where GNNPP_TUNE_TRAIN_FORK
-                                         can move them to a second stream.  Same gradients to the bit (v330)               */
 #define GNNPP_TUNE_TRAIN_RUNNING_FUSED 19 /* 1 (default): gnnpp_encoder_train_fwd updates the BatchNorm running statistics inside
                                          its last BatchNorm launch (the workgroups of a channel tile publish their statistics
                                          with an agent-scope release / ticket / acquire hand-off and the last one to arrive

@@ -138,24 +138,32 @@ def test_emu_train_encoder_forward_backward(N, B, seed, fbn, ext_pack):
     rc = lib.gnnpp_encoder_train_bwd(ctypes.byref(P), el.ptr(obs_np), el.ptr(ws), el.ptr(cot_np), ctypes.byref(G),
                                      B, N, fbn, el.ptr(tp) if tp is not None else None, None)
     assert rc == 0
-    # r06b: the weight gradients of all five layers come from ONE launch behind the chain (GNNPP_TUNE_TRAIN_WGRAD_MERGED,
-    # default); the per-layer launches of r05 (knob 18 = 0) give the same bits
-    assert (lib.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_MERGED) == 1
-            and lib.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 0) == 0)
-    try:
-        G2, outs2 = EncoderGrads(), {}
-        for i in range(5):
-            for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
-                               ('bn_w', 'ConvLayers.%d.weight' % BN[i]), ('bn_b', 'ConvLayers.%d.bias' % BN[i])):
-                o = np.full(tuple(sd[key].shape), np.nan, np.float32); outs2[key] = o
-                getattr(G2, field)[i] = o.ctypes.data
-        rc = lib.gnnpp_encoder_train_bwd(ctypes.byref(P), el.ptr(obs_np), el.ptr(ws), el.ptr(cot_np), ctypes.byref(G2),
-                                         B, N, fbn, el.ptr(tp) if tp is not None else None, None)
-        assert rc == 0
-        for key in outs:
-            assert np.array_equal(outs[key], outs2[key]), key
-    finally:
-        assert lib.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 1) == 0
+    # A second backward call on the same workspace, fresh outputs: bit-identical, with the per-layer slabs of weight-gradient
+    # partials (`wpart`: the tail of the workspace, behind the 8 arrival counters of the forward) poisoned with NaN first --
+    # every partial the split sum reads was written by THIS call.  Slab of a layer, as train_ws_layout has it:
+    # [image splits x K groups][Cout][j tiles x 16], GNNPP_TUNE_TRAIN_WGRAD_WGS workgroups (0: 128 up to 1 280 images).
+    NB, wgs = N * B, lib.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS) or (128 if N * B <= 1280 else 256)
+    tail = 0
+    for cin, cout in ((3, 32), (32, 32), (32, 64), (64, 64), (64, 128)):
+        ips = -(-NB // min(-(-wgs // (cout // 16)), NB))
+        jt = -(-(cin * 9 + 1) // 16)
+        tail += -(-NB // ips) * (2 if jt <= 2 else 1) * cout * jt * 16
+    ws[ws.size - tail - 8:] = np.nan                         # (the counters too: the backward leaves them alone)
+    G2, outs2 = EncoderGrads(), {}
+    for i in range(5):
+        for field, key in (('conv_w', 'ConvLayers.%d.weight' % CONV[i]), ('conv_b', 'ConvLayers.%d.bias' % CONV[i]),
+                           ('bn_w', 'ConvLayers.%d.weight' % BN[i]), ('bn_b', 'ConvLayers.%d.bias' % BN[i])):
+            o = np.full(tuple(sd[key].shape), np.nan, np.float32); outs2[key] = o
+            getattr(G2, field)[i] = o.ctypes.data
+    rc = lib.gnnpp_encoder_train_bwd(ctypes.byref(P), el.ptr(obs_np), el.ptr(ws), el.ptr(cot_np), ctypes.byref(G2),
+                                     B, N, fbn, el.ptr(tp) if tp is not None else None, None)
+    assert rc == 0
+    # the restated slab sizes are the library's: the call rewrote exactly the floats behind the counters
+    assert np.isnan(ws[ws.size - tail - 8:ws.size - tail]).all() and not np.isnan(ws[ws.size - tail:]).any()
+    for key in outs:
+        assert np.array_equal(outs[key], outs2[key]), key
+    for k in (15, 18):                                       # the retired schedule keys (fork, one launch per layer)
+        assert lib.gnnpp_get_tuning(k) == -1 and lib.gnnpp_set_tuning(k, 1) == -1
     for key, o in outs.items():
         want = p_ref[key].grad.numpy()
         scale = np.abs(want).max()

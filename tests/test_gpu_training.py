@@ -251,13 +251,13 @@ def test_graphed_train_step_equals_eager(dev):
 
 
 @pytest.mark.parametrize('B', [8, 64])
-def test_backward_weight_gradient_fork_is_bit_identical(dev, B):
-    """r05: gnnpp_encoder_train_bwd runs the weight-gradient kernels of every layer on a second HIP stream (forks
-    behind each layer's BatchNorm backward, joins before the call hands the stream back; GNNPP_TUNE_TRAIN_FORK = 2:
-    always, 1: from 4096 agent-samples on, 0: never).  The
-    same kernels on the same data: every gradient, the loss and the parameters after several optimisation steps are
-    the one-stream run's BIT FOR BIT -- eager, and as a captured HIP graph (where the fork / join are graph edges) --
-    and a race on the double-buffered dz / the shared partial-sum buffers would show up as run-to-run differences."""
+def test_training_steps_are_bit_identical_eager_repeated_and_graphed(dev, B):
+    """The training step is deterministic: every reduction has a fixed order and the backward of the encoder enqueues
+    one chain of launches on the caller's stream (the weight gradients of all five layers as ONE launch behind it).  The
+    loss and the parameters after several optimisation steps, and the gradients of the last one, are the same BIT FOR BIT
+    in an eager run, a second eager run, and a captured HIP graph -- a race on the per-layer dz buffers or the shared
+    partial-sum buffers would show up as run-to-run differences.  The keys of the two retired schedules (15: the weight
+    gradients on a second stream, 18: one weight-gradient launch per layer) are unknown to the library."""
     from gnn_pathplanning_amd import _native
     from gnn_pathplanning_amd.decentralplanner import DecentralPlannerNet
     from gnn_pathplanning_amd.training import FusedAdam, GraphedTrainStep, train_step
@@ -274,12 +274,7 @@ def test_backward_weight_gradient_fork_is_bit_identical(dev, B):
         batches.append((obs, tgt, S))
     sd0 = orc.init_state_dict(3, seed=13)
 
-    def run(fork, graphed, merged=0):
-        # merged (r06b, GNNPP_TUNE_TRAIN_WGRAD_MERGED, the default): all five weight gradients as ONE launch behind the
-        # chain -- the fork rule only applies to the per-layer launches (merged = 0)
-        assert (L.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, merged) == 0
-                and L.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_MERGED) == merged)
-        assert L.gnnpp_set_tuning(_native.TUNE_TRAIN_FORK, fork) == 0 and L.gnnpp_get_tuning(_native.TUNE_TRAIN_FORK) == fork
+    def run(graphed):
         net = DecentralPlannerNet(Cfg()).to(dev).train()
         net.load_state_dict(sd0)
         opt = FusedAdam(net.parameters(), lr=1e-3, weight_decay=1e-5)
@@ -295,19 +290,15 @@ def test_backward_weight_gradient_fork_is_bit_identical(dev, B):
             grads = [p.grad.clone() for p in net.parameters()]
         torch.cuda.synchronize()
         return losses, grads, [p.detach().clone() for p in net.parameters()]
-    try:
-        ref = run(0, False)
-        for fork, graphed, merged in ((2, False, 0), (2, False, 0), (2, True, 0), (0, True, 0), (1, False, 0),
-                                      (1, False, 1), (1, True, 1), (2, True, 1)):
-            got = run(fork, graphed, merged)
-            assert got[0] == ref[0], (fork, graphed, got[0], ref[0])
-            assert all(torch.equal(a, b) for a, b in zip(got[2], ref[2])), (fork, graphed)
-            if got[1] is not None:
-                assert all(torch.equal(a, b) for a, b in zip(got[1], ref[1])), (fork, graphed)
-        assert L.gnnpp_set_tuning(_native.TUNE_TRAIN_FORK, 3) == -1 and L.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 2) == -1
-    finally:
-        L.gnnpp_set_tuning(_native.TUNE_TRAIN_FORK, 1)
-        L.gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 1)
+    ref = run(False)
+    for graphed in (False, True):
+        got = run(graphed)
+        assert got[0] == ref[0], (graphed, got[0], ref[0])
+        assert all(torch.equal(a, b) for a, b in zip(got[2], ref[2])), graphed
+        if got[1] is not None:
+            assert all(torch.equal(a, b) for a, b in zip(got[1], ref[1])), graphed
+    for key in (15, 18):
+        assert L.gnnpp_set_tuning(key, 1) == -1 and L.gnnpp_get_tuning(key) == -1
 
 
 def test_small_cotangents_keep_relative_accuracy(dev):

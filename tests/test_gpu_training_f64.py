@@ -31,7 +31,7 @@ CONV = (0, 4, 7, 11, 14)
 BN = (1, 5, 8, 12, 15)
 POS = (121, 25, 25, 4, 4)                 # positions per image at each convolution's output
 EPS, MOMENTUM = 1e-5, 0.1
-KNOB_WGS, KNOB_MERGED, KNOB_FUSED = 17, 18, 19
+KNOB_WGS, KNOB_FUSED = 17, 19
 
 
 @pytest.fixture(scope='module')
@@ -409,10 +409,10 @@ def test_planner_unequal_widths_larger_gso_against_float64(dev, monkeypatch):
     one_case(dev, monkeypatch, 4, 6, via_step=False, **kw)
 
 
-@pytest.mark.parametrize('knob,value', [(KNOB_WGS, 16), (KNOB_WGS, 2048), (KNOB_MERGED, 0), (KNOB_FUSED, 0)])
+@pytest.mark.parametrize('knob,value', [(KNOB_WGS, 16), (KNOB_WGS, 2048), (KNOB_FUSED, 0)])
 def test_training_knobs_against_float64(dev, monkeypatch, knob, value):
-    """Every training knob setting against float64 itself, not only against the default setting (the defaults, merged
-    weight gradients and fused running statistics, are the other tests)."""
+    """Every training knob setting against float64 itself, not only against the default setting (the defaults, 128 / 256
+    weight-gradient workgroups by batch and fused running statistics, are the other tests)."""
     from gnn_pathplanning_amd import _native
     Lb = _native.lib()
     old = Lb.gnnpp_get_tuning(knob)

@@ -141,7 +141,7 @@ def test_python_abi_matches_header():
     from gnn_pathplanning_amd import _native
     header = _parse_header(open(os.path.join(ROOT, 'include', 'gnnpp.h')).read())
     protos, structs, defines = header
-    assert len(protos) == 59 and len(structs) == 7 and len(defines) == 46, (len(protos), len(structs), len(defines))
+    assert len(protos) == 59 and len(structs) == 7 and len(defines) == 44, (len(protos), len(structs), len(defines))
     assert list(protos) == list(_native.SIGNATURES) and _native.EXPORTS == tuple(_native.SIGNATURES)    # header order
     assert not set(_native.MEASURE_SIGNATURES) & set(_native.EXPORTS)
     fields = {c: getattr(_native, py)._fields_ for c, py in _STRUCT_CLASSES.items()}

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU-box session.  Usage (repo root on the GPU box): bash tools/gpu_session.sh <tag> [steps...]
-# steps: wave8 pmc35 trainab hostov distbench test smoke bench benchdrv bench35 train traincpu trainprof cpab cptiles distcheck stamps b3stamps filterstamps filtersweep prof prof35 proftrain pmc pmclds filterpmc pipeablate
+# steps: wave8 pmc35 hostov distbench test smoke bench benchdrv bench35 train traincpu trainprof cpab cptiles distcheck stamps b3stamps filterstamps filtersweep prof prof35 proftrain pmc pmclds filterpmc pipeablate
 TAG=${1:-r01}; shift
 STEPS=${@:-test smoke bench bench35 prof}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -27,14 +27,6 @@ if has train; then stamp "train bench"
   timeout 300 python tools/train_bench.py --steps 50 --graph 2>&1 | tail -3 | tee $OUT/train_bench_graph.json
   timeout 300 python tools/train_bench.py --steps 50 --graph --batch 512 2>&1 | tail -1 | tee -a $OUT/train_bench_graph.json
   timeout 300 python tools/train_bench.py --steps 50 --batch 512 2>&1 | tail -1 | tee -a $OUT/train_bench.json; fi
-if has trainab; then stamp "train bench: weight-gradient fork on / off (graphed and eager, B = 64 and 512)"
-  for b in 64 512; do for g in "--graph" ""; do for f in "--fork" "--no-fork"; do
-    timeout 300 python tools/train_bench.py --steps 100 $g --batch $b $f 2>&1 | tail -1 | tee -a $OUT/train_fork_ab.jsonl
-  done; done; done; fi
-if has wgradab; then stamp "train bench: weight gradients merged into one launch (default) vs per layer (+ fork rule), B = 64 and 512"
-  for b in 64 512; do for g in "--graph" ""; do for m in "" "--wgrad-per-layer"; do
-    timeout 300 python tools/train_bench.py --steps 100 $g --batch $b $m 2>&1 | tail -1 | tee -a $OUT/train_wgrad_merged_ab.jsonl
-  done; done; done; fi
 if has wgradsweep; then stamp "train bench: workgroups per layer of the weight-gradient kernel (graphed, B = 64)"
   for w in 96 128 192 256 320 448; do
     timeout 300 python tools/train_bench.py --steps 100 --graph --wgrad-wgs $w 2>&1 | tail -1 | tee -a $OUT/train_wgrad_sweep.jsonl

@@ -140,13 +140,9 @@ def main():
                     help='optimizer: training.FusedAdam (gnnpp_adam_step) or torch.optim.Adam')
     ap.add_argument('--cpu-seconds', type=float, default=0.0,
                     help='> 0: also time the CPU oracle\'s training step on the host (rank 0, 1 GPU) for this long')
-    ap.add_argument('--no-fork', action='store_true',
-                    help='GNNPP_TUNE_TRAIN_FORK = 0: the backward pass of the encoder on ONE stream (A/B of the r05 fork)')
-    ap.add_argument('--fork', action='store_true', help='GNNPP_TUNE_TRAIN_FORK = 2: fork whatever the batch size')
     ap.add_argument('--wgrad-wgs', type=int, default=0,
-                    help='GNNPP_TUNE_TRAIN_WGRAD_WGS: workgroups per layer of the weight-gradient kernel (default 320)')
-    ap.add_argument('--wgrad-per-layer', action='store_true',
-                    help='GNNPP_TUNE_TRAIN_WGRAD_MERGED = 0: one weight-gradient launch per layer inside the chain (r05)')
+                    help='GNNPP_TUNE_TRAIN_WGRAD_WGS: workgroups per layer of the weight-gradient kernel '
+                         '(default 0: 128 up to 1 280 agent-samples, 256 beyond)')
     ap.add_argument('--dist-backend', default='nccl',
                     help='nccl (= RCCL, default); gloo only to exercise the data-parallel code path on a box with '
                          'fewer GPUs than ranks (with GNNPP_BENCH_DEVICE=0; eager mode only)')
@@ -165,12 +161,8 @@ def main():
             dist.init_process_group(args.dist_backend)
     from gnn_pathplanning_amd.sharding import gather_rank_devices
     from gnn_pathplanning_amd import _native
-    if args.wgrad_per_layer:
-        assert _native.lib().gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_MERGED, 0) == 0
     if args.wgrad_wgs:
         assert _native.lib().gnnpp_set_tuning(_native.TUNE_TRAIN_WGRAD_WGS, args.wgrad_wgs) == 0
-    if args.no_fork or args.fork:
-        assert _native.lib().gnnpp_set_tuning(_native.TUNE_TRAIN_FORK, 0 if args.no_fork else 2) == 0
     B, N = args.batch, 10
     per_step, loss = measure(dev, B, args.steps, args.warmup, args.graph, args.adam, rank, world)
     rank_devices = gather_rank_devices(dev)
@@ -181,9 +173,7 @@ def main():
                 'backend': dist.get_backend() if world > 1 else None,
                 'batch_per_gpu': B, 'ms_per_step': 1e3 * per_step,
                 'final_loss': loss, 'hip_graph': bool(args.graph), 'adam': args.adam,
-                'wgrad_wgs': _native.lib().gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS),
-                'wgrad_merged': _native.lib().gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_MERGED),
-                'backward_fork_knob': _native.lib().gnnpp_get_tuning(_native.TUNE_TRAIN_FORK)}
+                'wgrad_wgs': _native.lib().gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS)}
         if args.cpu_seconds > 0 and world == 1:
             cb = cpu_baseline(B, args.cpu_seconds)
             cb['speedup_gpu_over_cpu'] = line['value'] / cb['value']
