@@ -14,6 +14,7 @@
 #include "expert_team_kernels.hip"   // ... for teams of up to GNNPP_ROLLOUT_MAX_TEAM agents (one thread per agent, row tiles of S)
 #include "mapf_kernels.hip"          // prioritized-planning MAPF solver (the expert of the online loop)
 #include "mapf_team_kernels.hip"     // ... for teams of up to 1024 agents on maps of up to 256 x 256 (one workgroup per case)
+#include "mapf_distance_kernels.hip" // ... its planning orders: true goal distances and the orders ranked from them
 #include "encoder_kernel_h2.hip"
 #include "encoder_kernel_b3.hip"
 #include "lsigf_kernel.hip"
@@ -856,6 +857,39 @@ int gnnpp_mapf_team_solve(const gnnpp_mapf* m, void* stream) {
     const int slots = mapf_team_slots((long long)m->C * m->R, m->R, m->C, m->H, m->W, m->T_max, m->workspace_bytes);
     if (slots < 1) return GNNPP_ERR_ARG;
     return mapf_team_launch(*m, slots, static_cast<hipStream_t>(stream));
+}
+
+// include/gnnpp_mapf_distance.h: checked in gnnpp_mapf_team_solve's order, nothing is enqueued on an error
+int gnnpp_mapf_distances(const unsigned char* grid, int grid_batched, const int* start, const int* goal, int C, int N,
+                         int H, int W, int* dist, int* lower_makespan, int* lower_flowtime, void* stream) {
+    if (!grid || !start || !goal || !dist || !lower_makespan || !lower_flowtime || C <= 0 || N <= 0 ||
+        N > GNNPP_ROLLOUT_MAX_TEAM || H <= 0 || W <= 0 || (long long)C * N > 0x7fffffffLL)
+        return GNNPP_ERR_ARG;
+    if (H > GNNPP_MAPF_TEAM_MAX_SIDE || W > GNNPP_MAPF_TEAM_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
+    MapfDistArgs a;
+    a.grid = grid;
+    a.grid_batched = grid_batched;
+    a.start = start;
+    a.goal = goal;
+    a.C = C;
+    a.N = N;
+    a.H = H;
+    a.W = W;
+    a.dist = dist;
+    a.lower_makespan = lower_makespan;
+    a.lower_flowtime = lower_flowtime;
+    return mapf_distance_launch(a, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_mapf_orders(const int* dist, int C, int N, int R, const int* rules, unsigned seed, int* order, void* stream) {
+    if (!rules || !order || C <= 0 || R <= 0 || N <= 0 || N > GNNPP_ROLLOUT_MAX_TEAM || (long long)C * R > 0x7fffffffLL)
+        return GNNPP_ERR_ARG;
+    for (int r = 0; r < R; ++r) {
+        if (rules[r] < GNNPP_MAPF_ORDER_INDEX || rules[r] > GNNPP_MAPF_ORDER_HASHED) return GNNPP_ERR_ARG;
+        if (!dist && (rules[r] == GNNPP_MAPF_ORDER_LONGEST_FIRST || rules[r] == GNNPP_MAPF_ORDER_SHORTEST_FIRST))
+            return GNNPP_ERR_ARG;
+    }
+    return mapf_order_launch(dist, C, N, R, rules, seed, order, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -259,7 +259,9 @@ def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gs
 def solve_failures(rollout, results=None, **kw):
     """Plan every episode of a BatchedRollout whose `success` is false, straight from its device state: the agents'
     final positions as starts, their goals, the episode's map (what write_failure_cases would put in the files).
-    kw: mapf.solve's max_steps, restarts, priorities, seed.  Teams of more than mapf.MAX_AGENTS agents and maps with a
+    kw: mapf.solve's max_steps, restarts, priorities, seed -- priorities='longest_first' | 'shortest_first' | 'mixed'
+    ranks the planning orders on the device from the agents' true goal distances (no host round trip; the Solutions then
+    also carry .distance, .lower_makespan and .lower_flowtime).  Teams of more than mapf.MAX_AGENTS agents and maps with a
     side beyond mapf.MAX_SIDE go to mapf.solve_team (which also takes workspace_bytes), everything else to mapf.solve.
     Returns mapf.Solutions of those F episodes with `.episodes` (their indices in the rollout, numpy int64 [F]), or
     None when every episode succeeded.  samples_from_solutions turns them into training samples (team=True for teams

@@ -11,6 +11,12 @@ csrc/mapf_team_kernels.hip: one workgroup per case, up to 1024 agents on maps of
 same contract and, where both apply, the same outputs).  Restart 0 is the index order, further restarts seeded random permutations; a
 case keeps its best restart (solved, then smallest flowtime, smallest makespan, lowest index).  There is no CPU
 fallback.  Positions are (row, col) integers: the reference's (x, y).
+
+Orders that look at the case (include/gnnpp_mapf_distance.h, csrc/mapf_distance_kernels.hip): distances() is every
+agent's true shortest-path distance from start to goal on its map, with the lower bounds on makespan and flowtime that
+follow; heuristic_orders() ranks planning orders from them on the device (longest first, shortest first, hashed);
+priorities='longest_first' | 'shortest_first' | 'mixed' of solve / solve_team enqueue both ahead of the solve on the
+same stream; maxstep_from_distances() turns the makespan bound into a rollout's step limit.
 """
 import ctypes
 
@@ -23,12 +29,16 @@ MAX_AGENTS, MAX_SIDE, MAX_STEPS = _native.ROLLOUT_MAX_AGENTS, _native.MAPF_MAX_S
 MAX_TEAM, MAX_TEAM_SIDE, MAX_TEAM_STEPS = (_native.ROLLOUT_MAX_TEAM, _native.MAPF_TEAM_MAX_SIDE,      # (solve_team)
                                            _native.MAPF_TEAM_MAX_STEPS)
 NO_PATH, BAD_CASE = _native.MAPF_NO_PATH, _native.MAPF_BAD_CASE
+UNREACHABLE, INVALID = _native.MAPF_DIST_UNREACHABLE, _native.MAPF_DIST_INVALID         # (negative entries of dist)
+ORDER_RULES = {'index': _native.MAPF_ORDER_INDEX, 'longest_first': _native.MAPF_ORDER_LONGEST_FIRST,
+               'shortest_first': _native.MAPF_ORDER_SHORTEST_FIRST, 'hashed': _native.MAPF_ORDER_HASHED}
 
 
 class Solutions:
     """Device tensors of one solve call: schedules [C,T+1,N,2] int32 (agents wait on their goal after arriving; -1 for
     agents left unplanned), arrival [C,N], makespan / flowtime / status / failing / restart [C] int32 (-1 where they do
-    not apply), and the workspace."""
+    not apply), and the workspace.  Of a call with priorities given as a string also distance [C,N], lower_makespan and
+    lower_flowtime [C] (see distances()) and priorities [C,R,N], the orders that were planned."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -159,12 +169,104 @@ def _int32(x):
     return (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(torch.int32)
 
 
+class Distances:
+    """Device tensors of one distances() call: dist [C,N] int32 (UNREACHABLE = -1: no path; INVALID = -2: start or goal
+    off the map or on an obstacle), lower_makespan / lower_flowtime [C] int32 (max / sum of the case's distances, -1 when
+    one of them is negative).  Unpacks as (dist, lower_makespan, lower_flowtime)."""
+
+    def __init__(self, dist, lower_makespan, lower_flowtime):
+        self.dist, self.lower_makespan, self.lower_flowtime = dist, lower_makespan, lower_flowtime
+
+    def __iter__(self):
+        return iter((self.dist, self.lower_makespan, self.lower_flowtime))
+
+
+def enqueue_distances(grid, start, goal, out):
+    """gnnpp_mapf_distances alone, on torch's current stream: two launches, no allocation, no host synchronisation,
+    capturable.  grid uint8 [C,H,W] | [H,W]; start, goal int32 [C,N,2]; out: a Distances of int32 tensors ([C,N], [C],
+    [C]).  All contiguous device tensors."""
+    dev = _native.require_gpu(grid, start, goal, out.dist, out.lower_makespan, out.lower_flowtime)
+    with _native.device_guard(dev):
+        _native.check(_native.lib().gnnpp_mapf_distances(
+            grid.data_ptr(), int(grid.dim() == 3), start.data_ptr(), goal.data_ptr(), int(start.shape[0]),
+            int(start.shape[1]), int(grid.shape[-2]), int(grid.shape[-1]), out.dist.data_ptr(),
+            out.lower_makespan.data_ptr(), out.lower_flowtime.data_ptr(), _native.stream_ptr(dev)), 'gnnpp_mapf_distances')
+
+
+def enqueue_orders(dist, rules, seed, order):
+    """gnnpp_mapf_orders alone, on torch's current stream: order [C,R,N] int32 := the agents of every case ranked by
+    each of the R rules (codes of ORDER_RULES) from the keys dist [C,N] int32.  One launch per 32 rules, capturable."""
+    dev = _native.require_gpu(dist, order)
+    C, R, N = (int(v) for v in order.shape)
+    codes = (ctypes.c_int * R)(*[int(r) for r in rules])
+    with _native.device_guard(dev):
+        _native.check(_native.lib().gnnpp_mapf_orders(dist.data_ptr(), C, N, R, codes, int(seed) & 0xffffffff,
+                                                      order.data_ptr(), _native.stream_ptr(dev)), 'gnnpp_mapf_orders')
+
+
+def _rule_codes(rules):
+    if isinstance(rules, str):
+        rules = [rules]
+    rules = list(rules)
+    unknown = [r for r in rules if r not in ORDER_RULES]
+    if unknown or not rules:
+        raise _native.GnnppError('rules: a non-empty sequence of %s (got %r)' % (sorted(ORDER_RULES), unknown or rules))
+    return [ORDER_RULES[r] for r in rules]
+
+
+def distances(grids, starts, goals, device):
+    """Every agent's true distance to its goal: grids [C,H,W] or [H,W] (1 = obstacle), starts / goals [C,N,2] (row,
+    col), host or device, with solve_team's checks and limits.  Returns Distances (dist, lower_makespan, lower_flowtime
+    on the device); agents without a path or with an invalid start / goal are reported in dist, never raised."""
+    dev, g, start, goal, C, N, H, W = _inputs('mapf.distances', MAX_TEAM, MAX_TEAM_SIDE, grids, starts, goals, device)
+    return _distances(*_on_device(dev, g, start, goal))
+
+
+def _distances(grid, start, goal):
+    C, N = int(start.shape[0]), int(start.shape[1])
+    out = Distances(*(torch.empty(shape, dtype=torch.int32, device=start.device) for shape in ((C, N), (C,), (C,))))
+    enqueue_distances(grid, start, goal, out)
+    return out
+
+
+def heuristic_orders(dist, rules, seed=0):
+    """Planning orders [C,R,N] int32 on the device, one per rule of `rules` ('index' | 'longest_first' |
+    'shortest_first' | 'hashed'), ranked from dist [C,N] (distances().dist, or any integer keys; a device tensor).
+    longest_first / shortest_first: by distance descending / ascending, agents with a negative distance first; hashed:
+    by a counter hash of (seed, case, restart, agent); every tie goes to the lower agent index."""
+    codes = _rule_codes(rules)
+    if not torch.is_tensor(dist) or dist.dim() != 2 or not 1 <= dist.shape[1] <= MAX_TEAM or dist.shape[0] < 1:
+        raise _native.GnnppError('dist must be a [C,N] device tensor with 1 <= N <= %d' % MAX_TEAM)
+    _native.require_gpu(dist)
+    dist = dist.to(torch.int32).contiguous()
+    order = torch.empty((dist.shape[0], len(codes), dist.shape[1]), dtype=torch.int32, device=dist.device)
+    enqueue_orders(dist, codes, seed, order)
+    return order
+
+
+def maxstep_from_distances(lower_makespan, rate):
+    """int32 [C]: ceil(rate * lower_makespan) (the product in float64), at least 1 -- a per-episode step limit for
+    BatchedRollout(maxstep=...) where no expert makespan exists yet (the reference: rate_maxstep * the expert's makespan).
+    Raises GnnppError when a case has an agent without a path or with an invalid start / goal (lower_makespan < 0)."""
+    lm = lower_makespan if torch.is_tensor(lower_makespan) else torch.as_tensor(np.asarray(lower_makespan))
+    if not float(rate) > 0:
+        raise _native.GnnppError('rate must be positive (got %r)' % (rate,))
+    bad = (lm < 0).nonzero().flatten().tolist()
+    if bad:
+        raise _native.GnnppError('no step limit for cases %s: an agent cannot reach its goal' % bad[:8])
+    return torch.ceil(lm.to(torch.float64) * float(rate)).clamp_(min=1).to(torch.int32)
+
+
 def solve(grids, starts, goals, device, max_steps=None, restarts=1, priorities=None, seed=0):
     """Plan C cases: grids [C,H,W] or [H,W] (1 = obstacle), starts / goals [C,N,2] (row, col), host or device.
     max_steps: the horizon T_max (default 4 (H + W)).  priorities: planning orders [C,R,N] or [R,N] (shared by the
     cases), permutations of the agents; by default restart 0 is the index order and restarts 1 .. restarts-1 are
-    random permutations drawn from numpy's default_rng(seed).  Returns Solutions; unsolved and invalid cases are
-    reported in .status (NO_PATH, BAD_CASE), never raised."""
+    random permutations drawn from numpy's default_rng(seed).  priorities as a string: the orders are ranked on the
+    device from the agents' true goal distances, enqueued ahead of the solve on the same stream (distances(),
+    heuristic_orders()) -- 'longest_first' / 'shortest_first': that one order; 'mixed': max(restarts, 3) orders, the
+    index order, longest first, shortest first, the rest hashed with `seed`; the Solutions then carry .distance,
+    .lower_makespan, .lower_flowtime and .priorities.  Returns Solutions; unsolved and invalid cases are reported in
+    .status (NO_PATH, BAD_CASE), never raised."""
     return _solve('mapf.solve', False, MAX_AGENTS, MAX_SIDE, MAX_STEPS, grids, starts, goals, device, max_steps,
                   restarts, priorities, seed, None)
 
@@ -186,8 +288,8 @@ def default_orders(C, N, restarts, seed):
     return np.concatenate([np.broadcast_to(np.arange(N), (C, 1, N)), perm], 1)
 
 
-def _solve(what, team, max_agents, max_side, max_steps_limit, grids, starts, goals, device, max_steps, restarts,
-           priorities, seed, workspace_bytes):
+def _inputs(what, max_agents, max_side, grids, starts, goals, device):
+    """The checks of a call's inputs, on the host: (dev, grids, starts, goals as tensors, C, N, H, W)."""
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise _native.GnnppError('%s needs a HIP device (no CPU fallback)' % what)
@@ -204,11 +306,33 @@ def _solve(what, team, max_agents, max_side, max_steps_limit, grids, starts, goa
     H, W = int(g.shape[-2]), int(g.shape[-1])
     if not (1 <= H <= max_side and 1 <= W <= max_side):
         raise _native.GnnppError('maps of at most %d x %d cells (got %d x %d)' % (max_side, max_side, H, W))
+    return dev, g, start, goal, C, N, H, W
+
+
+def _on_device(dev, g, start, goal):
+    """The checked inputs as contiguous device tensors (grid uint8, start, goal int32)."""
+    _native.lib()
+    return g.to(torch.uint8).contiguous().to(dev), start.contiguous().to(dev), goal.contiguous().to(dev)
+
+
+def _solve(what, team, max_agents, max_side, max_steps_limit, grids, starts, goals, device, max_steps, restarts,
+           priorities, seed, workspace_bytes):
+    dev, g, start, goal, C, N, H, W = _inputs(what, max_agents, max_side, grids, starts, goals, device)
     T = 4 * (H + W) if max_steps is None else int(max_steps)
     if not 0 <= T <= max_steps_limit:
         raise _native.GnnppError('max_steps must be in 0 .. %d (got %d)' % (max_steps_limit, T))
-    order = None
-    if priorities is not None:
+    order, dist, rules = None, None, None
+    if isinstance(priorities, str):
+        if int(restarts) < 1:
+            raise _native.GnnppError('restarts must be >= 1 (got %d)' % restarts)
+        if priorities == 'mixed':
+            rules = (['index', 'longest_first', 'shortest_first'] + ['hashed'] * (int(restarts) - 3))
+        elif priorities in ('longest_first', 'shortest_first'):
+            rules = [priorities]
+        else:
+            raise _native.GnnppError("priorities as a string: 'longest_first', 'shortest_first' or 'mixed' (got %r)"
+                                     % priorities)
+    elif priorities is not None:
         order = _int32(priorities)
         if order.dim() == 2:
             order = order.unsqueeze(0).expand(C, -1, -1)
@@ -219,15 +343,19 @@ def _solve(what, team, max_agents, max_side, max_steps_limit, grids, starts, goa
         order = torch.from_numpy(default_orders(C, N, restarts, seed)).to(torch.int32)
     elif int(restarts) < 1:
         raise _native.GnnppError('restarts must be >= 1 (got %d)' % restarts)
+    grid, start, goal = _on_device(dev, g, start, goal)
+    if rules is not None:                               # enqueued ahead of the solve, on the same stream
+        dist = _distances(grid, start, goal)
+        order = heuristic_orders(dist.dist, rules, seed)
     R = 1 if order is None else int(order.shape[1])
-    _native.lib()
-    grid = g.to(torch.uint8).contiguous().to(dev)
-    start, goal = start.contiguous().to(dev), goal.contiguous().to(dev)
     order = order.contiguous().to(dev) if order is not None else None
     if team:
         out = empty_solutions(C, N, H, T, dev, R, W=W, team=True, workspace_bytes=workspace_bytes)
     else:
         out = empty_solutions(C, N, H, T, dev, R)
     out._keep = (grid, start, goal, order)              # inputs of the enqueued launches
+    if dist is not None:
+        out.distance, out.lower_makespan, out.lower_flowtime = dist.dist, dist.lower_makespan, dist.lower_flowtime
+        out.priorities = order
     enqueue_solve(grid, start, goal, order, out, _team=team)
     return out

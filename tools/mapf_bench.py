@@ -2,6 +2,7 @@
 
     python tools/mapf_bench.py [--reps 10] [--out profiles/mapf_solve.json] [--only NAME] [--cpu-cases 16]
     python tools/mapf_bench.py --team [--reps 10] [--out profiles/mapf_team_solve.json] [--only NAME] [--cpu-cases 2]
+    python tools/mapf_bench.py --priorities [--reps 10] [--out profiles/mapf_distance.json] [--only NAME]
 
 Configurations (random maps of tests/expert_cases.random_map at density 0.1, horizon 4 (H + W)): 512 cases x 10 agents
 on 20 x 20 with R = 1 and R = 4 orders, 256 x 20 on 20 x 20, 128 x 64 on 40 x 40.  Outputs and workspace are
@@ -16,6 +17,13 @@ one-wave call on inputs both accept, 128 x 64 on 40 x 40 (timed through BOTH cal
 by one workgroup from its first agent to its last, so a call lasts as long as its slowest case: us_per_step_or_hop = call
 time / (2 x the largest flowtime), the time of one forward search step or one walk-back hop (a flowtime of F means F steps
 forward and F hops back; commit, t_min scan and the per-case set-up are inside this figure, so it is an upper bound).
+
+--priorities: the planning orders ranked on the device from true goal distances (csrc/mapf_distance_kernels.hip) on the
+inputs of both lists above (each set of inputs once, through the call its list times it with).  Per configuration and
+per choice of orders -- None with R = 1 (the index order), None with R = 4 (the index order and three host-drawn
+permutations, mapf.default_orders), 'longest_first' (R = 1), 'mixed' with R = 4 -- the solved count and the time of the
+whole call (for the string forms: the distance, bounds and order launches and the solve, enqueued back to back), and
+the distance + bounds launches and the order launch timed on their own, with their share of the whole call.
 """
 import argparse
 import json
@@ -50,6 +58,61 @@ def timed(fn, reps, warmup=3):
     return t0.elapsed_time(t1) * 1e-3 / reps                           # seconds per call
 
 
+def priorities_records(a, mc, mapf, dev):
+    """--priorities: one record per distinct set of inputs of CONFIGS and TEAM_CONFIGS."""
+    records, seen = [], set()
+    for team, (name, C, N, side, _) in [(False, c) for c in CONFIGS] + [(True, c) for c in TEAM_CONFIGS]:
+        name = name.rsplit('_r', 1)[0]
+        if (a.only and name != a.only) or name in seen:
+            continue
+        seen.add(name)
+        rng = np.random.default_rng(C * N + side)
+        cases = mc.random_cases(rng, C, N, side, density=0.1)
+        T = mc.default_horizon(side, side)
+        grid = torch.from_numpy(np.stack([c[0] for c in cases])).to(dev)
+        start = torch.from_numpy(np.stack([c[1] for c in cases]).astype(np.int32)).to(dev)
+        goal = torch.from_numpy(np.stack([c[2] for c in cases]).astype(np.int32)).to(dev)
+        enqueue = mapf.enqueue_solve_team if team else mapf.enqueue_solve
+        dist = mapf.Distances(*(torch.empty(shape, dtype=torch.int32, device=dev) for shape in ((C, N), (C,), (C,))))
+        rec = {'config': name, 'call': 'gnnpp_mapf_team_solve' if team else 'gnnpp_mapf_solve', 'cases': C, 'agents': N,
+               'map': '%dx%d' % (side, side), 'T_max': T,
+               'what': 'HIP events, mean of %d calls after 3; outputs and orders preallocated' % a.reps}
+        rec['distances_ms'] = round(timed(lambda: mapf.enqueue_distances(grid, start, goal, dist), a.reps) * 1e3, 4)
+        torch.cuda.synchronize()
+        rec['unreachable_agents'] = int((dist.dist < 0).sum().item())
+        rec['lower_makespan_max'] = int(dist.lower_makespan.max().item())
+        for label, prio, R in (('none_r1', None, 1), ('none_r4', None, 4), ('longest_first', 'longest_first', 1),
+                               ('mixed_r4', 'mixed', 4)):
+            out = (mapf.empty_solutions(C, N, side, T, dev, R, W=side, team=True) if team
+                   else mapf.empty_solutions(C, N, side, T, dev, R))
+            if prio is None:
+                order = (torch.from_numpy(mapf.default_orders(C, N, R, 0).astype(np.int32)).to(dev) if R > 1 else None)
+                sec = timed(lambda: enqueue(grid, start, goal, order, out), a.reps)
+            else:
+                rules = [mapf.ORDER_RULES[r] for r in (['index', 'longest_first', 'shortest_first', 'hashed']
+                                                       if prio == 'mixed' else [prio])]
+                order = torch.empty((C, R, N), dtype=torch.int32, device=dev)
+                rec[label + '_orders_ms'] = round(timed(lambda: mapf.enqueue_orders(dist.dist, rules, 0, order),
+                                                        a.reps) * 1e3, 4)
+
+                def chain():
+                    mapf.enqueue_distances(grid, start, goal, dist)
+                    mapf.enqueue_orders(dist.dist, rules, 0, order)
+                    enqueue(grid, start, goal, order, out)
+                sec = timed(chain, a.reps)
+                rec[label + '_distance_and_order_share'] = round(
+                    (rec['distances_ms'] + rec[label + '_orders_ms']) / (sec * 1e3), 4)
+            rec[label + '_ms_per_call'] = round(sec * 1e3, 4)
+            rec[label + '_solved'] = int((out.status == 0).sum().item())
+            flow = out.flowtime[out.status == 0]
+            rec[label + '_flowtime_mean_of_solved'] = round(float(flow.double().mean().item()), 1) if flow.numel() else None
+            del out, order
+            torch.cuda.empty_cache()
+        print(json.dumps(rec), flush=True)
+        records.append(rec)
+    return records
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=10)
@@ -57,6 +120,8 @@ def main():
     ap.add_argument('--only', default=None)
     ap.add_argument('--cpu-cases', type=int, default=None)
     ap.add_argument('--team', action='store_true')
+    ap.add_argument('--priorities', action='store_true',
+                    help='compare the planning orders: None, longest_first, mixed (see the module docstring)')
     a = ap.parse_args()
     if a.cpu_cases is None:
         a.cpu_cases = 2 if a.team else 16
@@ -64,8 +129,8 @@ def main():
     import mapf_cases as mc
     from gnn_pathplanning_amd import mapf
     dev = torch.device('cuda:0')
-    records = []
-    for name, C, N, side, R in (TEAM_CONFIGS if a.team else CONFIGS):
+    records = priorities_records(a, mc, mapf, dev) if a.priorities else []
+    for name, C, N, side, R in (() if a.priorities else TEAM_CONFIGS if a.team else CONFIGS):
         if a.only and name != a.only:
             continue
         rng = np.random.default_rng(C * N + side)
