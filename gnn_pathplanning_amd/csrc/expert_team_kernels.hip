@@ -16,7 +16,8 @@
 //
 // The degrees go through memory because the tiles of a step all need every agent's s: one workgroup per step for the
 // whole of S would leave a call of a few steps on a handful of compute units.
-// Squared distances are unsigned: a map of GNNPP_ROLLOUT_TEAM_MAX_CELLS cells can be 1 x 65536, (H-1)^2 + (W-1)^2 < 2^32.
+// Squared distances are unsigned (dist2_bound, dist2 of rollout_kernels.hip): a map of GNNPP_ROLLOUT_TEAM_MAX_CELLS
+// cells can be 1 x 65536, (H-1)^2 + (W-1)^2 < 2^32.
 // This file is included from gnnpp_api.hip after expert_kernels.hip and rollout_team_kernels.hip and uses their helpers.
 
 namespace gnnpp {
@@ -25,17 +26,6 @@ constexpr int kTeamGraphRows = 32;            // rows of S per workgroup of expe
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
-
-// the integer form of `distance < r` (dist2_threshold) as an unsigned bound; r > 0 so the threshold is >= 0
-__device__ __forceinline__ unsigned team_dist2_bound(double r) {
-    const long long T = dist2_threshold(r);
-    return T > 0xffffffffLL ? 0xffffffffu : T < 0 ? 0u : (unsigned)T;
-}
-
-__device__ __forceinline__ unsigned team_dist2(int ax, int ay, int bx, int by) {
-    const unsigned dx = (unsigned)(ax - bx), dy = (unsigned)(ay - by);
-    return dx * dx + dy * dy;
-}
 
 __host__ __device__ inline size_t expert_team_scan_smem(int N) { return round16((size_t)8 * N) + 3 * kTeamWords * 8; }
 
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(1024) void expert_team_scan_kernel(const ScheduleAr
         unsigned built = 0;
         bool have = false;
         for (;;) {
-            const unsigned Tu = team_dist2_bound(r);
+            const unsigned Tu = dist2_bound(r);
             if (!have || Tu != built) {                          // same threshold = same graph: still disconnected
                 have = true;
                 built = Tu;
@@ -96,7 +86,7 @@ __global__ __launch_bounds__(1024) void expert_team_scan_kernel(const ScheduleAr
                         for (int w = 0; w < nw && !join; ++w) {
                             for (unsigned long long f = fr[cur][w]; f; f &= f - 1) {
                                 const int j = w * 64 + __ffsll((long long)f) - 1;
-                                if (team_dist2(px[j], py[j], mx, my) <= Tu) { join = true; break; }
+                                if (dist2(px[j], py[j], mx, my) <= Tu) { join = true; break; }
                             }
                         }
                     }
@@ -135,9 +125,9 @@ __global__ __launch_bounds__(1024) void expert_team_degree_kernel(const Schedule
     if (live) { mx = pos[2 * a]; my = pos[2 * a + 1]; px[a] = mx; py[a] = my; }
     __syncthreads();
     if (!live) return;
-    const unsigned Tu = team_dist2_bound(p.radius[c]);
+    const unsigned Tu = dist2_bound(p.radius[c]);
     int deg = 0;
-    for (int j = 0; j < N; ++j) deg += j != a && team_dist2(px[j], py[j], mx, my) <= Tu;
+    for (int j = 0; j < N; ++j) deg += j != a && dist2(px[j], py[j], mx, my) <= Tu;
     inv_ws[(size_t)t * N + a] = deg ? sqrt(1.0 / (double)deg) : 0.0;
     const bool last = t + 1 >= p.case_start[c + 1] || t + 1 >= p.T_total;
     const int* nxt = last ? p.goal + (size_t)c * N * 2 : pos + 2 * N;
@@ -167,7 +157,7 @@ __global__ __launch_bounds__(256) void expert_team_graph_kernel(const ScheduleAr
     const double* inv_g = inv_ws + (size_t)t * N;
     for (int n = tid; n < N; n += 256) { px[n] = pos[2 * n]; py[n] = pos[2 * n + 1]; inv[n] = inv_g[n]; }
     __syncthreads();
-    const unsigned Tu = team_dist2_bound(p.radius[c]);
+    const unsigned Tu = dist2_bound(p.radius[c]);
     const int i0 = tile * kTeamGraphRows, rows = min(N, i0 + kTeamGraphRows) - i0;
     float* S = p.S + ((size_t)t * N + i0) * N;
     double* S64 = p.S64 ? p.S64 + ((size_t)t * N + i0) * N : nullptr;
@@ -186,7 +176,7 @@ __global__ __launch_bounds__(256) void expert_team_graph_kernel(const ScheduleAr
             double v[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                v[e] = (i != j + e && team_dist2(jx[e], jy[e], ix, iy) <= Tu) ? ii * ij[e] : 0.0;
+                v[e] = (i != j + e && dist2(jx[e], jy[e], ix, iy) <= Tu) ? ii * ij[e] : 0.0;
             const v4f o = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
             *reinterpret_cast<v4f*>(S + (size_t)r * N + j) = o;
             if (S64) {
@@ -200,7 +190,7 @@ __global__ __launch_bounds__(256) void expert_team_graph_kernel(const ScheduleAr
     } else {
         for (; r < rows; r += dr) {
             const int i = i0 + r;
-            const double v = (i != u && team_dist2(px[u], py[u], px[i], py[i]) <= Tu) ? inv[i] * inv[u] : 0.0;
+            const double v = (i != u && dist2(px[u], py[u], px[i], py[i]) <= Tu) ? inv[i] * inv[u] : 0.0;
             S[(size_t)r * N + u] = (float)v;
             if (S64) S64[(size_t)r * N + u] = v;
             u += du;

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kListCols) void expert_team_lists_kernel(const Sche
     }
     __syncthreads();
     if (n >= N) return;
-    const unsigned Tu = team_dist2_bound(p.radius[c]);
+    const unsigned Tu = dist2_bound(p.radius[c]);
     const size_t col = (size_t)t * N + n;
     unsigned short* il = idx_out + col * cap;                    // 8-byte aligned (cap % 4 == 0)
     float* wl = val_out + col * cap;                             // 16-byte aligned
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kListCols) void expert_team_lists_kernel(const Sche
 #pragma unroll 4
     for (int i = 0; i < N; ++i) {
         const v2i q = pl[i];
-        if (i != n && team_dist2(q[0], q[1], me[0], me[1]) <= Tu) {
+        if (i != n && dist2(q[0], q[1], me[0], me[1]) <= Tu) {
             pk = (pk >> 16) | ((unsigned long long)i << 48);
             const v4f s = {w[1], w[2], w[3], (float)(inv[i] * sn)};
             w = s;

@@ -207,6 +207,21 @@ __device__ __forceinline__ long long dist2_threshold(double R) {
     return t;
 }
 
+// The threshold as the unsigned bound every `d2 <= T` test compares against, and the squared distance of two cells in
+// the same unsigned word.  Coordinates lie in [0, 65535] (a map of 65 536 cells can be 1 x 65 536), so
+// d2 <= 65535^2 + 0^2 = 4 294 836 225 < 2^32 - 1: neither the products nor the sum wrap, and the clamp to 0xffffffff
+// never cuts a threshold below a distance that occurs.  r <= 0: the threshold is -1 and the bound 0 (no pair is at
+// distance 0: agents stand on distinct cells).
+__device__ __forceinline__ unsigned dist2_bound(double r) {
+    const long long T = dist2_threshold(r);
+    return T > 0xffffffffLL ? 0xffffffffu : T < 0 ? 0u : (unsigned)T;
+}
+
+__device__ __forceinline__ unsigned dist2(int ax, int ay, int bx, int by) {
+    const unsigned dx = (unsigned)(ax - bx), dy = (unsigned)(ay - by);
+    return dx * dx + dy * dy;
+}
+
 constexpr int kGsoSmemBytes = 2 * kMaxAgents * 8 + kMaxAgents * 8 + 32;   // adj [N][2] | inv [N] | radius, flag
 
 // Communication graph of one episode on ONE wavefront (lane l: agents l and l + 64), registers only:
@@ -238,17 +253,17 @@ __device__ __forceinline__ void gso_wave0(const RolloutArgs& p, const int* pos, 
     unsigned long long a0[2] = {0ull, 0ull}, a1[2] = {0ull, 0ull};                 // my agents' rows
     if (grow) r = r / 1.1;
     int connected = 0;
+    // Termination with grow: r grows by 1.1 per trip, so the bound reaches 65535^2 (the largest d2 of two cells, below
+    // the clamp of dist2_bound) after finitely many trips; from then on every pair is an edge and the graph is connected.
     for (;;) {
         if (grow) r = r * 1.1;
-        const long long T = dist2_threshold(r);
-        const int Ti = T > 0x7fffffffLL ? 0x7fffffff : (int)T;       // d2 < 2^18 on a 256 x 256 map
+        const unsigned Tu = dist2_bound(r);              // d2 < 2^32 - 1: coordinates in [0, 65535]
         for (int i = 0; i < N; ++i) {
             const int bx = lane_get(px, i), by = lane_get(py, i);
             bool e[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const int dx = px[h] - bx, dy = py[h] - by;
-                e[h] = live[h] && lane + 64 * h != i && dx * dx + dy * dy <= Ti;
+                e[h] = live[h] && lane + 64 * h != i && dist2(px[h], py[h], bx, by) <= Tu;
             }
             const MaskPair row = ballot2(e[0], two && e[1]);
             if (lane == (i & 63)) {
@@ -301,15 +316,13 @@ __device__ __forceinline__ void gso_all_waves(const RolloutArgs& p, const int* p
         px[h] = live[h] ? pos[2 * n] : -(1 << 20);
         py[h] = live[h] ? pos[2 * n + 1] : -(1 << 20);
     }
-    const long long T = dist2_threshold(r);
-    const int Ti = T > 0x7fffffffLL ? 0x7fffffff : (int)T;
+    const unsigned Tu = dist2_bound(r);
     for (int i = wave; i < N; i += nw) {
         const int bx = lane_get(px, i), by = lane_get(py, i);
         bool e[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const int dx = px[h] - bx, dy = py[h] - by;
-            e[h] = live[h] && lane + 64 * h != i && dx * dx + dy * dy <= Ti;
+            e[h] = live[h] && lane + 64 * h != i && dist2(px[h], py[h], bx, by) <= Tu;
         }
         const MaskPair row = ballot2(e[0], two && e[1]);
         if (lane == 0) { adj[2 * i] = row.lo; adj[2 * i + 1] = row.hi; }
@@ -504,9 +517,11 @@ __device__ __forceinline__ int next_set_bit(MaskPair m, int from) {
 //           duplicates can only appear at those cells -- a ballot per stopped agent adds them;
 //   loop 2: list_nextpos is a snapshot and nxt only ever changes to cur, which cannot create a swap.
 // When nothing is marked the call is the no-op the reference's would be, and returns False.
-// (row, col) of a cell as one comparable word; dead lanes carry distinct negative dummies, maps are at
-// most 256 x 256 (the occupancy grid lives in LDS), so keys never collide
-__device__ __forceinline__ int cell_key(int x, int y) { return x * 65536 + y; }
+// (row, col) of a cell as one comparable word, row * 65536 + col modulo 2^32 (rows and columns <= 65535).  Dead lanes
+// carry the distinct dummies (-1 - n, -1 - n), n < 128: the word of row 65534 - n, column 65535 - n.  A map has at most
+// 65 536 cells, so a cell with a column >= 65408 lies in row 0 (a larger map, which only the stand-alone move accepts,
+// has H, W <= 32767): keys never collide.
+__device__ __forceinline__ int cell_key(int x, int y) { return (int)(((unsigned)x << 16) + (unsigned)y); }
 
 template <bool two>
 __device__ __forceinline__ MaskPair ballot_eq(const int (&key)[2], int value) {

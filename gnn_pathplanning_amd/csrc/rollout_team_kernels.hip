@@ -358,12 +358,13 @@ __global__ __launch_bounds__(1024) void rollout_team_gso_kernel(const RolloutArg
     __syncthreads();
     double r = p.radius[b];
     if (grow) r = r / 1.1;
-    int Ti = 0;
+    unsigned Tu = 0u;
     bool connected = false;
+    // Termination with grow: r grows by 1.1 per trip, so the bound reaches 65535^2 (the largest d2 of two cells, below
+    // the clamp of dist2_bound) after finitely many trips; from then on every pair is an edge and the graph is connected.
     for (;;) {
         if (grow) r = r * 1.1;
-        const long long T = dist2_threshold(r);
-        Ti = T > 0x7fffffffLL ? 0x7fffffff : (int)T;    // d2 < 2^17 on a map of 65 536 cells
+        Tu = dist2_bound(r);                             // d2 < 2^32 - 1: a map of 65 536 cells can be 1 x 65 536
         bool in_r = t == 0;                              // reached set; the frontier starts as {0}
         int cur = 0;
         {
@@ -377,8 +378,7 @@ __global__ __launch_bounds__(1024) void rollout_team_gso_kernel(const RolloutArg
                 for (int w = 0; w < nw && !join; ++w) {
                     for (unsigned long long f = fr[cur][w]; f; f &= f - 1) {
                         const int j = w * 64 + __ffsll((long long)f) - 1;
-                        const int dx = px[j] - mx, dy = py[j] - my;
-                        if (dx * dx + dy * dy <= Ti) { join = true; break; }
+                        if (dist2(px[j], py[j], mx, my) <= Tu) { join = true; break; }
                     }
                 }
             }
@@ -396,10 +396,7 @@ __global__ __launch_bounds__(1024) void rollout_team_gso_kernel(const RolloutArg
     }
     if (live) {
         int deg = 0;
-        for (int j = 0; j < N; ++j) {
-            const int dx = px[j] - mx, dy = py[j] - my;
-            deg += j != t && dx * dx + dy * dy <= Ti;
-        }
+        for (int j = 0; j < N; ++j) deg += j != t && dist2(px[j], py[j], mx, my) <= Tu;
         inv[t] = deg ? sqrt(1.0 / (double)deg) : 0.0;
     }
     __syncthreads();
@@ -408,10 +405,8 @@ __global__ __launch_bounds__(1024) void rollout_team_gso_kernel(const RolloutArg
     for (int j = t; j < N; j += nt) {
         const int jx = px[j], jy = py[j];
         const double ij = inv[j];
-        for (int i = 0; i < N; ++i) {
-            const int dx = px[i] - jx, dy = py[i] - jy;
-            S[(size_t)i * N + j] = (i != j && dx * dx + dy * dy <= Ti) ? (float)(inv[i] * ij) : 0.f;
-        }
+        for (int i = 0; i < N; ++i)
+            S[(size_t)i * N + j] = (i != j && dist2(px[i], py[i], jx, jy) <= Tu) ? (float)(inv[i] * ij) : 0.f;
     }
     if (t == 0) {
         p.radius[b] = r;

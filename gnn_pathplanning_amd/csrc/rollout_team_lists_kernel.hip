@@ -3,7 +3,7 @@
 // the N^2 floats of a dense S.  Any 1 <= N <= GNNPP_ROLLOUT_MAX_TEAM.
 //
 // One workgroup per episode, thread t = agent t = column t (the relation is symmetric: column t is row t).  The same
-// statement as rollout_team_gso_kernel -- the same dist2_threshold, the same /= 1.1 then *= 1.1 growth sequence,
+// statement as rollout_team_gso_kernel -- the same dist2_bound, the same /= 1.1 then *= 1.1 growth sequence,
 // inv = sqrt(1.0 / deg) in fp64, weight (float)(inv[i] * inv[n]) -- in the order the lists invite:
 //   1. the positions go to LDS;
 //   2. thread t scans i = 0 .. N-1 in ascending order (every thread reads the same cell: an LDS broadcast) and
@@ -50,14 +50,15 @@ __global__ __launch_bounds__(1024) void rollout_team_lists_kernel(const RolloutA
     __syncthreads();
     double r = p.radius[b];
     if (grow) r = r / 1.1;
-    int Ti = 0, cnt = 0;
+    unsigned Tu = 0u;
+    int cnt = 0;
     bool built = false, connected = false;
+    // Termination with grow: as in rollout_team_gso_kernel (the bound reaches 65535^2, the largest d2 of two cells).
     for (;;) {
         if (grow) r = r * 1.1;
-        const long long T = dist2_threshold(r);
-        const int Tn = T > 0x7fffffffLL ? 0x7fffffff : (int)T;   // d2 < 2^17 on a map of 65 536 cells
-        if (!built || Tn != Ti) {                        // (workgroup-uniform)
-            Ti = Tn;
+        const unsigned Tn = dist2_bound(r);              // d2 < 2^32 - 1: a map of 65 536 cells can be 1 x 65 536
+        if (!built || Tn != Tu) {                        // (workgroup-uniform)
+            Tu = Tn;
             built = true;
             cnt = 0;
             if (live) {
@@ -65,8 +66,7 @@ __global__ __launch_bounds__(1024) void rollout_team_lists_kernel(const RolloutA
 #pragma unroll 4
                 for (int i = 0; i < N; ++i) {
                     const v2i q = pl[i];
-                    const int dx = q[0] - mx, dy = q[1] - my;
-                    if (i != t && dx * dx + dy * dy <= Ti) {
+                    if (i != t && dist2(q[0], q[1], mx, my) <= Tu) {
                         pk = (pk >> 16) | ((unsigned long long)i << 48);
                         ++cnt;
                         if ((cnt & 3) == 0) {

@@ -539,8 +539,12 @@ int gnnpp_lsigf_team_lists_input_grad(const float* dy, const void* lists_t, cons
  * is the largest square) at every team size, and answer GNNPP_ERR_UNSUPPORTED with nothing enqueued beyond it.  Up to
  * that limit no accepted call answers GNNPP_ERR_LAUNCH for its LDS: the launchers raise their kernels' dynamic LDS
  * limit above the default 64 KB (66 560 bytes for observe / gso_observe, 72 736 for step).  gnnpp_rollout_move and
- * gnnpp_rollout_gso have no map limit of their own (move reads the map from memory; cells are compared as
- * row * 65 536 + column, so H, W <= 32 767), and gnnpp_rollout_policy_step(s) has a smaller one, stated below. */
+ * gnnpp_rollout_gso have no map limit of their own (move reads the map from memory), and gnnpp_rollout_policy_step(s)
+ * has a smaller one, stated below.
+ * Coordinates.  At every team size rows and columns lie in [0, 65 535]: a map of GNNPP_ROLLOUT_TEAM_MAX_CELLS cells may
+ * be 1 x 65 536 or 65 536 x 1.  Squared distances are compared as unsigned 32-bit words (65 535^2 + 0^2 < 2^32 - 1) and
+ * cells as row * 65 536 + column modulo 2^32, both exact on that range; H, W > 65 536 is outside the contract
+ * (gnnpp_rollout_move on a map of more than GNNPP_ROLLOUT_TEAM_MAX_CELLS cells, which it alone accepts: H, W <= 32 767). */
 #define GNNPP_ROLLOUT_MAX_AGENTS 128
 #define GNNPP_ROLLOUT_MAX_TEAM 1024
 #define GNNPP_ROLLOUT_TEAM_MAX_CELLS 65536

@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE ONLY: the one-wave simulator (csrc/rollout_kernels.hip: teams of at most 128 agents) at its map and
 team-size edges.  Each case is built once here, with the facts the sequential oracle's answer must show, and runs through
 ONE runner that takes a backend: the host emulation (tests/test_emu_rollout_sim.py) and the device
-(tests/test_gpu_rollout_sim_cases.py).  A plain helper module, not a conftest.
+(tests/test_gpu_rollout_sim_cases.py).  A plain helper module, not a conftest.  The runner serves both simulators:
+tests/rollout_team_sim_cases.py brings the cases of the large-team kernels (N > 128) to it.
 
 A case is dict(name, grids [B,H,W] or [H,W] (shared), starts / goals [B,N,2], maxstep [B], actions [T,B,N] (T <= 4),
 radius, grow, grid_skew (bytes the map pointer is moved off its 64-byte alignment), check(case, trace)).
