@@ -15,6 +15,7 @@
 #include "mapf_kernels.hip"          // prioritized-planning MAPF solver (the expert of the online loop)
 #include "mapf_team_kernels.hip"     // ... for teams of up to 1024 agents on maps of up to 256 x 256 (one workgroup per case)
 #include "mapf_distance_kernels.hip" // ... its planning orders: true goal distances and the orders ranked from them
+#include "casegen_kernels.hip"       // ... its cases: connected random maps with start and goal pairs, from a seed
 #include "encoder_kernel_h2.hip"
 #include "encoder_kernel_b3.hip"
 #include "lsigf_kernel.hip"
@@ -890,6 +891,30 @@ int gnnpp_mapf_orders(const int* dist, int C, int N, int R, const int* rules, un
             return GNNPP_ERR_ARG;
     }
     return mapf_order_launch(dist, C, N, R, rules, seed, order, static_cast<hipStream_t>(stream));
+}
+
+// include/gnnpp_casegen.h: checked in gnnpp_mapf_distances' order, nothing is enqueued on an error
+int gnnpp_casegen(const unsigned char* grid_in, int grid_in_batched, unsigned obstacle_threshold, unsigned seed, int C,
+                  int N, int H, int W, unsigned char* grid, int* start, int* goal, int* cells, int* status, void* stream) {
+    if (!grid || !start || !goal || !cells || !status || C <= 0 || N <= 0 || N > GNNPP_ROLLOUT_MAX_TEAM || H <= 0 ||
+        W <= 0 || (long long)C * N > 0x7fffffffLL)
+        return GNNPP_ERR_ARG;
+    if (H > GNNPP_MAPF_TEAM_MAX_SIDE || W > GNNPP_MAPF_TEAM_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
+    CasegenArgs a;
+    a.grid_in = grid_in;
+    a.grid_in_batched = grid_in_batched;
+    a.threshold = obstacle_threshold;
+    a.seed = seed;
+    a.C = C;
+    a.N = N;
+    a.H = H;
+    a.W = W;
+    a.grid = grid;
+    a.start = start;
+    a.goal = goal;
+    a.cells = cells;
+    a.status = status;
+    return casegen_launch(a, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
     python tools/mapf_bench.py [--reps 10] [--out profiles/mapf_solve.json] [--only NAME] [--cpu-cases 16]
     python tools/mapf_bench.py --team [--reps 10] [--out profiles/mapf_team_solve.json] [--only NAME] [--cpu-cases 2]
     python tools/mapf_bench.py --priorities [--reps 10] [--out profiles/mapf_distance.json] [--only NAME]
+    python tools/mapf_bench.py --generated [--reps 10] [--out profiles/casegen.json] [--only NAME] [--cpu-cases 2]
 
 Configurations (random maps of tests/expert_cases.random_map at density 0.1, horizon 4 (H + W)): 512 cases x 10 agents
 on 20 x 20 with R = 1 and R = 4 orders, 256 x 20 on 20 x 20, 128 x 64 on 40 x 40.  Outputs and workspace are
@@ -24,6 +25,12 @@ per choice of orders -- None with R = 1 (the index order), None with R = 4 (the 
 permutations, mapf.default_orders), 'longest_first' (R = 1), 'mixed' with R = 4 -- the solved count and the time of the
 whole call (for the string forms: the distance, bounds and order launches and the solve, enqueued back to back), and
 the distance + bounds launches and the order launch timed on their own, with their share of the whole call.
+
+--generated: the configurations of --priorities on cases GENERATED on the device (casegen.generate, csrc/casegen_kernels.hip)
+at the same density, next to the host-drawn cases of the same configuration: the time of one gnnpp_casegen call (HIP
+events, outputs preallocated), the agents with dist < 0 (0 by construction on generated cases: asserted), and the solved
+counts under None (the index order), 'longest_first' and 'mixed' with R = 4 for both kinds of cases.  Beside the call's
+time: the numpy / queue yardstick (tests/casegen_cases.py) on the first --cpu-cases cases, on one host core, as context.
 """
 import argparse
 import json
@@ -113,6 +120,53 @@ def priorities_records(a, mc, mapf, dev):
     return records
 
 
+def generated_records(a, mc, mapf, dev):
+    """--generated: one record per distinct set of inputs of CONFIGS and TEAM_CONFIGS."""
+    import casegen_cases as cc
+    from gnn_pathplanning_amd import casegen
+    records, seen = [], set()
+    for team, (name, C, N, side, _) in [(False, c) for c in CONFIGS] + [(True, c) for c in TEAM_CONFIGS]:
+        name = name.rsplit('_r', 1)[0]
+        if (a.only and name != a.only) or name in seen:
+            continue
+        seen.add(name)
+        seed = C * N + side
+        cases = mc.random_cases(np.random.default_rng(seed), C, N, side, density=0.1)
+        drawn = tuple(torch.from_numpy(np.stack([c[k] for c in cases]).astype(np.uint8 if k == 0 else np.int32)).to(dev)
+                      for k in range(3))
+        out = casegen.empty_cases(C, N, side, side, dev)
+        sec = timed(lambda: casegen.enqueue_generate(out, density=0.1, seed=seed), a.reps)
+        torch.cuda.synchronize()
+        rec = {'config': name, 'call': 'gnnpp_casegen', 'cases': C, 'agents': N, 'map': '%dx%d' % (side, side),
+               'density': 0.1, 'seed': seed,
+               'what': 'HIP events, mean of %d calls after 3; outputs preallocated' % a.reps,
+               'casegen_ms_per_call': round(sec * 1e3, 4), 'casegen_cases_per_s': round(C / sec),
+               'too_small_cases': int((out.status != 0).sum().item()),
+               'cells_min': int(out.cells.min().item()), 'cells_mean': round(float(out.cells.double().mean().item()), 1),
+               'obstacles_mean': round(float(out.grid.sum((1, 2)).double().mean().item()), 1)}
+        k = min(a.cpu_cases, C)
+        t0 = time.perf_counter()
+        want = cc.generate(k, N, side, side, casegen.threshold_of(0.1), seed) if k else None
+        rec['cpu_yardstick_cases_per_s'] = round(k / (time.perf_counter() - t0), 2) if k else None
+        rec['cpu_yardstick_cases_timed'] = k
+        rec['cpu_yardstick_agrees'] = all(np.array_equal(getattr(out, key)[:k].cpu().numpy(), want[key])
+                                          for key in cc.OUTPUTS) if k else None
+        solve = mapf.solve_team if team else mapf.solve
+        for kind, (grid, start, goal) in (('generated', (out.grid, out.start, out.goal)), ('host_drawn', drawn)):
+            d = mapf.distances(grid, start, goal, dev)
+            rec[kind + '_agents_without_path'] = int((d.dist < 0).sum().item())
+            rec[kind + '_cases_with_such_an_agent'] = int((d.dist < 0).any(1).sum().item())
+            for label, prio, R in (('none_r1', None, 1), ('longest_first', 'longest_first', 1), ('mixed_r4', 'mixed', 4)):
+                sol = solve(grid, start, goal, dev, restarts=R, priorities=prio)
+                rec['%s_%s_solved' % (kind, label)] = int((sol.status == 0).sum().item())
+                del sol
+                torch.cuda.empty_cache()
+        assert rec['generated_agents_without_path'] == 0, rec        # a condition of the contract, not a measurement
+        print(json.dumps(rec), flush=True)
+        records.append(rec)
+    return records
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=10)
@@ -122,15 +176,18 @@ def main():
     ap.add_argument('--team', action='store_true')
     ap.add_argument('--priorities', action='store_true',
                     help='compare the planning orders: None, longest_first, mixed (see the module docstring)')
+    ap.add_argument('--generated', action='store_true',
+                    help='the --priorities configurations on cases generated on the device (see the module docstring)')
     a = ap.parse_args()
     if a.cpu_cases is None:
-        a.cpu_cases = 2 if a.team else 16
+        a.cpu_cases = 2 if a.team or a.generated else 16
     assert torch.cuda.is_available(), 'needs the MI355X: a CPU run measures nothing'
     import mapf_cases as mc
     from gnn_pathplanning_amd import mapf
     dev = torch.device('cuda:0')
-    records = priorities_records(a, mc, mapf, dev) if a.priorities else []
-    for name, C, N, side, R in (() if a.priorities else TEAM_CONFIGS if a.team else CONFIGS):
+    records = (priorities_records(a, mc, mapf, dev) if a.priorities else
+               generated_records(a, mc, mapf, dev) if a.generated else [])
+    for name, C, N, side, R in (() if a.priorities or a.generated else TEAM_CONFIGS if a.team else CONFIGS):
         if a.only and name != a.only:
             continue
         rng = np.random.default_rng(C * N + side)
