@@ -28,6 +28,7 @@ H2_UNSAFE_MARK = LIB_PATH + '.split_f16_disabled'
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp.h')
 MAPF_DISTANCE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_distance.h')
 CASEGEN_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_casegen.h')
+MAPF_AUDIT_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_audit.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
@@ -61,6 +62,11 @@ MAPF_DIST_UNREACHABLE, MAPF_DIST_INVALID = -1, -2
 MAPF_ORDER_INDEX, MAPF_ORDER_LONGEST_FIRST, MAPF_ORDER_SHORTEST_FIRST, MAPF_ORDER_HASHED = 0, 1, 2, 3
 # include/gnnpp_casegen.h (GNNPP_CASEGEN_*)
 CASEGEN_OK, CASEGEN_TOO_SMALL = 0, 1
+# include/gnnpp_mapf_audit.h (GNNPP_MAPF_AUDIT_*): the seam constant, the class indices, the status bits
+MAPF_AUDIT_CHUNK = 32
+MAPF_AUDIT_CLASS_STATE, MAPF_AUDIT_CLASS_VERTEX, MAPF_AUDIT_CLASS_MOVE, MAPF_AUDIT_CLASS_SWAP = 0, 1, 2, 3
+MAPF_AUDIT_STATE, MAPF_AUDIT_VERTEX, MAPF_AUDIT_MOVE, MAPF_AUDIT_SWAP = 1, 2, 4, 8
+MAPF_AUDIT_BAD_START, MAPF_AUDIT_NOT_AT_GOAL, MAPF_AUDIT_SKIPPED = 16, 32, 64
 # csrc/gnnpp_measure.h: keys that exist in the -DGNNPP_MEASURE build only (libgnnpp.so answers GNNPP_ERR_ARG)
 TUNE_FILTER_ABLATE, TUNE_ENCODER_STOP = 3, 4
 PRECISIONS = {'fp32': PREC_FP32, 'fp32_mfma': PREC_FP32_MFMA, 'split_f16': PREC_SPLIT_F16}
@@ -85,7 +91,8 @@ def precision_code(p):
 
 
 def _sources():
-    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [HEADER, MAPF_DISTANCE_HEADER, CASEGEN_HEADER]
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [HEADER, MAPF_DISTANCE_HEADER, CASEGEN_HEADER,
+                                                                          MAPF_AUDIT_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -318,16 +325,23 @@ MAPF_DISTANCE_SIGNATURES = {
 CASEGEN_SIGNATURES = {
     'gnnpp_casegen': (_ci, [_vp, _ci, ctypes.c_uint, ctypes.c_uint, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# include/gnnpp_mapf_audit.h, the companion header of the schedule audit: a table of its own for the same reason
+# (tests/test_mapf_audit_abi.py)
+MAPF_AUDIT_SIGNATURES = {
+    'gnnpp_mapf_audit_workspace_bytes': (_cs, [_ci] * 3),
+    'gnnpp_mapf_audit': (_ci, [_vp, _ci] + [_vp] * 4 + [_ci] * 5 + [_vp] * 7 + [_cs, _vp]),
+}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
 MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 
 
 def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
-    build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES and CASEGEN_SIGNATURES; returns the library."""
+    build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES and MAPF_AUDIT_SIGNATURES; returns the
+    library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
-            list(CASEGEN_SIGNATURES.items()) + optional:
+            list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

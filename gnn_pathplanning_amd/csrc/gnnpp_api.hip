@@ -16,6 +16,7 @@
 #include "mapf_team_kernels.hip"     // ... for teams of up to 1024 agents on maps of up to 256 x 256 (one workgroup per case)
 #include "mapf_distance_kernels.hip" // ... its planning orders: true goal distances and the orders ranked from them
 #include "casegen_kernels.hip"       // ... its cases: connected random maps with start and goal pairs, from a seed
+#include "mapf_audit_kernels.hip"    // ... its checker: conflicts, arrivals and costs of any schedule
 #include "encoder_kernel_h2.hip"
 #include "encoder_kernel_b3.hip"
 #include "lsigf_kernel.hip"
@@ -915,6 +916,51 @@ int gnnpp_casegen(const unsigned char* grid_in, int grid_in_batched, unsigned ob
     a.cells = cells;
     a.status = status;
     return casegen_launch(a, static_cast<hipStream_t>(stream));
+}
+
+// include/gnnpp_mapf_audit.h: sizes (GNNPP_ERR_ARG), the supported map size, the horizon, pointers, the workspace; nothing
+// is enqueued on an error
+static int mapf_audit_sizes(int C, int N, int H, int W, int T_max) {
+    if (C <= 0 || N <= 0 || N > GNNPP_ROLLOUT_MAX_TEAM || H <= 0 || W <= 0) return GNNPP_ERR_ARG;
+    if (H > GNNPP_MAPF_TEAM_MAX_SIDE || W > GNNPP_MAPF_TEAM_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
+    if (T_max < 0 || T_max > GNNPP_MAPF_TEAM_MAX_STEPS || (long long)C * mapf_audit_chunks(T_max) > 0x7fffffffLL)
+        return GNNPP_ERR_ARG;
+    return GNNPP_OK;
+}
+
+size_t gnnpp_mapf_audit_workspace_bytes(int C, int N, int T_max) {
+    if (mapf_audit_sizes(C, N, 1, 1, T_max) != GNNPP_OK) return 0;
+    return mapf_audit_ws_bytes(C, N, T_max);
+}
+
+int gnnpp_mapf_audit(const unsigned char* grid, int grid_batched, const int* start, const int* goal, const int* schedule,
+                     const int* steps, int C, int N, int H, int W, int T_max, int* status, int* arrival, int* makespan,
+                     int* flowtime, int* counts, int* first, void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = mapf_audit_sizes(C, N, H, W, T_max);
+    if (rc != GNNPP_OK) return rc;
+    if (!grid || !goal || !schedule || !status || !arrival || !makespan || !flowtime || !counts || !first || !workspace)
+        return GNNPP_ERR_ARG;
+    if (workspace_bytes < mapf_audit_ws_bytes(C, N, T_max)) return GNNPP_ERR_ARG;
+    MapfAuditArgs a;
+    a.grid = grid;
+    a.grid_batched = grid_batched;
+    a.start = start;
+    a.goal = goal;
+    a.schedule = schedule;
+    a.steps = steps;
+    a.C = C;
+    a.N = N;
+    a.H = H;
+    a.W = W;
+    a.T_max = T_max;
+    a.status = status;
+    a.arrival = arrival;
+    a.makespan = makespan;
+    a.flowtime = flowtime;
+    a.counts = counts;
+    a.first = first;
+    a.ws = static_cast<int*>(workspace);
+    return mapf_audit_launch(a, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -138,15 +138,19 @@ def team_output_bytes(T_total, N, keep_fp64_gso=False):
     return T_total * N * (1452 + 4 * N + 20) + (8 * N * N * T_total if keep_fp64_gso else 0)
 
 
-def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False):
+def samples_from_schedules(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False, audit=False):
     """grids [C,H,W] or [H,W] (1 = obstacle); goals [C,N,2]; schedules: list of C arrays [T_c,N,2] (states of a solved
     case, agents that arrived waiting on their goal) -> ScheduleSamples.  A schedule with a move that is not one of
     the five actions, or a state off the map / on an obstacle, raises GnnppError naming the case (the reference dies
-    with ValueError there); this reads the per-case status back, the only host synchronisation."""
-    return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, False)
+    with ValueError there); this reads the per-case status back, the only host synchronisation.
+    audit=True: the schedules first go through mapf.audit (without a start check), which also looks at two agents at once:
+    a vertex or swap conflict, or an agent that does not end on its goal, raises GnnppError naming the case, the class,
+    t and the agents before any sample is built (one more read of a status).  The default changes nothing."""
+    return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, False, audit=audit)
 
 
-def samples_from_schedules_team(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False, graph='dense'):
+def samples_from_schedules_team(grids, goals, schedules, device, commR=5.0, keep_fp64_gso=False, graph='dense',
+                                audit=False):
     """samples_from_schedules for teams of 2 to MAX_TEAM = 1024 agents on maps of up to 65 536 cells: same arguments,
     same ScheduleSamples (the same bytes for every team both take), same errors naming the bad case.  The outputs are
     team_output_bytes(T, N, keep_fp64_gso) bytes; a call that would not fit the device's free memory raises GnnppError
@@ -155,13 +159,13 @@ def samples_from_schedules_team(grids, goals, schedules, device, commR=5.0, keep
     is None) and no [N,N] matrix is written: gnnpp_schedule_team_plan, the host read of the cases' status and the steps'
     largest degrees, cap = that maximum rounded up to 4, then gnnpp_schedule_team_fill_lists.  The outputs are
     team_lists_output_bytes(T, N, cap) bytes, checked against the free memory once cap is known.  SampleListPool takes
-    the result.  keep_fp64_gso is refused."""
+    the result.  keep_fp64_gso is refused.  audit=True: as for samples_from_schedules."""
     if graph not in ('dense', 'lists'):
         raise _native.GnnppError("unknown graph %r (one of ['dense', 'lists'])" % (graph,))
     if graph == 'lists' and keep_fp64_gso:
         raise _native.GnnppError("samples_from_schedules_team: graph='lists' keeps no dense GSO, keep_fp64_gso=True needs "
                                  "graph='dense'")
-    return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, True, graph == 'lists')
+    return _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, True, graph == 'lists', audit=audit)
 
 
 def _raise_if_flagged(bad, C):
@@ -174,7 +178,15 @@ def _raise_if_flagged(bad, C):
                                  % (c, C, ' and '.join(what), int(bad[c]), int((bad != 0).sum())))
 
 
-def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, team, lists=False):
+def _raise_if_audit_flagged(found, C):
+    status = found.status.cpu()
+    if bool((status != 0).any()):
+        c = int((status != 0).nonzero()[0])
+        raise _native.GnnppError('schedule of case %d (of %d) fails its audit: %s; %d case(s) flagged'
+                                 % (c, C, found.describe(c).split(': ', 1)[1], int((status != 0).sum())))
+
+
+def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gso, team, lists=False, audit=False):
     name = 'samples_from_schedules_team' if team else 'samples_from_schedules'
     dev = torch.device(device)
     if dev.type != 'cuda':
@@ -195,6 +207,9 @@ def _samples_from_schedules(grids, goals, schedules, device, commR, keep_fp64_gs
     for c, s in enumerate(sched):
         if s.dim() != 3 or s.shape[0] < 1 or tuple(s.shape[1:]) != (N, 2):
             raise _native.GnnppError('schedule %d must be [T,%d,2] with T >= 1 (got %s)' % (c, N, tuple(s.shape)))
+    if audit:
+        from . import mapf
+        _raise_if_audit_flagged(mapf.audit(g, None, goal, sched, dev), C)
     bounds = [0]
     for s in sched:
         bounds.append(bounds[-1] + int(s.shape[0]))
@@ -280,12 +295,13 @@ def solve_failures(rollout, results=None, **kw):
     return sol
 
 
-def samples_from_solutions(solutions, grids, goals, commR=5.0, team=False, graph='dense'):
+def samples_from_solutions(solutions, grids, goals, commR=5.0, team=False, graph='dense', audit=False):
     """(ScheduleSamples of the solved cases of a mapf.Solutions, their case ids numpy int64 [S]) through
     samples_from_schedules / enqueue_schedule_samples, or with team=True through samples_from_schedules_team (teams of
     up to MAX_TEAM agents, what mapf.solve_team plans; graph='lists' is passed on to it and needs team=True).
     grids [C,H,W] or [H,W] and goals [C,N,2]: the cases' maps and goals as solve() was given them (host or device).
-    Unsolved cases are left out (their ids are missing from the list); (None, empty ids) when no case was solved."""
+    Unsolved cases are left out (their ids are missing from the list); (None, empty ids) when no case was solved.
+    audit=True: the solved schedules are audited first, as for samples_from_schedules."""
     if not team and int(solutions.arrival.shape[1]) > MAX_AGENTS:
         raise _native.GnnppError('samples_from_solutions: samples are built for teams of at most %d agents; these '
                                  'solutions have %d (pass team=True: samples_from_schedules_team takes teams of up to '
@@ -304,9 +320,10 @@ def samples_from_solutions(solutions, grids, goals, commR=5.0, team=False, graph
     g = g.to(dev).index_select(0, idx) if g.dim() == 3 else g
     gl = (goals if torch.is_tensor(goals) else torch.as_tensor(np.asarray(goals))).to(dev).index_select(0, idx)
     sched = [solutions.schedules[c, :int(makespan[c]) + 1] for c in ids]
+    extra = {'audit': True} if audit else {}             # (the default call is the call it always was)
     if graph != 'dense':
-        return samples_from_schedules_team(g, gl, sched, dev, commR=commR, graph=graph), ids
-    return (samples_from_schedules_team if team else samples_from_schedules)(g, gl, sched, dev, commR=commR), ids
+        return samples_from_schedules_team(g, gl, sched, dev, commR=commR, graph=graph, **extra), ids
+    return (samples_from_schedules_team if team else samples_from_schedules)(g, gl, sched, dev, commR=commR, **extra), ids
 
 
 # ---- the files around the solver ---------------------------------------------------------------------

@@ -17,6 +17,11 @@ agent's true shortest-path distance from start to goal on its map, with the lowe
 follow; heuristic_orders() ranks planning orders from them on the device (longest first, shortest first, hashed);
 priorities='longest_first' | 'shortest_first' | 'mixed' of solve / solve_team enqueue both ahead of the solve on the
 same stream; maxstep_from_distances() turns the makespan bound into a rollout's step limit.
+
+The checker of all of it (include/gnnpp_mapf_audit.h, csrc/mapf_audit_kernels.hip): audit() says of any schedule in the
+solvers' layout -- their own, or another solver's read from a file -- whether it is a legal, collision-free plan that
+ends on the goals, with the agents' arrivals, the costs, the offences counted per class and the first one named;
+Solutions.audit() audits a call's own answer, quality() sets the costs against the distances' lower bounds.
 """
 import ctypes
 
@@ -30,6 +35,13 @@ MAX_TEAM, MAX_TEAM_SIDE, MAX_TEAM_STEPS = (_native.ROLLOUT_MAX_TEAM, _native.MAP
                                            _native.MAPF_TEAM_MAX_STEPS)
 NO_PATH, BAD_CASE = _native.MAPF_NO_PATH, _native.MAPF_BAD_CASE
 UNREACHABLE, INVALID = _native.MAPF_DIST_UNREACHABLE, _native.MAPF_DIST_INVALID         # (negative entries of dist)
+AUDIT_CHUNK = _native.MAPF_AUDIT_CHUNK
+AUDIT_STATE, AUDIT_VERTEX, AUDIT_MOVE, AUDIT_SWAP = (_native.MAPF_AUDIT_STATE, _native.MAPF_AUDIT_VERTEX,
+                                                     _native.MAPF_AUDIT_MOVE, _native.MAPF_AUDIT_SWAP)
+AUDIT_BAD_START, AUDIT_NOT_AT_GOAL, AUDIT_SKIPPED = (_native.MAPF_AUDIT_BAD_START, _native.MAPF_AUDIT_NOT_AT_GOAL,
+                                                     _native.MAPF_AUDIT_SKIPPED)
+AUDIT_CLASSES = ('a state off the map or on an obstacle', 'a vertex conflict', 'a move that is not one of the five actions',
+                 'a swap conflict')                      # by GNNPP_MAPF_AUDIT_CLASS_*
 ORDER_RULES = {'index': _native.MAPF_ORDER_INDEX, 'longest_first': _native.MAPF_ORDER_LONGEST_FIRST,
                'shortest_first': _native.MAPF_ORDER_SHORTEST_FIRST, 'hashed': _native.MAPF_ORDER_HASHED}
 
@@ -78,6 +90,57 @@ class Solutions:
             for t, (x, y) in enumerate(p):
                 lines += ['    - x: %d' % x, '      y: %d' % y, '      t: %d' % t]
         return '\n'.join(lines) + '\n'
+
+    def audit(self):
+        """The call's own schedules audited against the inputs it was given (kept in _keep), rows 0 .. makespan of every
+        solved case; an unsolved case (makespan -1) is reported as AUDIT_SKIPPED.  Enqueued behind the solve on the same
+        stream.  Returns Audit."""
+        grid, start, goal = self._keep[:3]
+        C, T1, N = (int(v) for v in self.schedules.shape[:3])
+        out = empty_audit(C, N, T1 - 1, self.schedules.device)
+        out._keep = (self,)
+        enqueue_audit(grid, start, goal, self.schedules, self.makespan, out)
+        return out
+
+
+class Audit:
+    """Device tensors of one audit call, all int32: status [C] (0: a legal, collision-free plan that ends on the goals;
+    else the OR of AUDIT_STATE, AUDIT_VERTEX, AUDIT_MOVE, AUDIT_SWAP, AUDIT_BAD_START, AUDIT_NOT_AT_GOAL, AUDIT_SKIPPED),
+    arrival [C,N], makespan / flowtime [C] (-1 when an agent does not end on its goal), counts [C,4] (flagged (step,
+    agent) pairs per class: state, vertex, move, swap), first [C,4] = (t, class, agent, other) of the first offence (-1
+    when there is none), and the workspace."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __len__(self):
+        return int(self.status.shape[0])
+
+    def ok(self):
+        """bool [C] on the host: the case's schedule is a legal, collision-free plan that ends on the goals."""
+        return (self.status == 0).cpu().numpy()
+
+    def describe(self, c):
+        """One line on case c: what was found first, where, and between whom."""
+        st = int(self.status[c])
+        if st == 0:
+            return 'case %d: a legal, collision-free plan (makespan %d, flowtime %d)' % (
+                c, int(self.makespan[c]), int(self.flowtime[c]))
+        if st & AUDIT_SKIPPED:
+            return 'case %d: skipped (no schedule to audit)' % c
+        parts = []
+        t, cls, agent, other = (int(v) for v in self.first[c].cpu().tolist())
+        if cls >= 0:
+            parts.append('%s at t = %d: agent %d%s (%s flagged)' % (
+                AUDIT_CLASSES[cls], t, agent, ' and agent %d' % other if other >= 0 else '',
+                ', '.join('%d x %s' % (n, w) for n, w in zip(self.counts[c].cpu().tolist(),
+                                                            ('state', 'vertex', 'move', 'swap')) if n)))
+        if st & AUDIT_BAD_START:
+            parts.append('an agent does not begin on its start')
+        if st & AUDIT_NOT_AT_GOAL:
+            away = (self.arrival[c] < 0).nonzero().flatten().tolist()
+            parts.append('agent %d does not end on its goal (%d agent(s))' % (away[0], len(away)))
+        return 'case %d: %s (status %d)' % (c, '; '.join(parts), st)
 
 
 def workspace_bytes(C, R, H, T):
@@ -163,6 +226,102 @@ def enqueue_solve_team(grid, start, goal, order, out):
     """enqueue_solve for teams of up to MAX_TEAM agents on maps of up to MAX_TEAM_SIDE rows and columns
     (gnnpp_mapf_team_solve); out: from empty_solutions(..., W=W, team=True)."""
     enqueue_solve(grid, start, goal, order, out, _team=True)
+
+
+def audit_workspace_bytes(C, N, T):
+    n = _native.lib().gnnpp_mapf_audit_workspace_bytes(int(C), int(N), int(T))
+    if n == 0:
+        raise _native.GnnppError('no audit workspace for C=%d N=%d T_max=%d' % (C, N, T))
+    return n
+
+
+def empty_audit(C, N, T, device):
+    """Output tensors and workspace of enqueue_audit on C cases of N agents with schedules of T + 1 rows."""
+    dev = torch.device(device)
+    nbytes = audit_workspace_bytes(C, N, T)
+
+    def i32(*shape):
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+    return Audit(status=i32(C), arrival=i32(C, N), makespan=i32(C), flowtime=i32(C), counts=i32(C, 4), first=i32(C, 4),
+                 workspace=torch.empty(nbytes, dtype=torch.uint8, device=dev))
+
+
+def enqueue_audit(grid, start, goal, schedule, steps, out):
+    """gnnpp_mapf_audit alone, on torch's current stream of the tensors' device: two launches, no allocation, no host
+    synchronisation, capturable in a HIP graph.  grid uint8 [C,H,W] | [H,W]; start int32 [C,N,2] or None (no start
+    check); goal int32 [C,N,2]; schedule int32 [C,T+1,N,2]; steps int32 [C] or None (the last row of each case that
+    counts; negative: the case is skipped); out: from empty_audit.  All contiguous device tensors."""
+    dev = _native.require_gpu(grid, start, goal, schedule, steps, out.status, out.arrival, out.makespan, out.flowtime,
+                              out.counts, out.first, out.workspace)
+    C, T1, N = (int(v) for v in schedule.shape[:3])
+    with _native.device_guard(dev):
+        _native.check(_native.lib().gnnpp_mapf_audit(
+            grid.data_ptr(), int(grid.dim() == 3), start.data_ptr() if start is not None else None, goal.data_ptr(),
+            schedule.data_ptr(), steps.data_ptr() if steps is not None else None, C, N, int(grid.shape[-2]),
+            int(grid.shape[-1]), T1 - 1, out.status.data_ptr(), out.arrival.data_ptr(), out.makespan.data_ptr(),
+            out.flowtime.data_ptr(), out.counts.data_ptr(), out.first.data_ptr(), out.workspace.data_ptr(),
+            out.workspace.numel(), _native.stream_ptr(dev)), 'gnnpp_mapf_audit')
+
+
+def audit(grids, starts, goals, schedules, device, steps=None):
+    """Audit C schedules: grids [C,H,W] or [H,W] (1 = obstacle), starts [C,N,2] or None (no start check), goals [C,N,2]
+    (row, col), host or device, with solve_team's checks and limits.  schedules: a [C,T+1,N,2] tensor or array (steps:
+    None, or [C] integers -- the last row of each case that counts, negative to skip the case), or a list of C arrays
+    [T_c,N,2] (what expert.read_solution and Solutions.schedule return), padded to the longest with steps = T_c - 1.
+    Returns Audit; offences are reported in .status / .counts / .first, never raised."""
+    if isinstance(schedules, (list, tuple)):
+        if steps is not None:
+            raise _native.GnnppError('mapf.audit: steps come from the lengths of a list of schedules; pass steps=None')
+        rows = [_int32(s) for s in schedules]
+        for c, s in enumerate(rows):
+            if s.dim() != 3 or s.shape[0] < 1 or s.shape[2] != 2 or s.shape[1] != rows[0].shape[1]:
+                raise _native.GnnppError('schedule %d must be [T,N,2] with T >= 1 and the N of schedule 0 (got %s)'
+                                         % (c, tuple(s.shape)))
+        if not rows:
+            raise _native.GnnppError('mapf.audit: an empty list of schedules')
+        steps = torch.tensor([int(s.shape[0]) - 1 for s in rows], dtype=torch.int32)
+        sched = torch.zeros((len(rows), int(steps.max()) + 1) + tuple(rows[0].shape[1:]), dtype=torch.int32,
+                            device=rows[0].device)
+        for c, s in enumerate(rows):
+            sched[c, :s.shape[0]] = s.to(sched.device)
+    else:
+        sched = _int32(schedules)
+    goal = _int32(goals)
+    if sched.dim() != 4 or sched.shape[3] != 2 or sched.shape[1] < 1 or goal.dim() != 3 or \
+            tuple(sched.shape[0:1] + sched.shape[2:]) != tuple(goal.shape):
+        raise _native.GnnppError('schedules must be [C,T+1,N,2] with goals [C,N,2] (got %s and %s)'
+                                 % (tuple(sched.shape), tuple(goal.shape)))
+    dev, g, start, goal, C, N, H, W = _inputs('mapf.audit', MAX_TEAM, MAX_TEAM_SIDE, grids, goal if starts is None else starts,
+                                              goal, device)
+    T = int(sched.shape[1]) - 1
+    if T > MAX_TEAM_STEPS:
+        raise _native.GnnppError('schedules of at most %d steps (got %d)' % (MAX_TEAM_STEPS, T))
+    if steps is not None:
+        steps = _int32(steps)
+        if tuple(steps.shape) != (C,):
+            raise _native.GnnppError('steps must be [C] = [%d] (got %s)' % (C, tuple(steps.shape)))
+        steps = steps.contiguous().to(dev)
+    grid, start, goal = _on_device(dev, g, start, goal)
+    if starts is None:
+        start = None
+    sched = sched.contiguous().to(dev)
+    out = empty_audit(C, N, T, dev)
+    out._keep = (grid, start, goal, sched, steps)        # inputs of the enqueued launches
+    enqueue_audit(grid, start, goal, sched, steps, out)
+    return out
+
+
+def quality(audit_or_solutions, distances):
+    """(flowtime / lower_flowtime, makespan / lower_makespan): float64 [C] each, on the device, of an Audit or a Solutions
+    against a Distances (or anything with .lower_flowtime / .lower_makespan, such as the Solutions of a solve with
+    priorities given as a string); NaN where either side is negative (unsolved, skipped, no path).  A lower bound of 0
+    (every agent starts on its goal) gives 1 for a cost of 0 and inf otherwise.  No host synchronisation."""
+    def ratio(cost, bound):
+        c, b = cost.to(torch.float64), bound.to(torch.float64)
+        r = torch.where((c == 0) & (b == 0), torch.ones_like(c), c / b)
+        return torch.where((c < 0) | (b < 0), torch.full_like(c, float('nan')), r)
+    return (ratio(audit_or_solutions.flowtime, distances.lower_flowtime),
+            ratio(audit_or_solutions.makespan, distances.lower_makespan))
 
 
 def _int32(x):

@@ -4,6 +4,7 @@
     python tools/mapf_bench.py --team [--reps 10] [--out profiles/mapf_team_solve.json] [--only NAME] [--cpu-cases 2]
     python tools/mapf_bench.py --priorities [--reps 10] [--out profiles/mapf_distance.json] [--only NAME]
     python tools/mapf_bench.py --generated [--reps 10] [--out profiles/casegen.json] [--only NAME] [--cpu-cases 2]
+    python tools/mapf_bench.py --audit [--reps 10] [--out profiles/mapf_audit.json] [--only NAME] [--cpu-cases 2]
 
 Configurations (random maps of tests/expert_cases.random_map at density 0.1, horizon 4 (H + W)): 512 cases x 10 agents
 on 20 x 20 with R = 1 and R = 4 orders, 256 x 20 on 20 x 20, 128 x 64 on 40 x 40.  Outputs and workspace are
@@ -31,6 +32,15 @@ at the same density, next to the host-drawn cases of the same configuration: the
 events, outputs preallocated), the agents with dist < 0 (0 by construction on generated cases: asserted), and the solved
 counts under None (the index order), 'longest_first' and 'mixed' with R = 4 for both kinds of cases.  Beside the call's
 time: the numpy / queue yardstick (tests/casegen_cases.py) on the first --cpu-cases cases, on one host core, as context.
+
+--audit: the schedule audit (mapf.enqueue_audit, csrc/mapf_audit_kernels.hip) on the schedules the solver produced for the
+configurations of --priorities on GENERATED cases (so that the cases are solvable), index order, steps = the solver's
+makespan: the time of one gnnpp_mapf_audit call (HIP events, outputs and workspace preallocated) next to the time of the
+solve call it checks, measured in the same process, the audit as a share of it, and the bytes of schedule the audit reads
+per second (rows 0 .. makespan of the solved cases, once).  Every solved case must audit clean with the solver's arrivals
+and costs (asserted: a condition, not a measurement).  Beside it the solve time the profiles record for the configuration
+on host-drawn cases (profiles/mapf_solve.json, profiles/mapf_team_solve.json), and the sequential restatement
+(tests/mapf_audit_cases.py) on the first --cpu-cases cases as context.
 """
 import argparse
 import json
@@ -167,6 +177,69 @@ def generated_records(a, mc, mapf, dev):
     return records
 
 
+def audit_records(a, mc, mapf, dev):
+    """--audit: one record per distinct set of inputs of CONFIGS and TEAM_CONFIGS."""
+    import mapf_audit_cases as ac
+    from gnn_pathplanning_amd import casegen
+    recorded = {}
+    for path in ('mapf_solve.json', 'mapf_team_solve.json'):
+        try:
+            with open(os.path.join(ROOT, 'profiles', path)) as f:
+                recorded.update({r['config']: r['ms_per_call'] for r in json.load(f)['records']})
+        except (OSError, KeyError, ValueError):
+            pass
+    records, seen = [], set()
+    for team, (full, C, N, side, _) in [(False, c) for c in CONFIGS] + [(True, c) for c in TEAM_CONFIGS]:
+        name = full.rsplit('_r', 1)[0]
+        if (a.only and name != a.only) or name in seen:
+            continue
+        seen.add(name)
+        seed = C * N + side
+        T = mc.default_horizon(side, side)
+        cases = casegen.generate(C, N, side, side, dev, density=0.1, seed=seed)
+        out = (mapf.empty_solutions(C, N, side, T, dev, 1, W=side, team=True) if team
+               else mapf.empty_solutions(C, N, side, T, dev, 1))
+        enqueue = mapf.enqueue_solve_team if team else mapf.enqueue_solve
+        solve_sec = timed(lambda: enqueue(cases.grid, cases.start, cases.goal, None, out), a.reps)
+        found = mapf.empty_audit(C, N, T, dev)
+        sec = timed(lambda: mapf.enqueue_audit(cases.grid, cases.start, cases.goal, out.schedules, out.makespan, found),
+                    a.reps)
+        torch.cuda.synchronize()
+        solved = out.status == 0
+        assert bool((found.status[solved] == 0).all()) and bool((found.status[~solved] == mapf.AUDIT_SKIPPED).all())
+        assert torch.equal(found.arrival[solved], out.arrival[solved])
+        assert torch.equal(found.flowtime[solved], out.flowtime[solved])
+        rows = int((out.makespan[solved] + 1).sum().item())
+        rec = {'config': name, 'call': 'gnnpp_mapf_audit', 'cases': C, 'agents': N, 'map': '%dx%d' % (side, side),
+               'T_max': T, 'chunk': mapf.AUDIT_CHUNK,
+               'what': 'HIP events, mean of %d calls after 3; outputs and workspace preallocated; generated cases '
+                       '(density 0.1, seed %d), index order, steps = makespan' % (a.reps, seed),
+               'solved': int(solved.sum().item()), 'makespan_max': int(out.makespan.max().item()), 'rows_audited': rows,
+               'audit_ms_per_call': round(sec * 1e3, 4),
+               'solve_call': 'gnnpp_mapf_team_solve' if team else 'gnnpp_mapf_solve',
+               'solve_ms_per_call_same_process': round(solve_sec * 1e3, 4),
+               'audit_share_of_solve': round(sec / solve_sec, 5),
+               'solve_ms_per_call_recorded_host_drawn': recorded.get(full),
+               'schedule_GB_read_per_s': round(rows * N * 8 / sec / 1e9, 3),
+               'workspace_MB': round(found.workspace.numel() / 2 ** 20, 3)}
+        k = min(a.cpu_cases, C, 0 if N >= 160 else C)       # (the restatement looks for swaps in O(N^2) per step)
+        if k:
+            case = ac.make_case(name, cases.grid[:k].cpu().numpy(), cases.goal[:k].cpu().numpy(),
+                                out.schedules[:k].cpu().numpy(), start=cases.start[:k].cpu().numpy(),
+                                steps=out.makespan[:k].cpu().numpy())
+            t0 = time.perf_counter()
+            want = ac.audit(case)
+            rec['cpu_restatement_cases_per_s'] = round(k / (time.perf_counter() - t0), 2)
+            rec['cpu_restatement_agrees'] = all(np.array_equal(getattr(found, key)[:k].cpu().numpy(), want[key])
+                                                for key in ac.OUTPUTS)
+        rec['cpu_restatement_cases_timed'] = k
+        print(json.dumps(rec), flush=True)
+        records.append(rec)
+        del out, found, cases
+        torch.cuda.empty_cache()
+    return records
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=10)
@@ -178,16 +251,19 @@ def main():
                     help='compare the planning orders: None, longest_first, mixed (see the module docstring)')
     ap.add_argument('--generated', action='store_true',
                     help='the --priorities configurations on cases generated on the device (see the module docstring)')
+    ap.add_argument('--audit', action='store_true',
+                    help='time the schedule audit next to the solve it checks (see the module docstring)')
     a = ap.parse_args()
     if a.cpu_cases is None:
-        a.cpu_cases = 2 if a.team or a.generated else 16
+        a.cpu_cases = 2 if a.team or a.generated or a.audit else 16
     assert torch.cuda.is_available(), 'needs the MI355X: a CPU run measures nothing'
     import mapf_cases as mc
     from gnn_pathplanning_amd import mapf
     dev = torch.device('cuda:0')
     records = (priorities_records(a, mc, mapf, dev) if a.priorities else
-               generated_records(a, mc, mapf, dev) if a.generated else [])
-    for name, C, N, side, R in (() if a.priorities or a.generated else TEAM_CONFIGS if a.team else CONFIGS):
+               generated_records(a, mc, mapf, dev) if a.generated else
+               audit_records(a, mc, mapf, dev) if a.audit else [])
+    for name, C, N, side, R in (() if a.priorities or a.generated or a.audit else TEAM_CONFIGS if a.team else CONFIGS):
         if a.only and name != a.only:
             continue
         rng = np.random.default_rng(C * N + side)
