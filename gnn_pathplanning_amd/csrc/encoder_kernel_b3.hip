@@ -1093,46 +1093,68 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
 #pragma unroll
     for (int i = 0; i < kRingH; ++i) h2_ring_load<END>(ws, ring, i);
 
-    // ---- observations: all loads first, zero-fill while they fly, then split + scatter -------------------
+    // ---- observations: all loads first, zero-fill while they fly, then the image -------------------------
     bool one_plane;
     {
-        constexpr int NV4 = (kTileAgents * kObsFloats + 3) / 4 + 1;
-        constexpr int PER = (NV4 + kThreads - 1) / kThreads;
+        // Loaded BY IMAGE ROWS: work item w = one row (11 pixels, 44 contiguous bytes at src + 11 w) of one channel of
+        // one agent, n_agents * 33 <= 528 of them strided over the 256 threads; a wave's 64 rows are one 2 816-byte
+        // span.  Only rows of the tile are read (whatever M, agent0 and the tensor's alignment: dword-aligned loads),
+        // a row slot beyond the tile holds zeros.
+        constexpr int kRowsPerAgent = kObsFloats / 11;                                  // 33
+        constexpr int RT = (kTileAgents * kRowsPerAgent + kThreads - 1) / kThreads;     // 3 trips
+        typedef unsigned v4u_a4 __attribute__((ext_vector_type(4), aligned(4)));
+        typedef unsigned v3u_a4 __attribute__((ext_vector_type(3), aligned(4)));
         const int valid = n_agents * kObsFloats;
         const float* src = obs + (size_t)agent0 * kObsFloats;
-        const int shift = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);
-        const float* src4 = src - shift;
-        const long floats_left = (long)(M - agent0) * kObsFloats + shift;   // from src4 to the end of the tensor
-        const bool head_ok = shift == 0 || agent0 > 0;                      // (never read in front of the tensor)
-        v4f v[PER];
+        const int n_rows = n_agents * kRowsPerAgent;
+        unsigned px[RT][12];                                                            // ([11]: unused)
 #pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int idx = tid + k * kThreads;
-            const int e0 = 4 * idx - shift;
-            if (head_ok && 4L * idx + 4 <= floats_left && e0 < valid) {
-                v[k] = *reinterpret_cast<const v4f*>(src4 + 4 * idx);
-            } else {
+        for (int k = 0; k < RT; ++k) {
+            const int w = tid + k * kThreads;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) v[k][c] = src[min(max(e0 + c, 0), valid - 1)];
+            for (int c = 0; c < 12; ++c) px[k][c] = 0u;
+            if (w < n_rows) {
+                const unsigned* row = reinterpret_cast<const unsigned*>(src) + 11 * w;
+                const v4u_a4 r0 = *reinterpret_cast<const v4u_a4*>(row);
+                const v4u_a4 r1 = *reinterpret_cast<const v4u_a4*>(row + 4);
+                const v3u_a4 r2 = *reinterpret_cast<const v3u_a4*>(row + 8);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { px[k][c] = r0[c]; px[k][4 + c] = r1[c]; }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) px[k][8 + c] = r2[c];
             }
         }
-        // PLANE SKIPPING, decided BEFORE the scatter: when every pixel of the tile is exactly one bf16 (the simulator's
-        // observations are {0, 1}: AgentState.toInputTensor, dataloader/statetransformer.py:82-130) the m and l planes are
-        // identically zero; L0 then does not issue their products -- skipping exact zeros, the result is the same to the
-        // bit -- and the pixels are stored PACKED (kPkChan).  A value is one bf16 iff its low 16 bits are clear (then
-        // m = l = 0; otherwise m or l is not).  Each wave publishes its flag in front of the barrier that ends the
-        // zero-fill, every thread reads all four behind it.  (A lane's elements outside the tile are copies of valid
-        // ones or other agents' pixels: they can only make the flag conservative.)
+        // PLANE SKIPPING, decided BEFORE the image is written: when every pixel of the tile is exactly one bf16 (the
+        // simulator's observations are {0, 1}: AgentState.toInputTensor, dataloader/statetransformer.py:82-130) the m and l
+        // planes are identically zero; L0 then does not issue their products -- skipping exact zeros, the result is the
+        // same to the bit -- and the pixels are stored PACKED (kPkChan).  A value is one bf16 iff its low 16 bits are
+        // clear (then m = l = 0; otherwise m or l is not).  Each wave publishes its flag in front of the barrier that
+        // ends the zero-fill, every thread reads all four behind it.  (Exactly the tile's pixels decide: a row slot
+        // outside the tile contributes zeros.)
         unsigned lowbits = 0;
 #pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const v4u vb = __builtin_bit_cast(v4u, v[k]);
-            lowbits |= vb[0] | vb[1] | vb[2] | vb[3];
-        }
+        for (int k = 0; k < RT; ++k)
+#pragma unroll
+            for (int c = 0; c < 11; ++c) lowbits |= px[k][c];
         const bool wave_inexact = __ballot((lowbits & 0xffffu) != 0u) != 0ull;
         if (lane == 0) planeflag[wave] = (wave_inexact || force_planes) ? 1u : 0u;
-        // the packed image; a tile that needs the word images (27 KiB h | m, 27 KiB l) clears the rest behind the barrier
-        for (int i = tid; i < kPkBytes / 16; i += kThreads) R4[i] = vzero();
+        // The zeros of the packed image.  b3_l0_stream addresses, per lane (agent a = 0 .. 15, whether the tile has it or
+        // not), the dwords 6 (2 wy + oy) + wx + {0, 1, 6, 7, 12, 13} of channel q (q < 3), + 13 of all three channels and
+        // + {0, 1} of channel 0 (q = 3), wy, wx <= 4, oy <= 1: dwords 0 .. 71 of each channel image and nothing else
+        // (dword 72 of a channel and 219 .. 230 of an agent are never addressed).  The row stores below write dwords
+        // 6 .. 71 (rows 1 .. 11, left pad included) of the tile's agents; what is zeroed here is the rest: the top pad
+        // row (dwords 0 .. 5) of each of their channels, and the whole images of the agents the tile does not have (from
+        // the 16-byte boundary below them: at most three slack dwords of the last agent).  A tile that needs the word
+        // images (27 KiB h | m, 27 KiB l) clears all of them behind the barrier.
+        static_assert(6 * (2 * 4 + 1) + 4 + 13 == kPadHW * kPadHW / 2 - 1 && kPadHW * kPadHW / 2 <= kPkChan &&
+                      kPkAgent - 3 * kPkChan >= 3 && 11 * (kPadHW / 2) + kPadHW / 2 == kPadHW * kPadHW / 2,
+                      "L0 reads dwords 0 .. 71 of a channel image: rows 1 .. 11 are stored, row 0 and absent agents zeroed");
+        if (tid < 3 * n_agents) {
+            unsigned* const top = obsw + (tid / 3) * kPkAgent + (tid % 3) * kPkChan;
+#pragma unroll
+            for (int c = 0; c < kPadHW / 2; ++c) top[c] = 0u;
+        }
+        for (int i = ((n_agents * kPkAgent) >> 2) + tid; i < kPkBytes / 16; i += kThreads) R4[i] = vzero();
         if (CP && tid < kCpRow / 16)                       // the row of zeros behind L1's input rows
             *reinterpret_cast<v4f*>(gnnpp_smem + geom.l1in + geom.T1 * kCpRow + tid * 16) = vzero();
 #pragma unroll
@@ -1143,18 +1165,52 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
             const v4u pf = *reinterpret_cast<const v4u*>(planeflag);
             one_plane = __builtin_amdgcn_readfirstlane((int)(pf[0] | pf[1] | pf[2] | pf[3])) == 0;   // (workgroup-uniform)
         }
-        // Scatter into the padded images, BRANCH-FREE (this loop is VALU-issue-bound and runs in both workgroups of a
-        // CU at the same time: every instruction counts).  Flat element e of [agent][3][11][11] -> pixel
-        //   o = agent * AS + ch * CS + (y + 1) * 12 + x + 1 = base + r + y + 13,   r = 11 y + x in 0..120
-        // (words, AS = kAgentStride, CS = 144 -- or, packed, halfwords, AS = 2 kPkAgent, CS = 2 kPkChan);
-        // a thread's four consecutive elements cross at most ONE channel / agent boundary (r wraps at 121).  Divisions
-        // by constants as 24-bit multiplies + shifts (exact on the ranges used); elements outside the tile go to a
-        // dump word behind the images instead of around a branch.
-        const unsigned dump = 2 * kObsFloatsLds + lane;
-        auto scatter = [&](auto packedc) {
-            constexpr bool PACKED = decltype(packedc)::value;
-            constexpr unsigned AS = PACKED ? 2 * kPkAgent : kAgentStride, CS = PACKED ? 2 * kPkChan : kPadHW * kPadHW;
-            unsigned short* const obsh = reinterpret_cast<unsigned short*>(gnnpp_smem);
+        if (one_plane) {
+            // Padded row y + 1 of a channel is 12 halfwords -- the left pad, then 11 pixels -- and starts on a dword:
+            // six dwords (0 | p0) (p1 | p2) .. (p9 | p10) at an address computed once per row; each pixel IS its high
+            // half, one v_perm per pair.
+#pragma unroll
+            for (int k = 0; k < RT; ++k) {
+                const unsigned w = tid + k * kThreads;
+                if ((int)w < n_rows) {
+                    const unsigned ag = w / kRowsPerAgent, rem = w - ag * kRowsPerAgent;
+                    const unsigned ch = rem / 11u, y = rem - ch * 11u;
+                    unsigned* const dst = obsw + ag * kPkAgent + ch * kPkChan + (y + 1) * (kPadHW / 2);
+                    dst[0] = px[k][0] & 0xffff0000u;
+#pragma unroll
+                    for (int c = 1; c < kPadHW / 2; ++c)
+                        dst[c] = __builtin_amdgcn_perm(px[k][2 * c], px[k][2 * c - 1], 0x07060302u);
+                }
+            }
+        } else {
+            // The three-plane word images (the rare path: it loads the tile a second time, by flat elements, four per
+            // trip).  Flat element e of [agent][3][11][11] -> word
+            //   o = agent * kAgentStride + ch * 144 + (y + 1) * 12 + x + 1 = base + r + y + 13,   r = 11 y + x in 0..120;
+            // a thread's four consecutive elements cross at most ONE channel / agent boundary (r wraps at 121).  Divisions
+            // by constants as 24-bit multiplies + shifts (exact on the ranges used); elements outside the tile go to a
+            // dump word behind the images instead of around a branch.
+            constexpr int NV4 = (kTileAgents * kObsFloats + 3) / 4 + 1;
+            constexpr int PER = (NV4 + kThreads - 1) / kThreads;
+            constexpr unsigned AS = kAgentStride, CS = kPadHW * kPadHW;
+            const int shift = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);
+            const float* src4 = src - shift;
+            const long floats_left = (long)(M - agent0) * kObsFloats + shift;   // from src4 to the end of the tensor
+            const bool head_ok = shift == 0 || agent0 > 0;                      // (never read in front of the tensor)
+            v4f v[PER];
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                const int idx = tid + k * kThreads;
+                const int e0 = 4 * idx - shift;
+                if (head_ok && 4L * idx + 4 <= floats_left && e0 < valid) {
+                    v[k] = *reinterpret_cast<const v4f*>(src4 + 4 * idx);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) v[k][c] = src[min(max(e0 + c, 0), valid - 1)];
+                }
+            }
+            for (int i = tid; i < 2 * kObsFloatsLds / 4; i += kThreads) R4[i] = vzero();
+            __syncthreads();
+            const unsigned dump = 2 * kObsFloatsLds + lane;
 #pragma unroll
             for (int k = 0; k < PER; ++k) {
                 const int e0 = (tid + k * kThreads) * 4 - shift;
@@ -1168,7 +1224,7 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
                 unsigned w1[4], w2[4];
                 const v4u vb = __builtin_bit_cast(v4u, v[k]);
                 const bool inexact = ((vb[0] | vb[1] | vb[2] | vb[3]) & 0xffffu) != 0u;   // some value of this lane is not ONE bf16
-                const bool any_l = !PACKED && __ballot(inexact) != 0ull;    // (wave-uniform)
+                const bool any_l = __ballot(inexact) != 0ull;               // (wave-uniform)
                 if (!any_l) {
                     // every value IS its h plane: no conversions, no l words
                     w1[0] = vb[0] >> 16; w1[1] = vb[1] >> 16; w1[2] = vb[2] >> 16; w1[3] = vb[3] >> 16;
@@ -1192,21 +1248,10 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
                     const unsigned y = __umul24((unsigned)r & 0xffu, 745u) >> 13;         // r / 11   (0 <= r < 121 where it matters)
                     const unsigned o = (wrap ? wrapped : base) + (unsigned)r + y;
                     const bool ok = e >= 0 && e < valid;
-                    if constexpr (PACKED) {
-                        obsh[ok ? o : 2 * dump] = (unsigned short)w1[c];
-                    } else {
-                        obsw[ok ? o : dump] = w1[c];
-                        if (any_l) obsw[ok ? o + kObsFloatsLds : dump] = w2[c];
-                    }
+                    obsw[ok ? o : dump] = w1[c];
+                    if (any_l) obsw[ok ? o + kObsFloatsLds : dump] = w2[c];
                 }
             }
-        };
-        if (one_plane) {
-            scatter(std::true_type{});
-        } else {
-            for (int i = kPkBytes / 16 + tid; i < 2 * kObsFloatsLds / 4; i += kThreads) R4[i] = vzero();
-            __syncthreads();
-            scatter(std::false_type{});
         }
     }
     __syncthreads();
