@@ -33,7 +33,6 @@ namespace gnnpp {
 typedef ::gnnpp_schedules ScheduleArgs;
 
 constexpr int kScanStepsPerWg = 4;            // expert_scan_kernel: 256 threads = 4 waves = 4 steps
-constexpr int kGrowthCap = 0xffff;            // step_info keeps k_t in 16 bits (1.1^65535 overflows fp64 long before)
 
 // largest c with case_start[c] <= t (case_start [C + 1] ascending, case_start[0] = 0): wave-uniform
 __device__ __forceinline__ int schedule_case_of(const int* case_start, int C, int t) {
@@ -54,8 +53,33 @@ __device__ __forceinline__ RolloutArgs schedule_as_rollout(const ScheduleArgs& p
     return q;
 }
 
-// Pass 1.  Lane l of the step's wave holds agents l and l + 64 (the layout of gso_wave0).  step_info[t] = k_t |
-// status << 16.  A step with a state off the map gets no graph search (k_t = 0): its case is flagged and not built.
+// ---- per-agent pieces shared with expert_team_kernels.hip -------------------------------------------------------
+// the states step t moves to: the next step's, after a case's last state the goal
+__device__ __forceinline__ const int* schedule_next_state(const ScheduleArgs& p, int c, int t, const int* pos) {
+    const bool last = t + 1 >= p.case_start[c + 1] || t + 1 >= p.T_total;
+    return last ? p.goal + (size_t)c * p.N * 2 : pos + 2 * p.N;
+}
+
+// legality of one agent's state (x, y) and of its move to (nx, ny)
+__device__ __forceinline__ void schedule_agent_flags(const ScheduleArgs& p, const unsigned char* grid, int x, int y,
+                                                     int nx, int ny, bool& bad_move, bool& off_map, bool& on_obstacle) {
+    // one of [-1,0] [0,-1] [1,0] [0,1] [0,0] (compared, not subtracted: no overflow on wild input)
+    const bool legal = (nx == x && (ny == y || ny == y - 1 || ny == y + 1)) ||
+                       (ny == y && (nx == x - 1 || nx == x + 1));
+    bad_move = !legal;
+    off_map = x < 0 || x >= p.H || y < 0 || y >= p.W;
+    on_obstacle = !off_map && grid[(size_t)x * p.W + y] != 0;
+}
+
+// expert action: one-hot of next - current = (dx, dy) in the order [-1,0] [0,-1] [1,0] [0,1] [0,0] (legal: pass 1)
+__device__ __forceinline__ void expert_target_store(float* o, int dx, int dy) {
+    const int a = dx == -1 ? 0 : dy == -1 ? 1 : dx == 1 ? 2 : dy == 1 ? 3 : 4;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) o[j] = j == a ? 1.f : 0.f;
+}
+
+// Pass 1.  Lane l of the step's wave holds agents l and l + 64 (the one-wave form of comm_graph.hip).  step_info[t] =
+// k_t | status << 16.  A step with a state off the map gets no graph search (k_t = 0): its case is flagged and not built.
 __global__ __launch_bounds__(256) void expert_scan_kernel(const ScheduleArgs p) {
     const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * kScanStepsPerWg + (threadIdx.x >> 6);
@@ -64,27 +88,17 @@ __global__ __launch_bounds__(256) void expert_scan_kernel(const ScheduleArgs p) 
     const bool two = N > 64;
     const int c = schedule_case_of(p.case_start, p.C, t);
     const int* pos = p.pos + (size_t)t * N * 2;
-    const bool last = t + 1 >= p.case_start[c + 1] || t + 1 >= p.T_total;
-    const int* nxt = last ? p.goal + (size_t)c * N * 2 : pos + 2 * N;     // after the last state: the goal
+    const int* nxt = schedule_next_state(p, c, t, pos);
     const unsigned char* grid = p.grid + (p.grid_batched ? (size_t)c * p.H * p.W : 0);
-    int px[2], py[2];
-    bool live[2], bad_move[2], off_map[2], on_obstacle[2];
+    const WaveAgents A = wave_agents_load(pos, N, lane);
+    bool bad_move[2], off_map[2], on_obstacle[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int n = lane + 64 * h;
-        live[h] = n < N;
         bad_move[h] = off_map[h] = on_obstacle[h] = false;
-        px[h] = py[h] = -(1 << 20);                              // dead lanes: far away from everything
-        if (live[h]) {
-            const int x = pos[2 * n], y = pos[2 * n + 1];
-            const int nx = nxt[2 * n], ny = nxt[2 * n + 1];
-            // one of [-1,0] [0,-1] [1,0] [0,1] [0,0] (compared, not subtracted: no overflow on wild input)
-            const bool legal = (nx == x && (ny == y || ny == y - 1 || ny == y + 1)) ||
-                               (ny == y && (nx == x - 1 || nx == x + 1));
-            bad_move[h] = !legal;
-            off_map[h] = x < 0 || x >= p.H || y < 0 || y >= p.W;
-            on_obstacle[h] = !off_map[h] && grid[(size_t)x * p.W + y] != 0;
-            if (!off_map[h]) { px[h] = x; py[h] = y; }
+        if (A.live[h]) {
+            schedule_agent_flags(p, grid, A.px[h], A.py[h], nxt[2 * n], nxt[2 * n + 1], bad_move[h], off_map[h],
+                                 on_obstacle[h]);
         }
     }
     const MaskPair m_move = ballot2(bad_move[0], two && bad_move[1]);
@@ -94,42 +108,16 @@ __global__ __launch_bounds__(256) void expert_scan_kernel(const ScheduleArgs p) 
     if (m_move.lo | m_move.hi) status |= GNNPP_SCHEDULE_BAD_MOVE;
     if (m_off.lo | m_off.hi | m_obs.lo | m_obs.hi) status |= GNNPP_SCHEDULE_BAD_STATE;
     int k = 0;
+    // A.px / A.py hold the states as given, wild ones included: this guard alone keeps them out of dist2 (a step with a
+    // state off the map gets no search), so below every coordinate is a cell of the map
     if (!(m_off.lo | m_off.hi)) {                                // (wave-uniform)
-        unsigned long long a0[2] = {0ull, 0ull}, a1[2] = {0ull, 0ull};     // my agents' adjacency rows
-        double r = p.radius0;
-        int built = -2;                                          // integer threshold the rows were built with
-        for (;;) {
-            const long long T = dist2_threshold(r);
-            const int Ti = T > 0x7fffffffLL ? 0x7fffffff : (int)T;         // d2 < 2^29: H, W <= 16384
-            if (Ti != built) {                                   // same threshold = same graph: still disconnected
-                built = Ti;
-                for (int i = 0; i < N; ++i) {
-                    const int bx = lane_get(px, i), by = lane_get(py, i);
-                    bool e[2];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const int dx = px[h] - bx, dy = py[h] - by;
-                        e[h] = live[h] && lane + 64 * h != i && dx * dx + dy * dy <= Ti;
-                    }
-                    const MaskPair row = ballot2(e[0], two && e[1]);
-                    if (lane == (i & 63)) {
-                        a0[i >> 6] = row.lo;
-                        a1[i >> 6] = row.hi;
-                    }
-                }
-                MaskPair R = {1ull, 0ull}, F = R;                // reached set, frontier (level-synchronous search)
-                while (F.lo | F.hi) {
-                    const MaskPair nb = ballot2(live[0] && ((a0[0] & F.lo) | (a1[0] & F.hi)) != 0ull,
-                                                two && live[1] && ((a0[1] & F.lo) | (a1[1] & F.hi)) != 0ull);
-                    F.lo = nb.lo & ~R.lo; F.hi = nb.hi & ~R.hi;
-                    R.lo |= nb.lo; R.hi |= nb.hi;
-                }
-                if (__popcll(R.lo) + __popcll(R.hi) == N) break;
-            }
-            if (k == kGrowthCap) { status |= GNNPP_SCHEDULE_NO_RADIUS; break; }
-            r = r * 1.1;
-            ++k;
-        }
+        WaveRows rows = {{0ull, 0ull}, {0ull, 0ull}};
+        // The launcher accepts H, W <= 16384 and the API radius0 > 0 only: d2 < 2^29 and thresholds >= 0, where the unsigned
+        // dist2 <= dist2_bound and the signed test with a 2^31 - 1 clamp it replaces agree on every pair: the same k_t.
+        k = expert_radius_search(p.radius0, status, [&](unsigned Tu) {
+            wave_adjacency_rows(A, N, lane, Tu, rows);
+            return wave_connected(rows, A.live, N);
+        });
     }
     if (lane == 0) p.step_info[t] = k | (status << 16);
 }
@@ -173,15 +161,9 @@ __global__ __launch_bounds__(256) void expert_samples_kernel(const ScheduleArgs 
     const int* pos = p.pos + (size_t)t * N * 2;
     const double radius = p.radius[c];
 
-    // expert action: one-hot of next - current in the order [-1,0] [0,-1] [1,0] [0,1] [0,0] (legal: pass 1)
-    const bool last = t + 1 >= p.case_start[c + 1] || t + 1 >= p.T_total;
-    const int* nxt = last ? p.goal + (size_t)c * N * 2 : pos + 2 * N;
+    const int* nxt = schedule_next_state(p, c, t, pos);
     for (int n = tid; n < N; n += 256) {
-        const int dx = nxt[2 * n] - pos[2 * n], dy = nxt[2 * n + 1] - pos[2 * n + 1];
-        const int a = dx == -1 ? 0 : dy == -1 ? 1 : dx == 1 ? 2 : dy == 1 ? 3 : 4;
-        float* o = p.target + ((size_t)t * N + n) * 5;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) o[j] = j == a ? 1.f : 0.f;
+        expert_target_store(p.target + ((size_t)t * N + n) * 5, nxt[2 * n] - pos[2 * n], nxt[2 * n + 1] - pos[2 * n + 1]);
     }
 
     observe_stage(q, c, cell, goal_l, tid, 256);
@@ -190,22 +172,7 @@ __global__ __launch_bounds__(256) void expert_samples_kernel(const ScheduleArgs 
     else observe_prep(q, pos, cell, goal_l, tid - 64, 256 - 64);
     __syncthreads();
 
-    {   // S = (s_i * A_ij) * s_j in fp64, rounded once for the fp32 copy; 16 lanes per row
-        const unsigned long long* adj = reinterpret_cast<const unsigned long long*>(gso_smem);
-        const double* inv = reinterpret_cast<const double*>(adj + 2 * kMaxAgents);
-        float* S = p.S + (size_t)t * N * N;
-        double* S64 = p.S64 ? p.S64 + (size_t)t * N * N : nullptr;
-        for (int i = tid / 16; i < N; i += 256 / 16) {
-            const unsigned long long w0 = adj[2 * i], w1 = adj[2 * i + 1];
-            const double ii = inv[i];
-            for (int j = tid & 15; j < N; j += 16) {
-                const bool on = j < 64 ? (w0 >> j) & 1ull : (w1 >> (j - 64)) & 1ull;
-                const double v = on ? ii * inv[j] : 0.0;
-                S[i * N + j] = (float)v;
-                if (S64) S64[i * N + j] = v;
-            }
-        }
-    }
+    gso_store_S(gso_layout(gso_smem), N, p.S + (size_t)t * N * N, p.S64 ? p.S64 + (size_t)t * N * N : nullptr, tid, 256);
 
     for (int n0 = 0; n0 < N; n0 += kObsAgentsPerWg) {            // 16 agents' rows at a time through the LDS stage
         const int n1 = min(N, n0 + kObsAgentsPerWg);

@@ -16,7 +16,7 @@
 //
 // The degrees go through memory because the tiles of a step all need every agent's s: one workgroup per step for the
 // whole of S would leave a call of a few steps on a handful of compute units.
-// Squared distances are unsigned (dist2_bound, dist2 of rollout_kernels.hip): a map of GNNPP_ROLLOUT_TEAM_MAX_CELLS
+// Squared distances are unsigned (dist2_bound, dist2 of comm_graph.hip): a map of GNNPP_ROLLOUT_TEAM_MAX_CELLS
 // cells can be 1 x 65536, (H-1)^2 + (W-1)^2 < 2^32.
 // This file is included from gnnpp_api.hip after expert_kernels.hip and rollout_team_kernels.hip and uses their helpers.
 
@@ -41,21 +41,14 @@ __global__ __launch_bounds__(1024) void expert_team_scan_kernel(const ScheduleAr
     unsigned long long* words = fr[1] + kTeamWords;                                 // [kTeamWords]
     const int c = schedule_case_of(p.case_start, p.C, t);
     const int* pos = p.pos + (size_t)t * N * 2;
-    const bool last = t + 1 >= p.case_start[c + 1] || t + 1 >= p.T_total;
-    const int* nxt = last ? p.goal + (size_t)c * N * 2 : pos + 2 * N;     // after the last state: the goal
+    const int* nxt = schedule_next_state(p, c, t, pos);
     const unsigned char* grid = p.grid + (p.grid_batched ? (size_t)c * p.H * p.W : 0);
     const bool live = a < N;
     bool bad_move = false, off_map = false, on_obstacle = false;
     int mx = 0, my = 0;
     if (live) {
         const int x = pos[2 * a], y = pos[2 * a + 1];
-        const int nx = nxt[2 * a], ny = nxt[2 * a + 1];
-        // one of [-1,0] [0,-1] [1,0] [0,1] [0,0] (compared, not subtracted: no overflow on wild input)
-        const bool legal = (nx == x && (ny == y || ny == y - 1 || ny == y + 1)) ||
-                           (ny == y && (nx == x - 1 || nx == x + 1));
-        bad_move = !legal;
-        off_map = x < 0 || x >= p.H || y < 0 || y >= p.W;
-        on_obstacle = !off_map && grid[(size_t)x * p.W + y] != 0;
+        schedule_agent_flags(p, grid, x, y, nxt[2 * a], nxt[2 * a + 1], bad_move, off_map, on_obstacle);
         mx = x; my = y;
         px[a] = x; py[a] = y;
     }
@@ -128,14 +121,10 @@ __global__ __launch_bounds__(1024) void expert_team_degree_kernel(const Schedule
     const unsigned Tu = dist2_bound(p.radius[c]);
     int deg = 0;
     for (int j = 0; j < N; ++j) deg += j != a && dist2(px[j], py[j], mx, my) <= Tu;
-    inv_ws[(size_t)t * N + a] = deg ? sqrt(1.0 / (double)deg) : 0.0;
-    const bool last = t + 1 >= p.case_start[c + 1] || t + 1 >= p.T_total;
-    const int* nxt = last ? p.goal + (size_t)c * N * 2 : pos + 2 * N;
+    inv_ws[(size_t)t * N + a] = inv_sqrt_degree(deg);
+    const int* nxt = schedule_next_state(p, c, t, pos);
     const int dx = nxt[2 * a] - mx, dy = nxt[2 * a + 1] - my;
-    const int act = dx == -1 ? 0 : dy == -1 ? 1 : dx == 1 ? 2 : dy == 1 ? 3 : 4;
-    float* o = p.target + ((size_t)t * N + a) * 5;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) o[j] = j == act ? 1.f : 0.f;
+    expert_target_store(p.target + ((size_t)t * N + a) * 5, dx, dy);
 }
 
 // Pass 4: rows [tile * kTeamGraphRows, ...) of S[t] (and S64[t]): S64 = s_i * s_j where d2 <= threshold and i != j,

@@ -8,6 +8,7 @@
 #include "encoder_pack.hip"
 #include "encoder_ring_f32.hip"
 #include "encoder_kernel_f32.hip"
+#include "comm_graph.hip"           // the communication graph, once per execution form: used by the rollout and expert files
 #include "rollout_kernels.hip"       // before the fused policy kernel, which can run the simulator step too
 #include "rollout_team_kernels.hip"  // teams of more than GNNPP_ROLLOUT_MAX_AGENTS agents
 #include "expert_kernels.hip"        // training samples from expert schedules (uses the rollout's observation / graph code)

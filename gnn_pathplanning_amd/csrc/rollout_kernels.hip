@@ -9,29 +9,12 @@
 // rollout step is observe -> gso -> policy_fwd -> move with no host round trip.  This is integer /
 // boolean / fp64 work: results are bit-exact against traces of the real simulator.
 // Positions are int32 (row, col) pairs (the reference keeps integers in float tensors).
+// The communication graph's statement and its shared pieces (positions -> rows, search, D^-1/2, S) live in
+// comm_graph.hip, included before this file; here they get the rollout's thread mappings and stores.
 #include "../../include/gnnpp.h"
 #include "gnnpp_common.h"
 
 namespace gnnpp {
-
-constexpr int kMaxAgents = GNNPP_ROLLOUT_MAX_AGENTS;
-
-typedef ::gnnpp_rollout RolloutArgs;      // the C-ABI struct itself (include/gnnpp.h)
-
-// ---- wave-level helpers: lane l of a wave holds agents l and l + 64 (teams of up to 128) -------------
-__device__ __forceinline__ int lane_get(const int (&v)[2], int agent) {
-    return __builtin_amdgcn_readlane(agent < 64 ? v[0] : v[1], agent & 63);
-}
-
-struct MaskPair { unsigned long long lo, hi; };
-
-__device__ __forceinline__ MaskPair ballot2(bool p0, bool p1) {
-    MaskPair m;
-    m.lo = __ballot(p0);
-    m.hi = __ballot(p1);
-    return m;
-}
-
 
 // ---- observation builder ----------------------------------------------------------------------
 // Border cell standing for a goal outside the 9x9 field of view (statetransformer.py:47-66).  The
@@ -191,106 +174,27 @@ __global__ __launch_bounds__(256) void rollout_observe_kernel(const RolloutArgs 
 }
 
 // ---- communication GSO ---------------------------------------------------------------------------
-// A = (pdist < R) with zero diagonal; at step 0 R is divided by 1.1 once and multiplied by 1.1
-// until the graph is connected; S = D^-1/2 A D^-1/2 in fp64 (isolated nodes -> 0), rounded to fp32
-// (what `S.float()` does to the simulator's float64 GSO).  Connectivity by graph search on
-// adjacency bit masks -- the same boolean as the reference's Laplacian-spectrum test.
-// Largest integer d2 with sqrt((double)d2) < R, i.e. the exact integer form of the reference's
-// `distance < R` test on integer positions (-1 if none).  Evaluated with the same correctly rounded
-// fp64 sqrt the reference's pdist uses, once per radius instead of once per agent pair.
-__device__ __forceinline__ long long dist2_threshold(double R) {
-    if (!(R > 0.0)) return -1;
-    // start at ceil(fl(R*R)) >= the answer (the answer is < R^2 <= fl(R*R) (1 + 2^-53)) and walk down:
-    // two square roots in the common case instead of four
-    long long t = (long long)ceil(R * R);
-    while (t >= 0 && !(sqrt((double)t) < R)) --t;
-    return t;
-}
-
-// The threshold as the unsigned bound every `d2 <= T` test compares against, and the squared distance of two cells in
-// the same unsigned word.  Coordinates lie in [0, 65535] (a map of 65 536 cells can be 1 x 65 536), so
-// d2 <= 65535^2 + 0^2 = 4 294 836 225 < 2^32 - 1: neither the products nor the sum wrap, and the clamp to 0xffffffff
-// never cuts a threshold below a distance that occurs.  r <= 0: the threshold is -1 and the bound 0 (no pair is at
-// distance 0: agents stand on distinct cells).
-__device__ __forceinline__ unsigned dist2_bound(double r) {
-    const long long T = dist2_threshold(r);
-    return T > 0xffffffffLL ? 0xffffffffu : T < 0 ? 0u : (unsigned)T;
-}
-
-__device__ __forceinline__ unsigned dist2(int ax, int ay, int bx, int by) {
-    const unsigned dx = (unsigned)(ax - bx), dy = (unsigned)(ay - by);
-    return dx * dx + dy * dy;
-}
-
-constexpr int kGsoSmemBytes = 2 * kMaxAgents * 8 + kMaxAgents * 8 + 32;   // adj [N][2] | inv [N] | radius, flag
-
-// Communication graph of one episode on ONE wavefront (lane l: agents l and l + 64), registers only:
-//   * adjacency row i = ballot over the lanes of "dist(i, me) < R" with agent i's cell broadcast by
-//     readlane (N ballots instead of N^2 / 64 lane-loops; the relation is symmetric);
-//   * connectivity by LEVEL-synchronous search from node 0: a node joins when its row meets the
-//     frontier -- one ballot per level (graph diameter) instead of one LDS round trip per node;
-//   * at step 0 (grow) the radius is divided by 1.1 once and multiplied by 1.1 until connected, the
-//     same fp64 sequence as the host loop (multirobotsim_dcenlocal.py:342-348).
-// Leaves adj [N][2] (128-bit rows), inv [N] (fp64 D^-1/2, 0 for isolated nodes), the flag and the final
-// radius in LDS for gso_store.
+// (statement and shared pieces: comm_graph.hip)
+// Communication graph of one episode on ONE wavefront (lane l: agents l and l + 64), registers only; with grow
+// (step 0) the radius search runs here too, a sequential loop.  Leaves adj, inv, the flag and the final radius in
+// LDS (GsoLds) for gso_store.
 __device__ __forceinline__ void gso_wave0(const RolloutArgs& p, const int* pos, bool grow, double r,
                                           char* smem, int lane) {
-    unsigned long long* adj = reinterpret_cast<unsigned long long*>(smem);          // [N][2]
-    double* inv = reinterpret_cast<double*>(adj + 2 * kMaxAgents);                  // [N]
-    double* shared_r = inv + kMaxAgents;                                            // [1]
-    int* shared_flag = reinterpret_cast<int*>(shared_r + 1);                        // [1]
+    const GsoLds L = gso_layout(smem);
     const int N = p.N;
-    const bool two = N > 64;
-    int px[2], py[2];
-    bool live[2];
+    const WaveAgents A = wave_agents_load(pos, N, lane);
+    WaveRows rows = {{0ull, 0ull}, {0ull, 0ull}};
+    const bool connected = rollout_radius_search(r, grow, [&](unsigned T) {
+        wave_adjacency_rows(A, N, lane, T, rows);
+        return wave_connected(rows, A.live, N);
+    });
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int n = lane + 64 * h;
-        live[h] = n < N;
-        px[h] = live[h] ? pos[2 * n] : -(1 << 20);            // dead lanes: far away from everything
-        py[h] = live[h] ? pos[2 * n + 1] : -(1 << 20);
+        if (A.live[h]) { L.adj[2 * n] = rows.a0[h]; L.adj[2 * n + 1] = rows.a1[h]; }
     }
-    unsigned long long a0[2] = {0ull, 0ull}, a1[2] = {0ull, 0ull};                 // my agents' rows
-    if (grow) r = r / 1.1;
-    int connected = 0;
-    // Termination with grow: r grows by 1.1 per trip, so the bound reaches 65535^2 (the largest d2 of two cells, below
-    // the clamp of dist2_bound) after finitely many trips; from then on every pair is an edge and the graph is connected.
-    for (;;) {
-        if (grow) r = r * 1.1;
-        const unsigned Tu = dist2_bound(r);              // d2 < 2^32 - 1: coordinates in [0, 65535]
-        for (int i = 0; i < N; ++i) {
-            const int bx = lane_get(px, i), by = lane_get(py, i);
-            bool e[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                e[h] = live[h] && lane + 64 * h != i && dist2(px[h], py[h], bx, by) <= Tu;
-            }
-            const MaskPair row = ballot2(e[0], two && e[1]);
-            if (lane == (i & 63)) {
-                a0[i >> 6] = row.lo;
-                a1[i >> 6] = row.hi;
-            }
-        }
-        MaskPair R = {1ull, 0ull}, F = R;                              // reached set, frontier
-        while (F.lo | F.hi) {
-            const MaskPair nb = ballot2(live[0] && ((a0[0] & F.lo) | (a1[0] & F.hi)) != 0ull,
-                                        two && live[1] && ((a0[1] & F.lo) | (a1[1] & F.hi)) != 0ull);
-            F.lo = nb.lo & ~R.lo; F.hi = nb.hi & ~R.hi;
-            R.lo |= nb.lo; R.hi |= nb.hi;
-        }
-        connected = __popcll(R.lo) + __popcll(R.hi) == N;
-        if (connected || !grow) break;
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int n = lane + 64 * h;
-        if (live[h]) {
-            const int deg = __popcll(a0[h]) + __popcll(a1[h]);
-            adj[2 * n] = a0[h]; adj[2 * n + 1] = a1[h];
-            inv[n] = deg ? sqrt(1.0 / (double)deg) : 0.0;
-        }
-    }
-    if (lane == 0) { *shared_r = r; *shared_flag = connected; }
+    wave_store_inv(rows, A.live, lane, L.inv);
+    if (lane == 0) { *L.radius = r; *L.connected = connected; }
 }
 
 // The same graph built by ALL waves of the workgroup (no radius growth): the N adjacency rows are independent,
@@ -301,79 +205,36 @@ __device__ __forceinline__ void gso_wave0(const RolloutArgs& p, const int* pos, 
 // that remains.  Contains TWO workgroup barriers: every thread of the workgroup must call it.
 __device__ __forceinline__ void gso_all_waves(const RolloutArgs& p, const int* pos, double r, char* smem, int tid,
                                               int nt) {
-    unsigned long long* adj = reinterpret_cast<unsigned long long*>(smem);          // [N][2]
-    double* inv = reinterpret_cast<double*>(adj + 2 * kMaxAgents);                  // [N]
-    double* shared_r = inv + kMaxAgents;                                            // [1]
-    int* shared_flag = reinterpret_cast<int*>(shared_r + 1);                        // [1]
+    const GsoLds L = gso_layout(smem);
     const int N = p.N, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-    const bool two = N > 64;
-    int px[2], py[2];
-    bool live[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int n = lane + 64 * h;
-        live[h] = n < N;
-        px[h] = live[h] ? pos[2 * n] : -(1 << 20);
-        py[h] = live[h] ? pos[2 * n + 1] : -(1 << 20);
-    }
+    const WaveAgents A = wave_agents_load(pos, N, lane);
     const unsigned Tu = dist2_bound(r);
     for (int i = wave; i < N; i += nw) {
-        const int bx = lane_get(px, i), by = lane_get(py, i);
-        bool e[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            e[h] = live[h] && lane + 64 * h != i && dist2(px[h], py[h], bx, by) <= Tu;
-        }
-        const MaskPair row = ballot2(e[0], two && e[1]);
-        if (lane == 0) { adj[2 * i] = row.lo; adj[2 * i + 1] = row.hi; }
+        const MaskPair row = wave_adjacency_row(A, i, N, lane, Tu);
+        if (lane == 0) { L.adj[2 * i] = row.lo; L.adj[2 * i + 1] = row.hi; }
     }
     __syncthreads();
     if (wave == 0) {
-        unsigned long long a0[2] = {0ull, 0ull}, a1[2] = {0ull, 0ull};
+        WaveRows rows = {{0ull, 0ull}, {0ull, 0ull}};
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int n = lane + 64 * h;
-            if (live[h]) { a0[h] = adj[2 * n]; a1[h] = adj[2 * n + 1]; }
+            if (A.live[h]) { rows.a0[h] = L.adj[2 * n]; rows.a1[h] = L.adj[2 * n + 1]; }
         }
-        MaskPair R = {1ull, 0ull}, F = R;                              // reached set, frontier
-        while (F.lo | F.hi) {
-            const MaskPair nb = ballot2(live[0] && ((a0[0] & F.lo) | (a1[0] & F.hi)) != 0ull,
-                                        two && live[1] && ((a0[1] & F.lo) | (a1[1] & F.hi)) != 0ull);
-            F.lo = nb.lo & ~R.lo; F.hi = nb.hi & ~R.hi;
-            R.lo |= nb.lo; R.hi |= nb.hi;
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int n = lane + 64 * h;
-            if (live[h]) {
-                const int deg = __popcll(a0[h]) + __popcll(a1[h]);
-                inv[n] = deg ? sqrt(1.0 / (double)deg) : 0.0;
-            }
-        }
-        if (lane == 0) { *shared_r = r; *shared_flag = __popcll(R.lo) + __popcll(R.hi) == N; }
+        const bool connected = wave_connected(rows, A.live, N);
+        wave_store_inv(rows, A.live, lane, L.inv);
+        if (lane == 0) { *L.radius = r; *L.connected = connected; }
     }
     __syncthreads();
 }
 
-// S = float(D^-1/2 A D^-1/2) to HBM by all threads, radius / connected by thread 0 (after a barrier)
-__device__ __forceinline__ void gso_store(const RolloutArgs& p, int b, const char* smem, int tid, int nt) {
-    const unsigned long long* adj = reinterpret_cast<const unsigned long long*>(smem);
-    const double* inv = reinterpret_cast<const double*>(adj + 2 * kMaxAgents);
-    const double* shared_r = inv + kMaxAgents;
-    const int* shared_flag = reinterpret_cast<const int*>(shared_r + 1);
-    const int N = p.N;
-    float* S = p.S + (size_t)b * N * N;
-    for (int i = tid / 16; i < N; i += nt / 16) {               // nt/16 rows in flight, 16 lanes per row
-        const unsigned long long w0 = adj[2 * i], w1 = adj[2 * i + 1];
-        const double ii = inv[i];
-        for (int j = tid & 15; j < N; j += 16) {
-            const bool on = j < 64 ? (w0 >> j) & 1ull : (w1 >> (j - 64)) & 1ull;
-            S[i * N + j] = on ? (float)(ii * inv[j]) : 0.f;
-        }
-    }
+// S to HBM by all threads, radius / connected by thread 0 (after a barrier)
+__device__ __forceinline__ void gso_store(const RolloutArgs& p, int b, char* smem, int tid, int nt) {
+    const GsoLds L = gso_layout(smem);
+    gso_store_S(L, p.N, p.S + (size_t)b * p.N * p.N, nullptr, tid, nt);
     if (tid == 0) {
-        p.radius[b] = *shared_r;
-        if (p.connected) p.connected[b] = *shared_flag;
+        p.radius[b] = *L.radius;
+        if (p.connected) p.connected[b] = *L.connected;
     }
 }
 

@@ -334,10 +334,9 @@ __global__ __launch_bounds__(1024) void rollout_team_move_kernel(const RolloutAr
 }
 
 // ---- communication GSO ------------------------------------------------------------------------------------------
-// Same statement as gso_wave0 / gso_store: A = (d2 <= dist2_threshold(R)) off the diagonal; at step 0 R /= 1.1, then
-// R *= 1.1 until connected; connectivity by a level-synchronous search from node 0 (a node joins when one of the
-// frontier's nodes is within reach; N-bit frontier sets in LDS, one barrier per level); D^-1/2 in fp64;
-// S = float(inv_i * inv_j).  The adjacency is recomputed from the positions instead of being stored (N^2 bits).
+// The statement of comm_graph.hip (its dist2 / dist2_bound / inv_sqrt_degree) for one thread per agent: a node joins the
+// level-synchronous search when one of the frontier's nodes is within reach (N-bit frontier sets in LDS, one barrier per
+// level).  The adjacency is recomputed from the positions instead of being stored (N^2 bits).
 __host__ __device__ inline size_t team_gso_smem(int N) {
     return round16((size_t)8 * N) + (size_t)8 * N + 3 * kTeamWords * 8 + 16;
 }
@@ -397,7 +396,7 @@ __global__ __launch_bounds__(1024) void rollout_team_gso_kernel(const RolloutArg
     if (live) {
         int deg = 0;
         for (int j = 0; j < N; ++j) deg += j != t && dist2(px[j], py[j], mx, my) <= Tu;
-        inv[t] = deg ? sqrt(1.0 / (double)deg) : 0.0;
+        inv[t] = inv_sqrt_degree(deg);
     }
     __syncthreads();
     // S: thread t owns columns t, t + nt, ...; rows go by (consecutive threads store consecutive floats)

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(1024) void rollout_team_lists_kernel(const RolloutA
         connected = !team_any(live && !in_r, words, t, nw);
         if (connected || !grow) break;
     }
-    if (live) inv[t] = cnt ? sqrt(1.0 / (double)cnt) : 0.0;
+    if (live) inv[t] = inv_sqrt_degree(cnt);
     __syncthreads();
     if (live) {
         cnt_out[lcol] = cnt;

@@ -168,11 +168,11 @@ def load_golden():
 BAD_MOVE, BAD_STATE = 1, 2                               # GNNPP_SCHEDULE_* status bits
 
 
-def make_call(name, grids, goals, schedules, status=None, fp64=True):
+def make_call(name, grids, goals, schedules, status=None, fp64=True, radius0=5.0):
     return {'name': name, 'grids': np.ascontiguousarray(grids, dtype=np.uint8),
             'goals': np.ascontiguousarray(np.stack(goals), dtype=np.int32),
             'schedules': [np.ascontiguousarray(s, dtype=np.int32) for s in schedules],
-            'status': status or [('eq', 0)] * len(schedules), 'fp64': fp64}
+            'status': status or [('eq', 0)] * len(schedules), 'fp64': fp64, 'radius0': radius0}
 
 
 def flipped(grid, goal, schedule):
@@ -248,6 +248,47 @@ def team_growths_call():
     return make_call('team_growths', np.stack([wide[0], tight[0]]), [wide[1], tight[1]], scheds, fp64=False)
 
 
+def integer_bounds(radius0, growth):
+    """The integer thresholds (largest d2 with sqrt(d2) < r) of the radii radius0 * 1.1^k, k = 0 .. growth."""
+    out, r = [], radius0
+    for _ in range(growth + 1):
+        t = int(np.ceil(r * r))
+        while t >= 0 and not np.sqrt(float(t)) < r:
+            t -= 1
+        out.append(t)
+        r = r * 1.1
+    return out
+
+
+def repeated_bounds_call():
+    """radius0 = 1.0, where consecutive radii share an integer threshold (1.1, 1.21, 1.331 all admit d2 <= 1 only): trips
+    that build nothing new and still count.  Two cases of two standing steps each on an empty 3 x 24 map: seven agents
+    in a row three cells apart (connected from 1.1^12 on) and ten agents two cells apart (from 1.1^8 on)."""
+    def standing(N, gap):
+        pos = np.stack([np.ones(N, np.int64), gap * np.arange(N)], 1)
+        return pos, np.stack([pos, pos])
+    (g3, s3), (g2, s2) = standing(7, 3), standing(10, 2)
+    pad = np.array([[1, 19], [1, 20], [1, 21]])        # (the call's N is 10: three more behind the chain's end at column 18)
+    g3, s3 = np.concatenate([g3, pad]), np.concatenate([s3, np.stack([pad, pad])], 1)
+    call = make_call('repeated_bounds', np.zeros((3, 24), np.uint8), [g3, g2], [s3, s2], radius0=1.0)
+    wants = call_wants(call)
+    assert [w['growth'] for w in wants] == [12, 8]
+    for w in wants:
+        b = integer_bounds(1.0, w['growth'])
+        assert sum(x == y for x, y in zip(b, b[1:])) >= 4, b                  # the same bound on consecutive trips
+    return call
+
+
+def lane_boundary_calls():
+    """64 and 65 agents: the last team without and the first with a second agent per lane of the one-wave kernels."""
+    rng = np.random.default_rng(64)
+    calls = []
+    for N in (64, 65):
+        grid, goal, paths = random_case(rng, N, 26, 26, density=0.05, max_steps=2)
+        calls.append(make_call('%d_agents_on_26x26' % N, grid, [goal], [schedule_of(paths, goal)]))
+    return calls
+
+
 def team_status_bits_call():
     """140 agents, four steps, six times: legal, a diagonal move of agent 133, agent 70 on an obstacle, agent 139 off
     the map at step 0, agent 0 beyond the last column at step 2, legal."""
@@ -278,7 +319,8 @@ def call_wants(call):
     if call['name'] not in _CALL_WANTS:
         grids = call['grids']
         _CALL_WANTS[call['name']] = [
-            reference_samples(grids if grids.ndim == 2 else grids[c], call['goals'][c], call['schedules'][c])
+            reference_samples(grids if grids.ndim == 2 else grids[c], call['goals'][c], call['schedules'][c],
+                              call['radius0'])
             if call['status'][c] == ('eq', 0) else None for c in range(len(call['schedules']))]
     return _CALL_WANTS[call['name']]
 

@@ -126,6 +126,10 @@ CASES = [
     dict(name='packed_box/degree129', pos=_packed_box(), radius=20.0, grow=0, connected=[1], degree=129),
     dict(name='chain70', pos=_chain(70, 3), radius=3.5, grow=0, connected=[1]),
     dict(name='chain70/grow', pos=_chain(70, 3), radius=1.0, grow=1, connected=[1]),
+    # the thread-per-agent kernels (N > 128, here past the 192 / 193 wave boundary) growing from a radius below 2, where
+    # consecutive radii share an integer threshold (1.0, 1.1 .. 1.331 all admit d2 <= 1 only): rollout_team_lists_kernel
+    # keeps its lists over such a trip, rollout_team_gso_kernel searches again; both must end at the oracle's radius
+    dict(name='chain193/grow_from_1', pos=_chain(193, 3), radius=1.0, grow=1, connected=[1], min_growth=12),
 ]
 GPU_CASES = [
     dict(name='B2N1024/map64/grow', pos=_scatter(20, 2, 1024, 64), radius=2.0, grow=1),

@@ -170,3 +170,17 @@ def test_large_team_and_map_without_stage(lib):
         assert np.array_equal(out['obs'], want['input']) and np.array_equal(out['S64'], want['GSO'])
         assert np.array_equal(out['target'], want['target'])
     assert full['goals'].shape[1] == 128 and wide['grids'].shape == (230, 230)
+
+
+def test_radii_that_share_an_integer_bound(lib):
+    """radius0 = 1.0: growth counts the trips whose integer threshold equals the one before (nothing is rebuilt there)."""
+    case = ec.repeated_bounds_call()
+    out = call(lib, case['grids'], case['goals'], case['schedules'], radius0=case['radius0'])
+    ec.assert_call_outputs(out, case, np.nan)
+    assert (out['step_info'] & 0xffff).tolist() == [12, 12, 8, 8]
+
+
+def test_teams_at_the_second_agent_per_lane(lib):
+    for case in ec.lane_boundary_calls():
+        out = call(lib, case['grids'], case['goals'], case['schedules'])
+        ec.assert_call_outputs(out, case, np.nan)

@@ -129,6 +129,15 @@ def test_small_team_golden_case_same_bytes_as_one_wave_call(lib, ci):
     assert_same_bytes(out, call(lib, g['grid'], g['goal'][None], [g['schedule']], team=False))
 
 
+def test_radii_that_share_an_integer_bound_same_bytes_as_one_wave_call(lib):
+    """radius0 = 1.0: growth counts the trips whose integer threshold equals the one before, in both calls."""
+    case = ec.repeated_bounds_call()
+    out = call(lib, case['grids'], case['goals'], case['schedules'], radius0=case['radius0'])
+    ec.assert_call_outputs(out, case, np.nan)
+    assert (out['step_info'] & 0xffff).tolist() == [12, 12, 8, 8]
+    assert_same_bytes(out, call(lib, case['grids'], case['goals'], case['schedules'], radius0=case['radius0'], team=False))
+
+
 def test_ragged_cases_and_batched_maps_same_bytes_as_one_wave_call(lib):
     """Cases of 20, 7 and 3 steps with a map each (24 agents: 16-byte stores; 10 agents: 4-byte stores)."""
     for ci in (4, 0):

@@ -59,7 +59,8 @@ def device_call(expert, call, team, misalign=False):
                                  radius=f(C, dtype=torch.float64), growth=f(C, dtype=torch.int32),
                                  status=f(C, dtype=torch.int32), step_growth=f(T, dtype=torch.int32), bounds=bounds,
                                  workspace=torch.full((nbytes,), 0x5a, dtype=torch.uint8, device=dev))
-    (expert.enqueue_schedule_team_samples if team else expert.enqueue_schedule_samples)(grid, goal, pos, start, out)
+    (expert.enqueue_schedule_team_samples if team else expert.enqueue_schedule_samples)(grid, goal, pos, start, out,
+                                                                                       commR=call['radius0'])
     torch.cuda.synchronize()
     return {k: None if getattr(out, name) is None else getattr(out, name).cpu().numpy() for k, name in KEYS.items()}
 
@@ -91,6 +92,19 @@ def test_status_bits_flag_only_their_case(expert):
 
 def test_large_team_and_map_without_stage(expert):
     for call in ec.calls_without_stage():
+        run_call(expert, call, team=False)
+
+
+def test_radii_that_share_an_integer_bound(expert):
+    """radius0 = 1.0 through the one-wave and the large-team call: the same bytes, growth over repeated thresholds."""
+    call = ec.repeated_bounds_call()
+    out = run_call(expert, call, team=False)
+    assert (out['step_info'] & 0xffff).tolist() == [12, 12, 8, 8]
+    assert_same_bytes(run_call(expert, call, team=True), out)
+
+
+def test_teams_at_the_second_agent_per_lane(expert):
+    for call in ec.lane_boundary_calls():
         run_call(expert, call, team=False)
 
 
