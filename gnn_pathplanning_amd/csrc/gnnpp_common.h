@@ -280,6 +280,17 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
     return v;
 }
+// ... the smallest / the largest `v` of the wave (an integer below 2^24 goes through as a float exactly)
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
 
 // value of `v` held by the lane whose index differs in bit 0 / bit 1 (the partner inside a quad of four lanes): one
 // v_mov_b32_dpp quad_perm -- no LDS, no SALU.  Every lane of the wave must take part.

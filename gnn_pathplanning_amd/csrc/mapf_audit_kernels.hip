@@ -63,20 +63,6 @@ inline size_t mapf_audit_lds_bytes(int threads, int H, int W) {
     return (size_t)((H * W + 1) / 2 + 3 * threads + 3 * (kAuditChunk + 1) + 8 * kAuditWaves) * sizeof(int);
 }
 
-__device__ __forceinline__ int audit_wave_min(int v) {
-    float f = (float)v;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) f = fminf(f, __shfl_xor(f, m));
-    return (int)f;
-}
-
-__device__ __forceinline__ int audit_wave_max(int v) {          // v >= 0
-    float f = (float)v;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) f = fmaxf(f, __shfl_xor(f, m));
-    return (int)f;
-}
-
 __device__ __forceinline__ void audit_raise(int* flag) {
     __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // (on LDS; every writer writes 1)
 }
@@ -198,7 +184,7 @@ __global__ __launch_bounds__(1024) void mapf_audit_kernel(const MapfAuditArgs p)
         int* ws = p.ws + (size_t)item * (kAuditHdr + N);
         if (active) ws[kAuditHdr + tid] = lastoff;
         const int s0 = (int)wave_sum((float)cnt0), s1 = (int)wave_sum((float)cnt1), s2 = (int)wave_sum((float)cnt2);
-        const int s3 = (int)wave_sum((float)cnt3), s4 = (int)wave_sum((float)off_start), kmin = audit_wave_min(key);
+        const int s3 = (int)wave_sum((float)cnt3), s4 = (int)wave_sum((float)off_start), kmin = (int)wave_min((float)key);
         if ((tid & 63) == 0) {
             int* pw = part + (tid >> 6) * 8;
             pw[0] = s0;
@@ -256,7 +242,7 @@ __global__ __launch_bounds__(1024) void mapf_audit_final_kernel(const MapfAuditA
             arrival[tid] = arr;
         }
         const int away = (int)wave_sum(arr < 0 ? 1.0f : 0.0f);
-        const int amax = audit_wave_max(arr < 0 ? 0 : arr);
+        const int amax = (int)wave_max((float)(arr < 0 ? 0 : arr));
         const int asum = (int)wave_sum((float)(arr < 0 ? 0 : arr));
         if ((tid & 63) == 0) {
             part[(tid >> 6) * 4] = away;
@@ -289,7 +275,7 @@ __global__ __launch_bounds__(1024) void mapf_audit_final_kernel(const MapfAuditA
                     cand = tid;
             }
         }
-        const int cmin = audit_wave_min(cand);
+        const int cmin = (int)wave_min((float)cand);
         if ((tid & 63) == 0) part2[tid >> 6] = cmin;
         __syncthreads();
         if (tid < 4) {

@@ -674,3 +674,25 @@ def both_widest_one_word_map():
 def both_128_agents_on_16x16():
     g, s, gl = random_cases(np.random.default_rng(77), 1, 128, 16, density=0.05)[0]
     return make_case('both_128_agents_on_16x16', g, s, gl, 64, poison_ws=True)
+
+
+@_case(BOTH, 'unplanned_tail_past_one_wave_of_agents')
+def both_unplanned_tail_past_one_wave_of_agents():
+    """16 x 16, 72 agents, T_max + 1 = 41: agents 0 .. 69 are committed, agent 70 is walled into the corner, agent 71 is
+    never planned -- the unplanned rows of the schedule and of the arrivals lie past the first 64 agents."""
+    grid = np.zeros((16, 16), np.uint8)
+    grid[13, 13:] = 1
+    grid[13:, 13] = 1                                           # rows and columns 14, 15 walled in
+    rng = np.random.default_rng(70)
+    free = np.argwhere(grid == 0)
+    free = free[(free[:, 0] < 13) | (free[:, 1] < 13)]
+    idx = rng.choice(len(free), 2 * 72, replace=False)
+    starts, goals = free[idx[:72]].copy(), free[idx[72:]].copy()
+    starts[70] = (15, 15)
+
+    def facts(wants):
+        w = wants[0]
+        assert w['status'] == NO_PATH and w['failing'] == 70
+        assert (w['arrival'][:70] >= 0).all() and w['arrival'][70:].tolist() == [-1, -1]
+        assert (w['schedule'][:, 70:] == -1).all() and (w['schedule'][:, :70] >= 0).all()
+    return make_case('both_unplanned_tail_past_one_wave_of_agents', grid, starts, goals, 40, facts=facts, poison_ws=True)

@@ -250,6 +250,22 @@ def one_wave_items_finish_at_different_steps():
 
 
 @_case()
+def several_items_per_workgroup_end_one_bit_past_a_word():
+    """7 x 65: an item is 14 threads of a wave of its own, four items per workgroup, seven items so the second batch
+    is partial.  Row 3 is a wall whose only door is column 64, the one bit of word 1: every way between the halves
+    passes it, in every item at its own place in the workgroup's image.  (6, 0) is walled in."""
+    grid = np.zeros((7, 65), np.uint8)
+    grid[3, :64] = 1
+    grid[5, 0] = grid[6, 1] = 1
+
+    def facts(dist, lm, lf):
+        assert dist.tolist() == [[70, 3, -1, 0, 70, -1, 130]] and lm.tolist() == [-1] and lf.tolist() == [-1]
+    return make_case('several_items_per_workgroup_end_one_bit_past_a_word', grid,
+                     [[0, 0], [3, 64], [0, 5], [2, 64], [6, 64], [6, 0], [4, 0]],
+                     [[6, 64], [0, 64], [6, 0], [2, 64], [0, 0], [0, 64], [2, 0]], facts)
+
+
+@_case()
 def largest_map_nearly_open():
     """256 x 256: 1024 threads, rows of four words; distances around 500."""
     grid = np.zeros((256, 256), np.uint8)

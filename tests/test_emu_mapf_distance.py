@@ -90,6 +90,11 @@ def test_one_wave_items_finish_at_different_steps(lib):
     assert out['dist'][0, :7].tolist() == [126, 64, 0, -1, -2, -2, 0]
 
 
+def test_several_items_per_workgroup_end_one_bit_past_a_word(lib):
+    """7 x 65: four items of 14 threads in a workgroup and a partial second batch, the only door in the bit of word 1."""
+    assert run_case(lib, 'several_items_per_workgroup_end_one_bit_past_a_word')['dist'][0, 6] == 130
+
+
 def test_largest_map(lib):
     assert run_case(lib, 'largest_map_nearly_open')['dist'][0, :2].tolist() == [510, 510]
 

@@ -142,9 +142,9 @@ def test_batched_grid_next_to_shared_grid(lib):
 
 def test_same_bytes_as_the_one_wave_call(lib):
     """Every case both entry points accept: all outputs byte-equal (random, crowded with failures, restarts with a bad
-    order, the widest one-word map, 128 agents)."""
+    order, the widest one-word map, 128 agents, the unplanned tail behind a failing agent 70 of 72)."""
     for name in ('random_10x10', 'crowded_with_failures', 'restarts_with_a_bad_order', 'widest_one_word_map',
-                 '128_agents_on_16x16'):
+                 '128_agents_on_16x16', 'unplanned_tail_past_one_wave_of_agents'):
         case = mc.BOTH[name]()
         args = (lib, case['grid'], case['starts'], case['goals'], case['T'], case['orders'])
         a = call(*args, team=False)
