@@ -31,6 +31,8 @@ typedef ::gnnpp_rollout RolloutArgs;      // the C-ABI struct itself (include/gn
 // Largest integer d2 with sqrt((double)d2) < R, i.e. the exact integer form of the reference's
 // `distance < R` test on integer positions (-1 if none).  Evaluated with the same correctly rounded
 // fp64 sqrt the reference's pdist uses, once per radius instead of once per agent pair.
+// For R < 65536 only (dist2_bound decides the rest before any cast): there R <= 65536 - 2^-37, R * R < 2^32 and
+// ceil(fl(R * R)) <= 2^32 converts exactly.  Beyond 2^63 (R >= 3.04e9, which the API accepts) the cast would be undefined.
 __device__ __forceinline__ long long dist2_threshold(double R) {
     if (!(R > 0.0)) return -1;
     // start at ceil(fl(R*R)) >= the answer (the answer is < R^2 <= fl(R*R) (1 + 2^-53)) and walk down:
@@ -45,7 +47,12 @@ __device__ __forceinline__ long long dist2_threshold(double R) {
 // d2 <= 65535^2 + 0^2 = 4 294 836 225 < 2^32 - 1: neither the products nor the sum wrap, and the clamp to 0xffffffff
 // never cuts a threshold below a distance that occurs.  r <= 0: the threshold is -1 and the bound 0 (no pair is at
 // distance 0: agents stand on distinct cells).
+// r >= 65536 (infinity included): the bound IS the clamp, decided on the double.  Every d2 an unsigned word holds is
+// <= 2^32 - 1 and sqrt(2^32 - 1) = 65536 - 2^-17 - ... rounds to a double below 65536.0 (ulp 2^-37), so sqrt(d2) < r
+// for all of them.  The walk-down gave the same word wherever its cast was defined (at r = 65536.0: 2^32 - 1 itself);
+// below 65536 nothing changes, so every radius keeps the integer it had.
 __device__ __forceinline__ unsigned dist2_bound(double r) {
+    if (r >= 65536.0) return 0xffffffffu;
     const long long T = dist2_threshold(r);
     return T > 0xffffffffLL ? 0xffffffffu : T < 0 ? 0u : (unsigned)T;
 }

@@ -311,6 +311,209 @@ def team_status_bits_call():
                      [('eq', 0), ('eq', BAD_MOVE), ('has', BAD_STATE), ('has', BAD_STATE), ('has', BAD_STATE), ('eq', 0)])
 
 
+# ---- thin maps: a coordinate difference of up to 65 535 (team call) and 16 383 (the one-wave call's limit) -----------
+# d2 reaches 65535^2 = 4 294 836 225: above 2^31, below 2^32 (tests/rollout_team_sim_cases.py has the simulator's twins).
+# Every schedule has 2 or 3 steps: the restatement's cost is the first step's radius search, the later steps carry it.
+THIN_SIDE = 65536                                        # GNNPP_ROLLOUT_TEAM_MAX_CELLS as one row or one column
+ONE_WAVE_SIDE = 16384                                    # schedule_samples_launch: H, W <= 16384
+HUGE_RADII = (65535.5, 65536.0, 70000.0, 3.0e9, 3.1e9, 1e10, 1e154, 1e155, 9e299)
+
+
+def thin_shapes(side):
+    return ((1, side), (side, 1))
+
+
+def _on_strip(H, cells):
+    """[..., 2] positions of `cells` along the long side of an H x W map of one row or one column."""
+    cells = np.asarray(cells, np.int64)
+    pos = np.zeros(cells.shape + (2,), np.int64)
+    pos[..., 1 if H == 1 else 0] = cells
+    return pos
+
+
+def _spread(N, side):
+    """N cells spread evenly over 0 .. side - 1, both ends occupied."""
+    return np.round(np.linspace(0, side - 1, N)).astype(np.int64)
+
+
+def _two_ends(N, side):
+    """One half of the team on the first cells, the other on the last (N = 2: the two end cells)."""
+    return np.concatenate([np.arange(N // 2), side - (N - N // 2) + np.arange(N - N // 2)])
+
+
+def _standing(H, W, cells, steps=2):
+    """(grid, goal, schedule) of a team that waits on `cells` of an empty strip."""
+    pos = _on_strip(H, cells)
+    assert len(set(np.asarray(cells).tolist())) == len(cells) and min(cells) >= 0 and max(cells) < max(H, W)
+    return np.zeros((H, W), np.uint8), pos, np.stack([pos] * steps)
+
+
+def _d2(pos):
+    p = np.asarray(pos, np.int64)
+    return ((p[:, None] - p[None]) ** 2).sum(-1)
+
+
+def _assert_wrapping_inputs(pos, name):
+    """Some pair has d2 above 2^31, and some pair has 2^31 - 2^17 < d2 mod 2^32: what a wrapped product gets wrong
+    (rollout_team_sim_cases._check_wrapping_inputs)."""
+    d2 = _d2(pos)
+    assert (d2 > 2 ** 31).any() and (d2 % 2 ** 32 > 2 ** 31 - 2 ** 17).any() and d2.max() < 2 ** 32, name
+
+
+def growth_to_span(radius0, gap):
+    """The multiplications by 1.1, in fp64 as the reference makes them, until sqrt(gap^2) < radius: (growth, radius)."""
+    r, k = radius0, 0
+    while not np.sqrt(float(gap * gap)) < r:
+        r, k = r * 1.1, k + 1
+    return k, r
+
+
+def both_ends_call(H, W, fp64=True):
+    """Two agents on the two end cells of the strip, two standing steps.  On 65 536 cells the radius grows exactly 100
+    times to 5 * 1.1^100; the last bound but one lies above 2^31 (the signed range) and the last above 2^32: the
+    0xffffffff clamp of dist2_bound."""
+    side = max(H, W)
+    grid, goal, sched = _standing(H, W, _two_ends(2, side))
+    call = make_call('both_ends_%dx%d' % (H, W), grid, [goal], [sched], fp64=fp64)
+    want = call_wants(call)[0]
+    assert (want['growth'], want['radius']) == growth_to_span(5.0, side - 1)
+    if side == THIN_SIDE:
+        assert want['growth'] == 100 and want['radius'] == 68903.06169911187
+        assert (want['radius'] / 1.1) ** 2 > 2 ** 31 and want['radius'] ** 2 > 2 ** 32
+        _assert_wrapping_inputs(sched[0], call['name'])
+    assert (want['GSO'] == np.array([[0.0, 1.0], [1.0, 0.0]])).all()
+    return call
+
+
+def two_ends_call(H, W, N, fp64=True, radius0=5.0):
+    """One half of the team on the first cells of the strip, the other on the last; two standing steps.  Each half is a
+    chain from radius0 on; the halves meet only when the radius spans the gap between them.  A squared distance that
+    wrapped would join them early: a smaller growth."""
+    side = max(H, W)
+    cells = _two_ends(N, side)
+    grid, goal, sched = _standing(H, W, cells)
+    call = make_call('two_ends_%dx%d_N%d_%s_r%r' % (H, W, N, 'fp64' if fp64 else 'fp32', radius0), grid, [goal], [sched],
+                     fp64=fp64, radius0=radius0)
+    want = call_wants(call)[0]
+    h = N // 2
+    gap = int(cells[h] - cells[h - 1])
+    assert gap == side - N + 1 and (want['growth'], want['radius']) == growth_to_span(radius0, gap)
+    if side == THIN_SIDE:
+        _assert_wrapping_inputs(sched[0], call['name'])
+        assert _d2(sched[0])[:h, h:].min() > 2 ** 31
+    # no edge between the halves at any growth below the final one, and the restatement's graph has them at the final one
+    assert not np.sqrt(float(gap * gap)) < want['radius'] / 1.1
+    G = want['GSO'][0]
+    assert G[h - 1, h] != 0 and (G[:h, h:] != 0).sum() >= 1 and (G[:h, :h] != 0).any(1).all()
+    return call
+
+
+def spread_call(H, W, N, radius0=5.0, fp64=True):
+    """The team evenly spaced over the strip, both ends occupied; two standing steps.  The growth is set by the widest
+    gap between neighbours (512 cells at N = 129 on 65 536)."""
+    side = max(H, W)
+    cells = _spread(N, side)
+    grid, goal, sched = _standing(H, W, cells)
+    call = make_call('spread_%dx%d_N%d_r%r' % (H, W, N, radius0), grid, [goal], [sched], fp64=fp64, radius0=radius0)
+    want = call_wants(call)[0]
+    gap = int(np.diff(cells).max())
+    assert cells[0] == 0 and cells[-1] == side - 1 and ((N, side) != (129, THIN_SIDE) or gap == 512)
+    assert (want['growth'], want['radius']) == growth_to_span(radius0, gap)
+    if side == THIN_SIDE:
+        _assert_wrapping_inputs(sched[0], call['name'])
+    return call
+
+
+def walk_case(H, W, N):
+    """(grid, goal, schedule [3,N,2]) on the strip: the team spread over it; every third agent waits on its goal, the
+    others walk three cells towards the middle, the third move taking them onto their goal (the last state is one legal
+    move from it).  Four cells on either side of every waiting agent -- inside its field of view, on nobody's way -- an
+    obstacle."""
+    side = max(H, W)
+    cells = _spread(N, side)
+    assert np.diff(cells).min() >= 16
+    waits = np.arange(N) % 3 == 0
+    step = np.where(waits, 0, np.where(np.arange(N) < N / 2, 1, -1))
+    sched = _on_strip(H, np.stack([cells + t * step for t in range(3)]))
+    goal = _on_strip(H, cells + 3 * step)
+    rocks = np.concatenate([cells[waits] - 4, cells[waits] + 4])
+    rocks = rocks[(rocks >= 0) & (rocks < side)]
+    assert len(rocks) >= 1 and waits.any() and (step != 0).any()
+    grid = np.zeros(side, np.uint8)
+    grid[rocks] = 1
+    visited = np.concatenate([cells + t * step for t in range(4)])
+    assert not grid[visited].any()
+    return grid.reshape(H, W), goal, sched
+
+
+def walk_call(H, W, N, fp64=True, extra=()):
+    """walk_case and the same case turned by 180 degrees, a map per case (grid_batched, C = 2): the maps differ, so a
+    step that read the other case's map -- c * H * W with H * W up to 65 536 -- shows in channel 0.  Targets along the
+    strip's axis in both directions, and 'stop'.  extra: further (grid, goal, schedule) cases."""
+    grid, goal, sched = walk_case(H, W, N)
+    other, fgoal, fsched = flipped(grid, goal, sched)
+    assert (grid != other).any() and grid.any() and other.any()
+    cases = [(grid, goal, sched), (other, fgoal, fsched)] + list(extra)
+    call = make_call('walk_%dx%d_N%d_%s%s' % (H, W, N, 'fp64' if fp64 else 'fp32', '+%d' % len(extra) if extra else ''),
+                     np.stack([c[0] for c in cases]), [c[1] for c in cases], [c[2] for c in cases], fp64=fp64)
+    axis = (1, 3) if H == 1 else (0, 2)
+    hot = np.concatenate([want['target'].argmax(-1).reshape(-1) for want in call_wants(call)[:2]])
+    assert set(np.unique(hot).tolist()) == {axis[0], axis[1], 4}
+    return call
+
+
+def thin_status_bits_call(N=129):
+    """walk_case on 1 x 65 536 five times: legal, agent 7 at row 1 of the one-row map in step 1, agent N - 1 at column
+    65 536 in step 0, agent 1's last move a diagonal one (its goal at row 1: a one-row map cannot host a legal one),
+    legal."""
+    grid, goal, sched = walk_case(1, THIN_SIDE, N)
+    sched = sched.astype(np.int32)
+    below = sched.copy()
+    below[1, 7, 0] = 1
+    beyond = sched.copy()
+    assert beyond[0, N - 1, 1] == THIN_SIDE - 1
+    beyond[0, N - 1, 1] = THIN_SIDE
+    diag = goal.copy()
+    assert (goal[1] - sched[-1, 1]).tolist() == [0, 1]
+    diag[1, 0] = 1
+    return make_call('thin_status_bits_N%d' % N, grid, [goal, goal, goal, diag, goal], [sched, below, beyond, sched, sched],
+                     [('eq', 0), ('has', BAD_STATE), ('has', BAD_STATE), ('eq', BAD_MOVE), ('eq', 0)])
+
+
+def one_wave_limit_call(H, W, N):
+    """The one-wave call at its map limit (a side of 16 384): walk, walk turned by 180 degrees and the team on the two
+    ends of an empty strip, a map per case."""
+    grid, goal, sched = _standing(H, W, _two_ends(N, max(H, W)), steps=3)
+    return walk_call(H, W, N, extra=[(grid, goal, sched)])
+
+
+def beyond_one_wave_limit_call(H, W):
+    """Two agents on the ends of a strip one cell longer than the one-wave call takes."""
+    assert max(H, W) == ONE_WAVE_SIDE + 1
+    grid, goal, sched = _standing(H, W, _two_ends(2, max(H, W)))
+    return make_call('beyond_one_wave_%dx%d' % (H, W), grid, [goal], [sched])
+
+
+def huge_radius_calls(radius0):
+    """(three agents on 1 x 40, the 129-agent spread on 1 x 65 536) at a radius0 beyond every distance of the map: the
+    restatement says growth 0, radius = radius0, every pair an edge, S64 = sqrt(1 / (N - 1))^2."""
+    assert radius0 in HUGE_RADII
+    grid, goal, sched = _standing(1, 40, np.array([0, 17, 39]))
+    tiny = make_call('huge_radius_tiny_r%r' % radius0, grid, [goal], [sched], radius0=radius0)
+    thin = spread_call(1, THIN_SIDE, 129, radius0=radius0)
+    for call in (tiny, thin):
+        want = call_wants(call)[0]
+        N = call['goals'].shape[1]
+        s = np.sqrt(1. / (N - 1))
+        full = np.full((N, N), (s * 1.0) * s)
+        np.fill_diagonal(full, 0.0)
+        assert want['growth'] == 0 and want['radius'] == radius0 and (want['GSO'] == full).all()
+    # 65535.5 is the first of the radii to span the strip: the ends are 65 535 apart, and a radius of 65 535.0 would not
+    d = np.sqrt(float(_d2(thin['schedules'][0][0]).max()))
+    assert d == 65535.0 and not d < 65535.0 and d < min(HUGE_RADII) == 65535.5
+    return tiny, thin
+
+
 _CALL_WANTS = {}
 
 

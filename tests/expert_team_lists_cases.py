@@ -399,6 +399,77 @@ def case_cap_four_below_the_need(lib, N, side, radius0, run=None):
     assert (h.out['idx'][live] == full.out['idx'][:, :, :need - 4][live]).all()
 
 
+# -- thin maps: the calls of tests/expert_cases.py on 1 x 65 536 and 65 536 x 1 through plan, fill and gather
+def _thin_calls():
+    import expert_cases as ec
+    side = ec.THIN_SIDE
+    return {'both_ends/1x65536': lambda: ec.both_ends_call(1, side), 'both_ends/65536x1': lambda: ec.both_ends_call(side, 1),
+            'two_ends/1x65536/N129': lambda: ec.two_ends_call(1, side, 129),
+            'two_ends/65536x1/N129': lambda: ec.two_ends_call(side, 1, 129),
+            # radius0 * 1.1^3 = 64 513.57 spans the gap of 64 513 cells and no more: the halves meet in ONE pair, and the
+            # largest degree is 512 = N / 2 (from radius0 = 5 the final radius of 68 903 makes every pair an edge: 1023)
+            'two_ends/1x65536/N1024': lambda: ec.two_ends_call(1, side, 1024, radius0=48470.0),
+            'spread/1x65536/N129': lambda: ec.spread_call(1, side, 129),
+            'spread/65536x1/N129': lambda: ec.spread_call(side, 1, 129),
+            'walk/1x65536/N129': lambda: ec.walk_call(1, side, 129), 'walk/65536x1/N129': lambda: ec.walk_call(side, 1, 129),
+            'status_bits/1x65536/N129': ec.thin_status_bits_call}
+
+
+THIN_CALLS = sorted(_thin_calls())
+THIN_SHORT_CAPS = ['two_ends/1x65536/N1024', 'two_ends/65536x1/N129']     # needs of 512 and of 128 (every pair an edge)
+
+
+def case_thin_map(lib, name, run=None, short=False):
+    """step_deg = the largest degree of the restatement's graph; the lists are those of its S (float32); the margins keep
+    their bytes; every other output is the dense call's; the gather into the standard block matches.  A flagged case of
+    the call has step_deg 0 and keeps its poison.  short: the fill runs with cap four below the need."""
+    import expert_cases as ec
+    call = _thin_calls()[name]()
+    wants = ec.call_wants(call)
+    bounds = np.cumsum([0] + [len(s) for s in call['schedules']])
+    h = HostCall(lib, call['grids'], call['goals'], call['schedules'], call['radius0'], run).plan()
+    built, deg = [], np.zeros(h.T, np.int64)
+    for c, want in enumerate(wants):
+        a, b = int(bounds[c]), int(bounds[c + 1])
+        if want is None:
+            assert h.out['status'][c] != 0 and (h.out['step_deg'][a:b] == 0).all()
+            continue
+        assert h.out['status'][c] == 0 and h.out['radius'][c] == want['radius'] and h.out['growth'][c] == want['growth']
+        deg[a:b] = (want['GSO'] != 0).sum(1).max(1)
+        built += [(a + t, c, t) for t in range(b - a)]
+    assert (h.out['step_deg'] == deg).all(), (h.out['step_deg'], deg)
+    need = max(4, roundup4(deg.max()))
+    if name == 'two_ends/1x65536/N1024':                # half the team each: a cap that is a multiple of 4 at N / 2
+        assert deg.max() == 512 and deg.min() == 512 and need == 512 and wants[0]['growth'] == 3
+        assert sorted((wants[0]['GSO'][0] != 0).sum(1).tolist()) == [511] * 1022 + [512] * 2
+    cap = need - 4 if short else need
+    assert cap >= 4
+    h.fill(cap)
+    for c, want in enumerate(wants):
+        a, b = int(bounds[c]), int(bounds[c + 1])
+        if want is None:
+            for k in ('cnt', 'idx', 'val'):
+                assert (h.out[k][a:b].view(np.uint8) == 0xFF).all(), k
+            assert np.isnan(h.out['obs'][a:b]).all() and np.isnan(h.out['target'][a:b]).all()
+            continue
+        check_lists(name, *h.lists(), lists_of_dense(want['GSO'].astype(np.float32)),
+                    graphs=[(a + t, t) for t in range(b - a)], cap=cap if short else None)
+        assert np.array_equal(h.out['obs'][a:b], want['input']) and np.array_equal(h.out['target'][a:b], want['target'])
+    assert h.margins_intact()
+    if short:
+        assert (h.out['cnt'] > cap).any() and h.out['cnt'].max() == deg.max()
+        return
+    dense = h.dense()
+    assert_plan_outputs_equal_dense(h, dense)
+    steps = [g for g, _, _ in built]
+    index = steps[::-1][:3]                              # (a standard block at N = 1024 is 6 MB per graph)
+    raw, block = host_gather(lib, h.lists(), h.T, h.cap, index, h.N, run=run, buffers=list(h.raw.values()))
+    assert margins_intact(raw, block)
+    S32 = np.stack([wants[c]['GSO'][t] for g, c, t in built[::-1][:3]]).astype(np.float32)
+    assert S32.tobytes() == dense['S'][index].tobytes()
+    check_lists('gather ' + name, *block_views(block, len(index), h.N), lists_of_dense(S32))
+
+
 # -- gnnpp_team_lists_gather
 def gather_pool(lib, run=None):
     """The capped set of the 5 steps of a 130-agent case and its dense S."""

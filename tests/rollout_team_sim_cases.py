@@ -255,6 +255,17 @@ def _check_grown(case, tr):
         assert steps > 100 and r > THIN_SIDE - 1 and (r / 1.1) ** 2 > 2 ** 31, (steps, r)   # the threshold passed 2^31
 
 
+HUGE_RADIUS = 1e10
+
+
+def _check_all_pairs(case, tr):
+    """The oracle's answer at a radius beyond every distance: every pair an edge, the radius as it was given."""
+    _check_wrapping_inputs(case)
+    N = case['starts'].shape[1]
+    assert ((tr['S'][0, 0] != 0) == ~np.eye(N, dtype=bool)).all() and tr['connected'][0, 0] == 1, case['name']
+    assert tr['radius'][0, 0] == HUGE_RADIUS, case['name']
+
+
 @functools.lru_cache(None)
 def thin_cases():
     cases = []
@@ -271,6 +282,10 @@ def thin_cases():
                 cases.append(_thin_case('two_ends', H, W, ends, 2.0, 0, _check_ends, seed + 2))
         for N in (2, 129):
             cases.append(_thin_case('grow', H, W, _spread(N), 2.0, 1, _check_grown, 1690 + 10 * N + o))
+    # a radius whose square (1e20) is beyond a 64-bit integer, grow = 0: dist2_bound decides it on the double.  One-wave
+    # (128) and team (129) kernels; lists_cases() below sends both through the neighbour-list call as well.
+    for N in (128, 129):
+        cases.append(_thin_case('radius_1e10', 1, THIN_SIDE, _spread(N), HUGE_RADIUS, 0, _check_all_pairs, 1700 + N))
     return cases
 
 
@@ -288,7 +303,7 @@ def lists_cases():
     for c in cases:
         if c['name'].endswith('/spread') or c['name'].endswith('/two_ends'):
             c['connected'] = [0]
-        if c['name'].endswith('/grow'):
+        if c['name'].endswith('/grow') or c['name'].endswith('/radius_1e10'):
             c['connected'] = [1]
     cases.append(dict(name='lists/team_sim/chain1024', pos=lc._chain(1024, 3), radius=3.5, grow=0, connected=[1]))
     cases.append(dict(name='lists/team_sim/chain1024/broken_at_700', pos=_broken_chain(), radius=3.5, grow=0, connected=[0]))

@@ -180,6 +180,72 @@ def test_radii_that_share_an_integer_bound(lib):
     assert (out['step_info'] & 0xffff).tolist() == [12, 12, 8, 8]
 
 
+def run_case(lib, case, **kw):
+    out = call(lib, case['grids'], case['goals'], case['schedules'], radius0=case['radius0'], fp64=case['fp64'], **kw)
+    ec.assert_call_outputs(dict(out, S64=out['S64'] if case['fp64'] else None), case, np.nan)
+    return out
+
+
+@pytest.mark.parametrize('N', [2, 128])
+@pytest.mark.parametrize('H,W', ec.thin_shapes(ec.ONE_WAVE_SIDE))
+def test_map_limit_of_16384_cells_a_side(lib, H, W, N):
+    """A walk with a map per case and the team on the two ends of the strip, on the longest map the launcher takes."""
+    case = ec.one_wave_limit_call(H, W, N)
+    out = run_case(lib, case)
+    want = ec.call_wants(case)[2]
+    assert (out['growth'][2], out['radius'][2]) == ec.growth_to_span(5.0, ec.ONE_WAVE_SIDE - N + 1) == \
+        (want['growth'], want['radius'])
+
+
+@pytest.mark.parametrize('H,W', ec.thin_shapes(ec.ONE_WAVE_SIDE + 1))
+def test_one_cell_beyond_the_map_limit_is_refused(lib, H, W):
+    case = ec.beyond_one_wave_limit_call(H, W)
+    out = call(lib, case['grids'], case['goals'], case['schedules'], expect=ERR_UNSUPPORTED)
+    assert all(np.isnan(out[k]).all() for k in ('obs', 'S', 'S64', 'target', 'radius'))
+    assert (out['status'] == -1).all() and (out['growth'] == -1).all() and (out['step_info'] == -1).all()
+
+
+def test_python_side_names_the_call_that_refused_the_map(lib, monkeypatch):
+    """expert.enqueue_schedule_samples, which samples_from_schedules goes through, on the emulated library with host
+    tensors: the project's error, naming the call and "not supported", and nothing else."""
+    import torch
+    from gnn_pathplanning_amd import _native, expert
+    case = ec.beyond_one_wave_limit_call(1, ec.ONE_WAVE_SIDE + 1)
+    monkeypatch.setattr(_native, 'lib', lambda: lib)
+    monkeypatch.setattr(_native, 'require_gpu', lambda *t: torch.device('cpu'))
+    monkeypatch.setattr(_native, 'stream_ptr', lambda dev: None)
+    monkeypatch.setattr(_native.device_guard, '__enter__', lambda self: self)
+
+    def enqueue(case):
+        bounds = np.cumsum([0] + [len(s) for s in case['schedules']]).tolist()
+        (C, N), T = case['goals'].shape[:2], bounds[-1]
+        out = expert.ScheduleSamples(
+            input=torch.full((T, N, 3, 11, 11), -7.0), GSO=torch.full((T, N, N), -7.0), GSO64=None,
+            target=torch.full((T, N, 5), -7.0), radius=torch.full((C,), -7.0, dtype=torch.float64),
+            growth=torch.full((C,), -7, dtype=torch.int32), status=torch.full((C,), -7, dtype=torch.int32),
+            step_growth=torch.full((T,), -7, dtype=torch.int32))
+        expert.enqueue_schedule_samples(torch.from_numpy(case['grids']), torch.from_numpy(case['goals']),
+                                        torch.from_numpy(np.concatenate(case['schedules'])),
+                                        torch.tensor(bounds, dtype=torch.int32), out)
+        return out
+
+    with pytest.raises(_native.GnnppError, match=r'^gnnpp_schedule_samples failed: .*not supported.*\(code -2\)$'):
+        enqueue(case)
+    limit = ec.one_wave_limit_call(1, ec.ONE_WAVE_SIDE, 2)              # one cell shorter: the same path builds it
+    out = enqueue(limit)
+    assert out.status.tolist() == [0, 0, 0] and out.growth.tolist() == [w['growth'] for w in ec.call_wants(limit)]
+
+
+@pytest.mark.parametrize('radius0', ec.HUGE_RADII, ids=repr)
+def test_radius_beyond_every_distance(lib, radius0):
+    """Three agents on 1 x 40: status 0, growth 0, radius = radius0 bit for bit, every pair an edge."""
+    tiny, _ = ec.huge_radius_calls(radius0)
+    out = run_case(lib, tiny)
+    assert out['status'][0] == 0 and out['growth'][0] == 0 and (out['step_info'] == 0).all()
+    assert out['radius'].tobytes() == np.array([radius0]).tobytes()
+    assert ((out['S64'] != 0) == ~np.eye(3, dtype=bool)).all() and ((out['S'] != 0) == ~np.eye(3, dtype=bool)).all()
+
+
 def test_teams_at_the_second_agent_per_lane(lib):
     for case in ec.lane_boundary_calls():
         out = call(lib, case['grids'], case['goals'], case['schedules'])

@@ -213,6 +213,110 @@ def test_status_bits_flag_only_their_case(lib):
             assert np.isnan(out[k][c * T:(c + 1) * T]).all(), k
 
 
+def run_case(lib, case, untouched=('obs', 'S'), **kw):
+    """A call of tests/expert_cases.py on poisoned host arrays, against the restatement."""
+    out = call(lib, case['grids'], case['goals'], case['schedules'], radius0=case['radius0'], fp64=case['fp64'], **kw)
+    ec.assert_call_outputs(dict(out, S64=out['S64'] if case['fp64'] else None), case, np.nan, untouched)
+    if not case['fp64'] and kw.get('team', True):
+        assert np.isnan(out['S64']).all()
+    return out
+
+
+def per_step_growths(case, c):
+    return [ec.schedule_gso(case['schedules'][c][t:t + 1], case['radius0'])[2] for t in range(len(case['schedules'][c]))]
+
+
+# ---- thin maps: 1 x 65 536 and 65 536 x 1 ---------------------------------------------------------------------------
+@pytest.mark.parametrize('H,W', ec.thin_shapes(ec.THIN_SIDE))
+def test_thin_map_two_agents_on_both_ends(lib, H, W):
+    """100 growths; the bounds pass 2^31 and end in the 0xffffffff clamp."""
+    out = run_case(lib, ec.both_ends_call(H, W))
+    assert out['growth'][0] == 100 and out['radius'][0] == 68903.06169911187
+    assert (out['step_info'] & 0xffff).tolist() == [100, 100]
+
+
+@pytest.mark.parametrize('H,W', ec.thin_shapes(ec.THIN_SIDE))
+def test_thin_map_two_halves_on_the_ends(lib, H, W):
+    """129 agents: the halves meet only at the final growth, at every step on its own."""
+    case = ec.two_ends_call(H, W, 129)
+    out = run_case(lib, case)
+    assert out['step_info'].tolist() == per_step_growths(case, 0) == [ec.call_wants(case)[0]['growth']] * 2
+
+
+@pytest.mark.parametrize('H,W,fp64', [(1, ec.THIN_SIDE, True), (ec.THIN_SIDE, 1, False)])
+def test_thin_map_two_halves_on_the_ends_full_workgroup(lib, H, W, fp64):
+    """1024 agents (the full workgroup), one call with and one without the fp64 copy.  About 6 s each on the host, nearly
+    all of it the restatement's 100 radius trips over a 1024 x 1024 distance matrix; the emulated call takes 0.3 s."""
+    case = ec.two_ends_call(H, W, 1024, fp64)
+    out = run_case(lib, case)
+    assert (out['step_info'] & 0xffff).tolist() == [ec.call_wants(case)[0]['growth']] * 2
+
+
+@pytest.mark.parametrize('H,W', ec.thin_shapes(ec.THIN_SIDE))
+def test_thin_map_spread_and_unaligned_graph_outputs(lib, H, W):
+    """129 agents 512 cells apart; S / S64 off the 16-byte boundary give the same bytes."""
+    case = ec.spread_call(H, W, 129)
+    out = run_case(lib, case)
+    assert out['step_info'].tolist() == per_step_growths(case, 0)
+    assert_same_bytes(out, run_case(lib, case, misalign=True))
+
+
+@pytest.mark.parametrize('H,W', ec.thin_shapes(ec.THIN_SIDE))
+def test_thin_map_walk_with_a_map_per_case(lib, H, W):
+    run_case(lib, ec.walk_call(H, W, 129))
+    run_case(lib, ec.walk_call(H, W, 129, fp64=False))
+
+
+def test_thin_map_status_bits_flag_only_their_case(lib):
+    case = ec.thin_status_bits_call()
+    out = run_case(lib, case, untouched=('obs', 'S', 'S64', 'target'))
+    assert out['status'][[0, 4]].tolist() == [0, 0] and out['status'][3] == BAD_MOVE
+    assert out['status'][1] & BAD_STATE and out['status'][2] & BAD_STATE
+    assert out['step_info'][3 + 1] & 0xffff == 0 and out['step_info'][6] & 0xffff == 0   # no search with a state off the map
+    alone = call(lib, case['grids'], case['goals'][:1], case['schedules'][:1])
+    T = 3
+    for c in (0, 4):                                    # the legal cases: the bytes of the case run alone
+        for k in ('obs', 'S', 'S64', 'target', 'step_info'):
+            assert out[k][c * T:(c + 1) * T].tobytes() == alone[k].tobytes(), k
+        assert out['radius'][c] == alone['radius'][0] and out['growth'][c] == alone['growth'][0]
+    for c in (1, 2, 3):                                 # a flagged case is not built
+        for k in ('obs', 'S', 'S64', 'target'):
+            assert np.isnan(out[k][c * T:(c + 1) * T]).all(), k
+
+
+# ---- the one-wave call's map limit: a side of 16 384 ----------------------------------------------------------------
+@pytest.mark.parametrize('N', [2, 128])
+@pytest.mark.parametrize('H,W', ec.thin_shapes(ec.ONE_WAVE_SIDE))
+def test_one_wave_map_limit_same_bytes_as_team_call(lib, H, W, N):
+    case = ec.one_wave_limit_call(H, W, N)
+    assert_same_bytes(run_case(lib, case, team=False), run_case(lib, case))
+
+
+@pytest.mark.parametrize('H,W', ec.thin_shapes(ec.ONE_WAVE_SIDE + 1))
+def test_one_cell_beyond_the_one_wave_map_limit(lib, H, W):
+    """The one-wave call refuses the map and writes nothing; the team call builds it."""
+    case = ec.beyond_one_wave_limit_call(H, W)
+    out = call(lib, case['grids'], case['goals'], case['schedules'], expect=ERR_UNSUPPORTED, team=False)
+    assert all(np.isnan(out[k]).all() for k in ('obs', 'S', 'S64', 'target', 'radius'))
+    assert (out['status'] == -1).all() and (out['growth'] == -1).all() and (out['step_info'] == -1).all()
+    run_case(lib, case)
+
+
+# ---- radii beyond every distance ------------------------------------------------------------------------------------
+@pytest.mark.parametrize('radius0', ec.HUGE_RADII, ids=repr)
+def test_radius_beyond_every_distance(lib, radius0):
+    """Status 0, growth 0, radius = radius0 bit for bit, every pair an edge.  Before dist2_bound decided r >= 65536 on the
+    double, the emulation's (long long)ceil(r * r) gave status 4, growth 65535, radius inf from 3.1e9 on."""
+    tiny, thin = ec.huge_radius_calls(radius0)
+    for case in (tiny, thin):
+        out = run_case(lib, case)
+        N = case['goals'].shape[1]
+        assert out['status'][0] == 0 and out['growth'][0] == 0 and (out['step_info'] == 0).all()
+        assert out['radius'].tobytes() == np.array([radius0]).tobytes()
+        assert ((out['S'] != 0) == ~np.eye(N, dtype=bool)).all() and ((out['S64'] != 0) == ~np.eye(N, dtype=bool)).all()
+    assert_same_bytes(run_case(lib, tiny, team=False), run_case(lib, tiny))
+
+
 def test_argument_errors(lib):
     m, g = ec.load_golden()[7]
     ok = dict(grids=g['grid'], goals=g['goal'][None], schedules=[g['schedule']])

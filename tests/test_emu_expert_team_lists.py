@@ -94,6 +94,16 @@ def test_cap_four_below_the_need(lib, N, side, radius0):
     lc.case_cap_four_below_the_need(lib, N, side, radius0)
 
 
+@pytest.mark.parametrize('name', lc.THIN_CALLS)
+def test_thin_map(lib, name):
+    lc.case_thin_map(lib, name)
+
+
+@pytest.mark.parametrize('name', lc.THIN_SHORT_CAPS)
+def test_thin_map_cap_four_below_the_need(lib, name):
+    lc.case_thin_map(lib, name, short=True)
+
+
 # ---- gnnpp_team_lists_gather ------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def pool(lib):

@@ -52,6 +52,16 @@ def test_cap_four_below_the_need(lib, run, N, side, radius0):
     lc.case_cap_four_below_the_need(lib, N, side, radius0, run)
 
 
+@pytest.mark.parametrize('name', lc.THIN_CALLS)
+def test_thin_map(lib, run, name):
+    lc.case_thin_map(lib, name, run)
+
+
+@pytest.mark.parametrize('name', lc.THIN_SHORT_CAPS)
+def test_thin_map_cap_four_below_the_need(lib, run, name):
+    lc.case_thin_map(lib, name, run, short=True)
+
+
 @pytest.fixture(scope='module')
 def pool(lib, run):
     return lc.gather_pool(lib, run)
