@@ -69,6 +69,9 @@ MAPF_AUDIT_STATE, MAPF_AUDIT_VERTEX, MAPF_AUDIT_MOVE, MAPF_AUDIT_SWAP = 1, 2, 4,
 MAPF_AUDIT_BAD_START, MAPF_AUDIT_NOT_AT_GOAL, MAPF_AUDIT_SKIPPED = 16, 32, 64
 # csrc/gnnpp_measure.h: keys that exist in the -DGNNPP_MEASURE build only (libgnnpp.so answers GNNPP_ERR_ARG)
 TUNE_FILTER_ABLATE, TUNE_ENCODER_STOP = 3, 4
+# csrc/encoder_kernel_b3.hip: 1 (default) = a team of 10 agents runs the packed policy kernel's compile-time-N form, 0 = the
+# run-time-N form like every other team size (same logits to the bit); a key of the tests and the A/B tools, in every build
+TUNE_POLICY_CP_TEAM = 21
 PRECISIONS = {'fp32': PREC_FP32, 'fp32_mfma': PREC_FP32_MFMA, 'split_f16': PREC_SPLIT_F16}
 
 
@@ -145,9 +148,13 @@ def build(force=False, verbose=False, measure=False):
 # filter items per tap ...
 RING_KERNELS = (('encoder_kernel_b3ILb0ELi3ELb0E', 294, 0), ('encoder_kernel_b3ILb1ELi2ELb0E', 342, 32),
                 ('encoder_kernel_b3ILb1ELi3ELb0E', 366, 32), ('encoder_kernel_b3ILb1ELi4ELb0E', 390, 32),
-                # ... and its column-packed form for teams of <= 12 agents (third template argument)
-                ('encoder_kernel_b3ILb1ELi2ELb1E', 342, 32), ('encoder_kernel_b3ILb1ELi3ELb1E', 366, 32),
-                ('encoder_kernel_b3ILb1ELi4ELb1E', 390, 32), ('encoder_kernel_b3ILb0ELi3ELb1E', 294, 0))
+                # ... and its column-packed form for teams of <= 12 agents (third template argument; fourth = 0: run-time N)
+                ('encoder_kernel_b3ILb1ELi2ELb1ELi0E', 342, 32), ('encoder_kernel_b3ILb1ELi3ELb1ELi0E', 366, 32),
+                ('encoder_kernel_b3ILb1ELi4ELb1ELi0E', 390, 32), ('encoder_kernel_b3ILb0ELi3ELb1ELi0E', 294, 0))
+# ... and the packed policy kernel with the team size as a constant (fourth template argument = 10): its first packed layer
+# drops the units that hold nothing but zeros, the ring sees the same items in the same order.  MUST PASS as well.
+RING_KERNELS_TEAM = (('encoder_kernel_b3ILb1ELi2ELb1ELi10E', 342, 32), ('encoder_kernel_b3ILb1ELi3ELb1ELi10E', 366, 32),
+                     ('encoder_kernel_b3ILb1ELi4ELb1ELi10E', 390, 32))
 # OPT-IN precision 'split_f16' (16 more fragments per tap): a violation here disables THAT precision
 # (H2_UNSAFE_MARK, precision_code) instead of failing the build of the default path
 RING_KERNELS_OPTIONAL = (('encoder_kernel_h2ILb0ELi3E', 196, 0), ('encoder_kernel_h2ILb1ELi2E', 228, 32),
@@ -165,7 +172,7 @@ def check_ring_isa(isa_path, verbose=False):
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     optional_errors = []
-    for kern, items, scratch in RING_KERNELS + RING_KERNELS_OPTIONAL:
+    for kern, items, scratch in RING_KERNELS + RING_KERNELS_TEAM + RING_KERNELS_OPTIONAL:
         errors, stats, meta = mod.check(isa_path, kern, scratch)
         ok = (not errors and stats['loads'] == items and stats['takes'] == items
               and meta.get('NumVgprs') == 256 and meta.get('Occupancy') == 2)

@@ -302,7 +302,8 @@ __device__ __forceinline__ void b3_conv_preload(const WStreamB& ws, v4f (&ring)[
 // With agents on the MFMA's 16 columns a 10-agent graph uses 10 / 16 of every MFMA.  For the two layers that hold 57 %
 // of the kernel's matrix work the columns are (agent, position) PAIRS instead:
 //   L1 (32 -> 32 @ 5x5)  column c = pos * N + n, c < 25 N: ceil(25 N / 16) tiles of 16 consecutive columns (N = 10: 16
-//        tiles x 9 taps instead of 25 position tiles x 6.76 reachable taps = 144 instead of 169 tile-taps), a wave takes
+//        tiles x 9 taps instead of 25 position tiles x 6.76 reachable taps = 144 instead of 169 tile-taps -- 123 where the team
+//        size is a compile-time constant and the tile-taps that hold only zeros are dropped: kCpTeamFixed below), a wave takes
 //        tiles wave, wave + 4, ..: 4 / 4 / 4 / 4 instead of 7 / 6 / 6 / 6 positions;
 //   L2 (32 -> 64 @ 5x5, the 4x4 the pool reads)  one tile PER AGENT whose 16 columns are the 16 output positions, the four
 //        positions of a pool window in four adjacent lanes (the 2x2 max is two quad_perm DPP steps): N tiles x 9 taps
@@ -341,6 +342,98 @@ __device__ __forceinline__ CpGeom cp_geom(int N) {
     g.l1in = kB3Region - (g.T1 + 1) * kCpRow;                      // (+ 1: the row of zeros behind the data rows)
     g.rcpN = (unsigned)(65536.f / (float)N) + 1u;
     return g;
+}
+// ---- a COMPILE-TIME team size (template argument NFIX; 0 = the run-time pt.N above) ---------------------------------------
+// Which L1 units (tap, tile) hold nothing but zeros is a fact of N: with c = pos * N + n a tile of 16 consecutive columns
+// can lie inside ONE image row (N = 10: row y = 0 is columns 0 .. 49 = tiles 0, 1, 2 and most of 3), and a tap with dy = -1
+// then redirects every lane of the tile to the zero row -- twelve MFMAs that add exact zeros.  As a run-time test the skip
+// costs more than it saves (every unit in its own basic block: lgkmcnt(0) before every MFMA group, see cp_layer1_main), so
+// the launcher picks an instantiation whose N is a constant for the team size that matters (10: BASELINE configs 1, 2, 4
+// and the reference's published model) and the units are dropped at compile time.  cp_geom(NFIX) is then a set of
+// constants too: its divisions, the tap shifts of cp_l1_addr and the tile counts of both packed layers fold.
+constexpr int kCpTeamFixed = 10;
+// unit (tap, tile) of a team of N: every EXISTING column of the tile (c < 25 N) leaves the image under this tap -- the rule
+// cp_layer1 states per lane as `fl & tmask` (N == 0, the run-time form, skips nothing)
+__host__ __device__ constexpr bool cp_l1_unit_empty_n(int N, int tap, int tile) {
+    if (N == 0) return false;
+    const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+    for (int c = 16 * tile; c < 16 * tile + 16 && c < 25 * N; ++c) {
+        const int pos = c / N, y = pos / 5, x = pos % 5;
+        if (!((dy < 0 && y == 0) || (dy > 0 && y == 4) || (dx < 0 && x == 0) || (dx > 0 && x == 4))) return false;
+    }
+    return true;
+}
+template <int NFIX>
+__host__ __device__ constexpr bool cp_l1_unit_empty(int tap, int tile) { return cp_l1_unit_empty_n(NFIX, tap, tile); }
+__host__ __device__ constexpr int cp_l1_empty_units(int N) {
+    int cnt = 0;
+    for (int tap = 0; tap < 9; ++tap)
+        for (int tile = 0; tile < (25 * N + 15) / 16; ++tile) cnt += cp_l1_unit_empty_n(N, tap, tile) ? 1 : 0;
+    return cnt;
+}
+// units that are empty through dy alone (a tile inside image row 0 or 4)
+__host__ __device__ constexpr int cp_l1_empty_row_units(int N) {
+    int cnt = 0;
+    for (int tap = 0; tap < 9; ++tap)
+        for (int tile = 0; tap % 3 == 1 && tile < (25 * N + 15) / 16; ++tile)
+            cnt += 3 * (tap / 3 != 1 && cp_l1_unit_empty_n(N, tap, tile) ? 1 : 0);
+    return cnt;
+}
+// N = 10: 18 units through dy -- tiles 0 - 2 (columns 0 .. 47 of row 0's 0 .. 49) under the three dy = -1 taps, tiles 13 - 15
+// (208 .. 249 of row 4's 200 .. 249) under the three dy = +1 taps -- and three more through dx: tile 15's existing columns
+// 240 .. 249 are all position (4, 4), empty under (-1, +1) and (0, +1) too, and tile 12 (columns 192 .. 207 = positions
+// (3, 4) and (4, 0)) is empty under (+1, +1).  252 of L1's 1 728 MFMAs per graph; per wave 32 / 30 / 30 / 31 units of 36.
+static_assert(cp_l1_empty_row_units(kCpTeamFixed) == 18 && cp_l1_empty_units(kCpTeamFixed) == 21,
+              "N = 10: 18 units empty by rows, tile 15 under two dx = +1 taps, tile 12 under (+1, +1)");
+// tiles of wave w (w, w + 4, ..) of a team of N
+__host__ __device__ constexpr int cp_l1_wave_tiles(int N, int w) {
+    const int na = ((25 * N + 15) / 16 - w + 3) >> 2;
+    return na < 0 ? 0 : na > kCpL1Tiles ? kCpL1Tiles : na;
+}
+// The unit sequence of one wave: the live units in (tap, tile) order.  ord = a unit's place in that sequence (-1: skipped),
+// first_tap[i] = the tap that starts tile i's accumulators (first_step_of_slot of the unpacked layers), last_tile[tap] =
+// the tile whose unit closes the tap's step (it carries the ring refills).  W < 0: every unit of NA tiles (run-time N).
+template <int NA>
+struct CpL1Sched {
+    int n;
+    int ord[9][NA > 0 ? NA : 1];
+    int tap[9 * NA + 1], tile[9 * NA + 1];
+    int first_tap[NA > 0 ? NA : 1], last_tile[9], live_tiles[9];
+};
+template <int NFIX, int W, int NA>
+__host__ __device__ constexpr CpL1Sched<NA> cp_l1_sched() {
+    CpL1Sched<NA> s{};
+    for (int i = 0; i < NA; ++i) s.first_tap[i] = -1;
+    for (int tap = 0; tap < 9; ++tap) {
+        s.last_tile[tap] = -1;
+        for (int i = 0; i < NA; ++i) {
+            const bool live = W < 0 || !cp_l1_unit_empty_n(NFIX, tap, W + 4 * i);
+            s.ord[tap][i] = live ? s.n : -1;
+            if (!live) continue;
+            s.tap[s.n] = tap;
+            s.tile[s.n] = i;
+            ++s.n;
+            if (s.first_tap[i] < 0) s.first_tap[i] = tap;
+            s.last_tile[tap] = i;
+            ++s.live_tiles[tap];
+        }
+    }
+    return s;
+}
+template <int NFIX, int W, int NA>
+struct CpL1S {
+    static constexpr CpL1Sched<NA> v = cp_l1_sched<NFIX, W, NA>();
+};
+// every tap keeps >= 2 units on every wave (a step's refills always have a unit to ride on, and two consecutive units
+// never share their accumulators), every tile keeps a tap that starts it
+template <int NFIX, int W, int NA>
+__host__ __device__ constexpr bool cp_l1_sched_ok() {
+    constexpr CpL1Sched<NA> s = cp_l1_sched<NFIX, W, NA>();
+    for (int tap = 0; tap < 9; ++tap)
+        if (s.live_tiles[tap] < 2) return false;
+    for (int i = 0; i < NA; ++i)
+        if (s.first_tap[i] < 0) return false;
+    return true;
 }
 // byte offset of cell (y, x) of agent n inside a (plane, q) block of the L2-input layout
 __device__ __forceinline__ int cp_l2in_cell(int y, int x, int n) {
@@ -748,15 +841,22 @@ __device__ __forceinline__ void cp_l1_load(const char* smem, int addr, v4f (&B)[
 #pragma unroll
     for (int p = 0; p < 3; ++p) B[p] = *reinterpret_cast<const v4f*>(smem + addr + p * kB3Frag);
 }
-template <int END, int NA>
+// NFIX != 0 (a compile-time team size, W = this wave): the units cp_l1_unit_empty<NFIX> names are not part of the sequence
+// -- no address, no plane reads, no MFMAs.  The ring sees the same steps: a tap's wait stands in front of its first LIVE
+// unit and its refills ride on its last live one (cp_l1_sched_ok: there always are two), and a tile whose dy = -1 taps
+// are dropped starts its accumulators at its first live tap.
+template <int END, int NA, int NFIX = 0, int W = -1>
 __device__ __forceinline__ void cp_layer1_main(const WStreamB& ws, v4f (&ring)[kRingH], const char* smem, const CpGeom& g,
                                                const CpL1Lane& ln, int wave, v4f (&acc)[kCpL1Tiles][2]) {
-    constexpr int NU = 9 * NA;                                      // units of this wave
+    using S = CpL1S<NFIX, W, NA>;
+    static_assert((NFIX == 0) == (W < 0), "a fixed team size names the wave, a run-time one does not");
+    static_assert(NFIX == 0 || (NA >= 2 && cp_l1_sched_ok<NFIX, W, NA>()), "the skip keeps the direct form's steps whole");
+    constexpr int NU = S::v.n;                                      // units of this wave (9 NA, less the empty ones)
     v4f Bb[2][3];
     if constexpr (NA > 0) {
         int addr[NU];                                               // unit u = (tap, tile): this lane's cell, tile row included
         [&]<int... U>(std::integer_sequence<int, U...>) {
-            ((addr[U] = cp_l1_addr<U / NA, U % NA>(g, ln, wave), cp_pin(addr[U])), ...);
+            ((addr[U] = cp_l1_addr<S::v.tap[U], S::v.tile[U]>(g, ln, wave), cp_pin(addr[U])), ...);
         }(std::make_integer_sequence<int, NU>{});
         __builtin_amdgcn_sched_barrier(0);
         GNNPP_STAMP(blockIdx.x, 7, wave == 0 && ln.j == 0 && ln.q == 0);
@@ -768,12 +868,15 @@ __device__ __forceinline__ void cp_layer1_main(const WStreamB& ws, v4f (&ring)[k
                 constexpr int tap = decltype(itc)::value, base = decltype(basec)::value;
                 constexpr bool ordered = tap >= 7;
                 auto unit = [&](auto ic) {
-                    constexpr int i = decltype(ic)::value, u = tap * NA + i;
-                    cp_unit_direct<base, tap == 0, i == NA - 1, ordered>(ring, Bb[u & 1], acc[i][0], acc[i][1],
-                        [&](int p) {
-                            if constexpr (u + 1 < NU)
-                                Bb[(u + 1) & 1][p] = *reinterpret_cast<const v4f*>(smem + addr[u + 1] + p * kB3Frag);
-                        }, refill);
+                    constexpr int i = decltype(ic)::value, u = S::v.ord[tap][i];
+                    if constexpr (u >= 0) {
+                        cp_unit_direct<base, tap == S::v.first_tap[i], i == S::v.last_tile[tap], ordered>(
+                            ring, Bb[u & 1], acc[i][0], acc[i][1],
+                            [&](int p) {
+                                if constexpr (u + 1 < NU)
+                                    Bb[(u + 1) & 1][p] = *reinterpret_cast<const v4f*>(smem + addr[u + 1] + p * kB3Frag);
+                            }, refill);
+                    }
                 };
                 [&]<int... I>(std::integer_sequence<int, I...>) { (unit(std::integral_constant<int, I>{}), ...); }(
                     std::make_integer_sequence<int, NA>{});
@@ -803,7 +906,7 @@ __device__ __forceinline__ void cp_layer1_main(const WStreamB& ws, v4f (&ring)[k
     }
 }
 
-template <int END>
+template <int END, int NFIX = 0>
 __device__ __forceinline__ void cp_layer1(const WStreamB& ws, v4f (&ring)[kRingH], char* smem, const float* sstab,
                                           const CpGeom& g, int wave, int lane, int tid) {
     constexpr int NT = kCpL1Tiles;
@@ -830,13 +933,27 @@ __device__ __forceinline__ void cp_layer1(const WStreamB& ws, v4f (&ring)[kRingH
 #pragma unroll
     for (int i = 0; i < NT; ++i) acc[i][0] = acc[i][1] = vzero();
     static_assert(NT == 5, "one case per tile count");
-    switch (na) {                                                   // (wave-uniform: a scalar branch)
-        case 0: cp_layer1_main<END, 0>(ws, ring, smem, g, ln, wave, acc); break;
-        case 1: cp_layer1_main<END, 1>(ws, ring, smem, g, ln, wave, acc); break;
-        case 2: cp_layer1_main<END, 2>(ws, ring, smem, g, ln, wave, acc); break;
-        case 3: cp_layer1_main<END, 3>(ws, ring, smem, g, ln, wave, acc); break;
-        case 4: cp_layer1_main<END, 4>(ws, ring, smem, g, ln, wave, acc); break;
-        default: cp_layer1_main<END, 5>(ws, ring, smem, g, ln, wave, acc); break;
+    if constexpr (NFIX == 0) {
+        switch (na) {                                               // (wave-uniform: a scalar branch)
+            case 0: cp_layer1_main<END, 0>(ws, ring, smem, g, ln, wave, acc); break;
+            case 1: cp_layer1_main<END, 1>(ws, ring, smem, g, ln, wave, acc); break;
+            case 2: cp_layer1_main<END, 2>(ws, ring, smem, g, ln, wave, acc); break;
+            case 3: cp_layer1_main<END, 3>(ws, ring, smem, g, ln, wave, acc); break;
+            case 4: cp_layer1_main<END, 4>(ws, ring, smem, g, ln, wave, acc); break;
+            default: cp_layer1_main<END, 5>(ws, ring, smem, g, ln, wave, acc); break;
+        }
+    } else {
+        // one copy per WAVE instead of one per tile count: which units are empty depends on the wave's tiles
+        auto layer = [&](auto wc) {
+            constexpr int w = decltype(wc)::value;
+            cp_layer1_main<END, cp_l1_wave_tiles(NFIX, w), NFIX, w>(ws, ring, smem, g, ln, w, acc);
+        };
+        switch (wave) {
+            case 0: layer(std::integral_constant<int, 0>{}); break;
+            case 1: layer(std::integral_constant<int, 1>{}); break;
+            case 2: layer(std::integral_constant<int, 2>{}); break;
+            default: layer(std::integral_constant<int, 3>{}); break;
+        }
     }
     GNNPP_STAMP(blockIdx.x, 8, tid == 0);
     __syncthreads();                                               // everyone is done reading L0's output
@@ -1023,7 +1140,7 @@ __device__ __forceinline__ void cp_layer2(const WStreamB& ws, v4f (&ring)[kRingH
     }
 }
 
-template <bool FUSED, int KT, bool CP = false>
+template <bool FUSED, int KT, bool CP = false, int NFIX = 0>
 __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kernel_b3(const float* __restrict__ obs,
                                                                  const float* __restrict__ pk,
                                                                  float* __restrict__ feat, int M, int stop_flags,
@@ -1050,7 +1167,9 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
     const int tile_agents = (FUSED || CP) ? pt.N : kTileAgents;
     const int agent0 = blockIdx.x * tile_agents;
     const int n_agents = FUSED ? pt.N : min(tile_agents, M - agent0);   // (>= 1: the grid is ceil(M / tile))
-    const CpGeom geom = cp_geom(CP ? n_agents : kTileAgents);        // (CP only; folded away otherwise)
+    static_assert(NFIX == 0 || (FUSED && CP && NFIX <= kCpMaxAgents), "a fixed team size is a form of the packed policy kernel");
+    // (CP only; folded away otherwise.  NFIX: the launcher guarantees pt.N == NFIX, and every field is a constant)
+    const CpGeom geom = cp_geom(NFIX != 0 ? NFIX : CP ? n_agents : kTileAgents);
     GNNPP_STAMP(blockIdx.x, 11, tid == 0);
 
     WStreamB ws;
@@ -1288,7 +1407,7 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
 
     // ---- L1: 32 -> 32 @ 5x5, in place; wave = its positions x both channel tiles ---------------------
     if constexpr (CP) {
-        cp_layer1<END>(ws, ring, gnnpp_smem, sstab, geom, wave, lane, tid);
+        cp_layer1<END, NFIX>(ws, ring, gnnpp_smem, sstab, geom, wave, lane, tid);
     } else {
         v4f acc[7][2];                                    // first touched by a zero-source MFMA (b3_mfma_chunk)
         constexpr int CH1 = 2;                            // slots per chunk: 6 LDS reads in flight beside <= 24 MFMAs
@@ -1612,7 +1731,12 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
 }
 
 std::atomic<int> g_policy_column_packing{1};   // GNNPP_TUNE_POLICY_CP: 0 = agents on the MFMA columns for every team size
-std::atomic<int> g_encoder_one_plane{1};       // GNNPP_TUNE_ENCODER_ONE_PLANE: 0 = the three-plane word path for every tile
+// 1 (default): a team of kCpTeamFixed agents runs the instantiation whose team size is a constant; 0: the run-time-N
+// packed form, as every other team size (same logits to the bit: the dropped units add exact zeros).  A key of the
+// tests and the A/B tools, stated here and in _native.py rather than in include/gnnpp.h, like gnnpp_measure.h's.
+#define GNNPP_TUNE_POLICY_CP_TEAM 21
+std::atomic<int> g_policy_cp_team{1};
+std::atomic<int> g_encoder_one_plane{1};      // GNNPP_TUNE_ENCODER_ONE_PLANE: 0 = the three-plane word path for every tile
 static int b3_plane_flag() { return g_encoder_one_plane.load(std::memory_order_relaxed) ? 0 : kB3ForcePlanes; }
 std::atomic<int> g_encoder_cp_tile{0};   // GNNPP_TUNE_ENCODER_CP_TILE: 0 = heuristic, 1 .. 12 = agents per tile, 16 = never
 
@@ -1648,26 +1772,32 @@ int encoder_launch_b3(const float* obs, const float* packed, float* feat, int M,
 }
 
 // whole policy step of B graphs with N <= 16 agents and K = 2, 3 or 4 taps: one workgroup per graph
-template <int KT, bool CP>
+template <int KT, bool CP, int NFIX = 0>
 static int policy_launch_fused_b3_k(const float* obs, const float* packed, const PolicyTail& pt, hipStream_t st) {
     static LdsAttrOnce once;
-    set_lds_attr_once(once, reinterpret_cast<const void*>(&encoder_kernel_b3<true, KT, CP>), (int)kB3SmemFused);
-    hipLaunchKernelGGL((encoder_kernel_b3<true, KT, CP>), dim3(pt.B), dim3(kThreads), kB3SmemFused, st, obs, packed,
+    set_lds_attr_once(once, reinterpret_cast<const void*>(&encoder_kernel_b3<true, KT, CP, NFIX>), (int)kB3SmemFused);
+    hipLaunchKernelGGL((encoder_kernel_b3<true, KT, CP, NFIX>), dim3(pt.B), dim3(kThreads), kB3SmemFused, st, obs, packed,
                        static_cast<float*>(nullptr), pt.B * pt.N, b3_plane_flag(), pt);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
+template <int KT>
+static int policy_launch_fused_b3_form(const float* obs, const float* packed, const PolicyTail& pt, hipStream_t st) {
+    if (pt.N > kCpMaxAgents || g_policy_column_packing.load(std::memory_order_relaxed) == 0)
+        return policy_launch_fused_b3_k<KT, false>(obs, packed, pt, st);
+    // the one team size with an instantiation of its own (kCpTeamFixed: more of them cost compile time and code size)
+    if (pt.N == kCpTeamFixed && g_policy_cp_team.load(std::memory_order_relaxed) != 0)
+        return policy_launch_fused_b3_k<KT, true, kCpTeamFixed>(obs, packed, pt, st);
+    return policy_launch_fused_b3_k<KT, true>(obs, packed, pt, st);
+}
 
 // pt.filt_h2 must point at the b3 region of the filter pack.  Teams of <= kCpMaxAgents agents take the column-packed
-// front half (same logits to the bit: tests/test_gpu_parity.py::test_column_packed_policy_kernel_is_bit_identical).
+// front half (same logits to the bit: tests/test_gpu_parity.py::test_column_packed_policy_kernel_is_bit_identical), a
+// team of kCpTeamFixed agents its compile-time form (again the same bits: tests/test_gpu_policy_team10.py).
 int policy_launch_fused_b3(const float* obs, const float* packed, const PolicyTail& pt, int K, hipStream_t st) {
-    const bool cp = pt.N <= kCpMaxAgents && g_policy_column_packing.load(std::memory_order_relaxed) != 0;
     switch (K) {
-        case 2: return cp ? policy_launch_fused_b3_k<2, true>(obs, packed, pt, st)
-                          : policy_launch_fused_b3_k<2, false>(obs, packed, pt, st);
-        case 3: return cp ? policy_launch_fused_b3_k<3, true>(obs, packed, pt, st)
-                          : policy_launch_fused_b3_k<3, false>(obs, packed, pt, st);
-        case 4: return cp ? policy_launch_fused_b3_k<4, true>(obs, packed, pt, st)
-                          : policy_launch_fused_b3_k<4, false>(obs, packed, pt, st);
+        case 2: return policy_launch_fused_b3_form<2>(obs, packed, pt, st);
+        case 3: return policy_launch_fused_b3_form<3>(obs, packed, pt, st);
+        case 4: return policy_launch_fused_b3_form<4>(obs, packed, pt, st);
         default: return -2;
     }
 }
