@@ -640,12 +640,13 @@ class _LSIGFFunction(torch.autograd.Function):
                 dx = _LSIGFFunction._dense_dx(ctx, h, S, dy.permute(0, 2, 1)).permute(0, 2, 1).contiguous()
         if ctx.needs_input_grad[0]:
             dyp = dy if ctx.Nin == N else torch.nn.functional.pad(dy, (0, N - ctx.Nin))
-            dy2 = dyp.permute(1, 0, 2).reshape(F_out, B * N)             # [F, B*N] (one copy)
+            # [F, B*N]: one copy -- or, for a single node (or sample), a VIEW of dy with other strides than a copy's
+            dy2 = dyp.permute(1, 0, 2).reshape(F_out, B * N)
             # dh[f,e,k,g] = sum_(b,n) dy2[f,(b,n)] zs[(e,k),(b,n),g]: E*K small GEMMs with a long contraction,
             # split over workgroups by gnnpp_gemm_kmajor and written straight into the [F,E,K,G] layout
             dh = _native.grad_out(ctx.param_ptrs[0], (F_out, E, K, G), dy.device)
-            _native.gemm_kmajor(dy2, (0, B * N, 1), zs, (B * N * G, G), dh, (G, E * K * G), E * K, F_out, G,
-                                B * N)
+            _native.gemm_kmajor(dy2, (0, dy2.stride(0), dy2.stride(1)), zs, (B * N * G, G), dh, (G, E * K * G), E * K,
+                                F_out, G, B * N)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             if ctx.bias_shape[-1] == 1 or len(ctx.bias_shape) == 1:
                 db = dy.sum(dim=(0, 2)).reshape(ctx.bias_shape)
