@@ -29,6 +29,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp.h')
 MAPF_DISTANCE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_distance.h')
 CASEGEN_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_casegen.h')
 MAPF_AUDIT_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_audit.h')
+ROLLOUT_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_trace.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
@@ -95,7 +96,7 @@ def precision_code(p):
 
 def _sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [HEADER, MAPF_DISTANCE_HEADER, CASEGEN_HEADER,
-                                                                          MAPF_AUDIT_HEADER]
+                                                                          MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -253,6 +254,13 @@ class MapfStruct(ctypes.Structure):
                 ('restart', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_size_t)]
 
 
+class RolloutTraceStruct(ctypes.Structure):
+    """struct gnnpp_rollout_trace (include/gnnpp_rollout_trace.h)."""
+    _fields_ = [('path', ctypes.c_void_p), ('action', ctypes.c_void_p), ('moves', ctypes.c_void_p),
+                ('shielded', ctypes.c_void_p), ('steps', ctypes.c_void_p), ('seen_done', ctypes.c_void_p),
+                ('T_cap', ctypes.c_int)]
+
+
 _vp, _ci, _cs, _ll, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_float
 _enc, _rollout = ctypes.POINTER(EncoderParams), ctypes.POINTER(RolloutStruct)
 _sched, _mapf, _gemm = ctypes.POINTER(ScheduleStruct), ctypes.POINTER(MapfStruct), ctypes.POINTER(GemmDesc)
@@ -338,17 +346,26 @@ MAPF_AUDIT_SIGNATURES = {
     'gnnpp_mapf_audit_workspace_bytes': (_cs, [_ci] * 3),
     'gnnpp_mapf_audit': (_ci, [_vp, _ci] + [_vp] * 4 + [_ci] * 5 + [_vp] * 7 + [_cs, _vp]),
 }
+# include/gnnpp_rollout_trace.h, the companion header of the rollout's trace: a table of its own for the same reason
+# (tests/test_rollout_trace_abi.py)
+_trace = ctypes.POINTER(RolloutTraceStruct)
+ROLLOUT_TRACE_SIGNATURES = {
+    'gnnpp_rollout_trace_begin': (_ci, [_rollout, _trace, _vp]),
+    'gnnpp_rollout_trace_record': (_ci, [_rollout, _trace, _vp]),
+    'gnnpp_rollout_policy_steps_traced': (_ci, [_rollout] + [_vp] * 5 + [_ci, _ci, _ci, _trace, _vp]),
+}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
 MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 
 
 def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
-    build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES and MAPF_AUDIT_SIGNATURES; returns the
-    library."""
+    build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES and
+    ROLLOUT_TRACE_SIGNATURES; returns the library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
-            list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + optional:
+            list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + \
+            list(ROLLOUT_TRACE_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

@@ -29,6 +29,7 @@
 #include "expert_team_lists_kernel.hip"    // the expert schedules' graphs as capped neighbour lists, and the draw from them
 #include "train_encoder.hip"
 #include "train_ops.hip"
+#include "rollout_trace_kernels.hip"       // the rollout's trace: a record launch behind each move, no simulator kernel touched
 
 using namespace gnnpp;
 
@@ -967,6 +968,44 @@ int gnnpp_mapf_audit(const unsigned char* grid, int grid_batched, const int* sta
     a.first = first;
     a.ws = static_cast<int*>(workspace);
     return mapf_audit_launch(a, static_cast<hipStream_t>(stream));
+}
+
+// include/gnnpp_rollout_trace.h: the struct's sizes and pointers, the trace's, then the `count` steps from `first` that are to
+// be recorded; nothing is enqueued on an error
+static bool rollout_trace_ok(const gnnpp_rollout* r, const gnnpp_rollout_trace* tr) {
+    return r && tr && r->pos && r->B > 0 && r->N > 0 && r->N <= GNNPP_ROLLOUT_MAX_TEAM &&
+           (long long)r->B * r->N <= 0x7fffffffLL && tr->path && tr->steps && tr->seen_done && tr->T_cap >= 1;
+}
+
+static bool rollout_trace_steps_ok(const gnnpp_rollout* r, const gnnpp_rollout_trace* tr, int first, int count) {
+    if (first < 1 || first > tr->T_cap || count < 1 || count > tr->T_cap - first + 1) return false;
+    return r->logits || r->actions || !(tr->action || tr->shielded);
+}
+
+int gnnpp_rollout_trace_begin(const gnnpp_rollout* r, const gnnpp_rollout_trace* tr, void* stream) {
+    if (!rollout_trace_ok(r, tr)) return GNNPP_ERR_ARG;
+    return rollout_trace_begin_launch(*r, *tr, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_rollout_trace_record(const gnnpp_rollout* r, const gnnpp_rollout_trace* tr, void* stream) {
+    if (!rollout_trace_ok(r, tr) || !rollout_trace_steps_ok(r, tr, r->currentstep, 1)) return GNNPP_ERR_ARG;
+    return rollout_trace_record_launch(*r, *tr, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_rollout_policy_steps_traced(const gnnpp_rollout* r, const float* enc_packed, const float* filt_packed,
+                                      const float* gf_bias, const float* act_w, const float* act_b, int K, int nsteps,
+                                      int precision, const gnnpp_rollout_trace* tr, void* stream) {
+    if (!r || nsteps <= 0 || r->tie_mode == GNNPP_TIE_REPLAY) return GNNPP_ERR_ARG;
+    if (!rollout_trace_ok(r, tr) || !rollout_trace_steps_ok(r, tr, r->currentstep, nsteps)) return GNNPP_ERR_ARG;
+    gnnpp_rollout rs = *r;
+    for (int s = 0; s < nsteps; ++s) {
+        rs.currentstep = r->currentstep + s;
+        int rc = gnnpp_rollout_policy_step(&rs, enc_packed, filt_packed, gf_bias, act_w, act_b, K, precision, stream);
+        if (rc != GNNPP_OK) return rc;                   // (argument / shape errors surface at s = 0)
+        rc = rollout_trace_record_launch(rs, *tr, static_cast<hipStream_t>(stream));
+        if (rc != GNNPP_OK) return rc;
+    }
+    return GNNPP_OK;
 }
 
 }  // extern "C"

@@ -363,6 +363,37 @@ def write_failure_cases(directory, rollout, ids=None, results=None):
     return written
 
 
+def write_prediction_cases(directory, rollout, ids=None, results=None):
+    """The predicted schedule of every episode of a RECORDED rollout (BatchedRollout / GroupedRollout with record=...) next
+    to the input file of its ORIGINAL starts, as save_success_cases writes them for the reference's movies
+    (multirobotsim_dcenlocal_onlineExpert.py:732-799): `directory`/input/{mode}Cases_ID{:05d}.yaml and
+    `directory`/predict_{mode}/{mode}Cases_ID{:05d}.yaml with mode = success | failure.  ids: the dataset ID of each
+    episode (default: its index); results: rollout.results() if already at hand.  Returns the list of (episode index,
+    input path, prediction path); read_solution(input path, prediction path) reads a pair back."""
+    trace = getattr(rollout, 'trace', None)
+    if trace is None:
+        raise _native.GnnppError('write_prediction_cases needs a recorded rollout (record=True)')
+    res = rollout.results() if results is None else results
+    grid, goal = trace.grid.cpu().numpy(), trace.goal.cpu().numpy()
+    starts = trace.path[:, 0].cpu().numpy()
+    ids = list(range(trace.B)) if ids is None else [int(i) for i in ids]
+    if len(ids) != trace.B:
+        raise _native.GnnppError('ids: one per episode (%d), got %d' % (trace.B, len(ids)))
+    written = []
+    for b in range(trace.B):
+        mode = 'success' if bool(res['success'][b]) else 'failure'
+        name = '{}Cases_ID{:05d}.yaml'.format(mode, ids[b])
+        paths = [os.path.join(directory, sub, name) for sub in ('input', 'predict_' + mode)]
+        texts = (failure_case_yaml(grid[b] if trace.grid_batched else grid, starts[b], goal[b]),
+                 trace.prediction_yaml(b, results=res))
+        for path, text in zip(paths, texts):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, 'w') as f:
+                f.write(text)
+        written.append((b, paths[0], paths[1]))
+    return written
+
+
 def _yaml_of(src):
     import yaml
     if isinstance(src, (bytes, str)) and not os.path.exists(src):

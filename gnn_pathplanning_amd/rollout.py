@@ -16,9 +16,13 @@ replaced by a deterministic rule (`tie_mode`): 'lowest' index, 'hashed' counter-
 recorded choices (parity tests), or 'mt19937' = CPython's random.choice itself on a per-episode
 Mersenne-Twister stream (episode b behaves as the reference does after random.seed(seed[b])).
 Positions are (row, col) integers.
+
+`record=True` keeps what the reference keeps as path_predict / action_predict: a RolloutTrace on the device, one small
+launch behind every move on every route, still without a host synchronisation.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _native
@@ -35,9 +39,89 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
+class RolloutTrace:
+    """What a recorded rollout did, as device tensors (include/gnnpp_rollout_trace.h):
+
+        path      int32 [B,T_cap+1,N,2]  the positions after every step, row 0 = the starts: the solvers' schedule layout
+        action    int8  [B,T_cap,N]      the action each agent asked for at step t + 1 (the argmax of its logits, first
+                                         maximum), -1 where nothing was recorded
+        moves     int32 [B,N]            steps at which the agent's position changed
+        shielded  int32 [B,N]            steps at which the agent asked to move and stood still instead: the map's edge, an
+                                         obstacle or the collision shield stopped it
+        steps     int32 [B]              the last step at which the episode was not frozen
+
+    An episode whose loop has ended is frozen by the move kernels; its rows after steps[b] repeat row steps[b], as a
+    solver's schedule repeats a goal, its `action` stays -1 there and its counters stand still.  `seen_done` [B] is the
+    recorder's own word behind that rule.  The tensors are filled by launches on the rollout's stream: synchronise (or call
+    rollout.results()) before reading them on the host; schedule() and prediction_yaml() do."""
+
+    def __init__(self, owner, grid, grid_batched, goal, T_cap, tensors=None):
+        self._owner = owner                                   # the rollout: results() for the files' statistics
+        self.grid, self.grid_batched, self.goal = grid, int(grid_batched), goal
+        self.B, self.N = int(goal.shape[0]), int(goal.shape[1])
+        self.T_cap, self.device = int(T_cap), goal.device
+        if tensors is None:
+            B, N, T, dev = self.B, self.N, self.T_cap, self.device
+            tensors = (torch.zeros(B, T + 1, N, 2, dtype=torch.int32, device=dev),   # (rows no record reached: 0)
+                       torch.empty(B, T, N, dtype=torch.int8, device=dev),
+                       torch.empty(B, N, dtype=torch.int32, device=dev), torch.empty(B, N, dtype=torch.int32, device=dev),
+                       torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+        self.path, self.action, self.moves, self.shielded, self.steps, self.seen_done = tensors
+        s = _native.RolloutTraceStruct()
+        s.path, s.action, s.moves, s.shielded = _p(self.path), _p(self.action), _p(self.moves), _p(self.shielded)
+        s.steps, s.seen_done, s.T_cap = _p(self.steps), _p(self.seen_done), self.T_cap
+        self._s = s
+
+    def _sync(self):
+        if hasattr(self._owner, 'join'):
+            self._owner.join()
+        torch.cuda.synchronize(self.device)
+
+    def schedule(self, b):
+        """[steps[b]+1, N, 2] int64 of episode b: what Solutions.schedule and expert.read_solution return."""
+        self._sync()
+        return self.path[b, :int(self.steps[b]) + 1].cpu().numpy().astype(np.int64)
+
+    def audit(self):
+        """mapf.enqueue_audit on `path` as it lies in memory, rows 0 .. steps[b] of every episode, against the rollout's
+        maps and goals and with row 0 as the starts, enqueued on the current stream behind the recorded steps.  Returns
+        mapf.Audit.  The move rule forbids a jump, a state off the map or on an obstacle and a false start; vertex and
+        swap conflicts are what the collision shield left, as the reference reports them in its own flag."""
+        from . import mapf
+        H, W = int(self.grid.shape[-2]), int(self.grid.shape[-1])
+        if H > mapf.MAX_TEAM_SIDE or W > mapf.MAX_TEAM_SIDE:
+            raise _native.GnnppError('maps of at most %d x %d cells (got %d x %d)'
+                                     % (mapf.MAX_TEAM_SIDE, mapf.MAX_TEAM_SIDE, H, W))
+        if self.T_cap > mapf.MAX_TEAM_STEPS:
+            raise _native.GnnppError('schedules of at most %d steps (got %d)' % (mapf.MAX_TEAM_STEPS, self.T_cap))
+        if hasattr(self._owner, 'join'):
+            self._owner.join()
+        out = mapf.empty_audit(self.B, self.N, self.T_cap, self.device)
+        start = self.path[:, 0].contiguous()
+        out._keep = (self, start)
+        mapf.enqueue_audit(self.grid, start, self.goal, self.path, self.steps, out)
+        return out
+
+    def prediction_yaml(self, b, results=None):
+        """Text of the predicted schedule of episode b as save_success_cases writes it
+        (multirobotsim_dcenlocal_onlineExpert.py:777-799): statistics (cost = the rollout's flowtime, its makespan,
+        succeed) and, per agent, x / y / t of rows 0 .. steps[b].  results: rollout.results() if already at hand."""
+        res = self._owner.results() if results is None else results
+        sched = self.schedule(b)
+        out = ['statistics:\n', '    cost: {}\n'.format(int(res['flowtime'][b])),
+               '    makespan: {}\n'.format(int(res['makespan'][b])),
+               '    succeed: {}\n'.format(int(bool(res['success'][b]))), 'schedule:\n']
+        for n in range(self.N):
+            out.append('    agent{}:\n'.format(n))
+            for t in range(sched.shape[0]):
+                out.append('       - x: {}\n         y: {}\n         t: {}\n'.format(int(sched[t, n, 0]),
+                                                                                  int(sched[t, n, 1]), t))
+        return ''.join(out)
+
+
 class BatchedRollout:
     def __init__(self, grid, starts, goals, maxstep, device, commR=6.0, tie_mode='lowest', seed=0,
-                 rng_words=None, graph='dense'):
+                 rng_words=None, graph='dense', record=False):
         """grid [B,H,W] or [H,W] (1 = obstacle); starts, goals [B,N,2]; maxstep int or [B].  Teams of up to
         MAX_TEAM agents; beyond MAX_AGENTS the simulator runs the large-team kernels, which need H * W <=
         MAX_TEAM_CELLS.  rng_words (tie_mode 'mt19937'): words of each episode's random stream, by default 2048,
@@ -45,7 +129,10 @@ class BatchedRollout:
         graph: 'dense' (default) -- the communication graph is the GSO S [B,N,N] -- or 'lists': it is the team filter's
         neighbour lists (gnnpp_rollout_lists; `self.lists`, a uint8 block of B graphs, see graphML.team_lists_views), no
         S is ever allocated, and step(model) needs a planner that takes lists (DecentralPlannerNet with
-        largeGraphFilter='lists', its forward_logits_lists).  Same episodes, step for step."""
+        largeGraphFilter='lists', its forward_logits_lists).  Same episodes, step for step.
+        record: True keeps a RolloutTrace (`self.trace`) of max(maxstep) steps, an integer one of that many steps; every
+        move of every route is recorded by a launch behind it, a step beyond the trace's last row raises before anything
+        is enqueued, and nothing else about the rollout changes."""
         dev = torch.device(device)
         if dev.type != 'cuda':
             raise _native.GnnppError('BatchedRollout needs a HIP device (no CPU fallback)')
@@ -123,11 +210,38 @@ class BatchedRollout:
         if self.tie_mode == 3:
             r.rng_words, r.rng_cursor, r.rng_max = _p(self.rng_words), _p(self.rng_cursor), int(rng_words)
         self._r = r
+        self.trace = None
+        if record is not False and record is not None:
+            T_cap = int(self.maxstep.max().item()) if record is True else int(record)
+            if T_cap < 1:
+                raise _native.GnnppError('record: a trace of at least one step (got %d)' % T_cap)
+            self.trace = RolloutTrace(self, self.grid, self.grid_batched, self.goal, T_cap)
+            self._trace_call(_native.lib().gnnpp_rollout_trace_begin, 'gnnpp_rollout_trace_begin')
 
     # -- the three simulator calls -------------------------------------------------------------
     def _call(self, fn, what):
         with _native.device_guard(self.device):
             _native.check(fn(ctypes.byref(self._r), _native.stream_ptr(self.device)), what)
+
+    def _trace_call(self, fn, what):
+        with _native.device_guard(self.device):
+            _native.check(fn(ctypes.byref(self._r), ctypes.byref(self.trace._s), _native.stream_ptr(self.device)), what)
+
+    def _record(self):
+        """The trace's row of the move just enqueued (its logits / actions are still in the struct)."""
+        if self.trace is not None:
+            self._trace_call(_native.lib().gnnpp_rollout_trace_record, 'gnnpp_rollout_trace_record')
+
+    def _check_room(self, n=1, currentstep=None):
+        """record: the next n steps must fit the trace, and be the rollout's own next steps -- before anything is enqueued."""
+        if self.trace is None:
+            return
+        if currentstep is not None and int(currentstep) != self.t + 1:
+            raise _native.GnnppError('a recorded rollout takes its steps in order: the next one is %d (got currentstep=%d)'
+                                     % (self.t + 1, int(currentstep)))
+        if self.t + n > self.trace.T_cap:
+            raise _native.GnnppError('step %d is beyond the trace (record: T_cap = %d steps)'
+                                     % (self.t + n, self.trace.T_cap))
 
     def observe(self):
         """[B,N,3,11,11] float32 observations of the current positions (buffer reused each step)."""
@@ -170,9 +284,11 @@ class BatchedRollout:
         (allReachGoal at entry, moveCollision, predictCollision) -- a device tensor."""
         self._prepare_move(logits, actions, choices, currentstep)
         self._call(_native.lib().gnnpp_rollout_move, 'gnnpp_rollout_move')
+        self._record()
         return self.flags
 
     def _prepare_move(self, logits, actions, choices, currentstep):
+        self._check_room(1, currentstep)
         r = self._r
         keep = []
         if logits is not None:
@@ -205,6 +321,7 @@ class BatchedRollout:
             self._call(_native.lib().gnnpp_rollout_observe, 'gnnpp_rollout_observe')
         else:
             self._call(_native.lib().gnnpp_rollout_step, 'gnnpp_rollout_step')
+        self._record()                                     # (pos, and the logits / actions of this move, are in memory)
         self._state_step = self.t                          # obs / S describe the positions after step t
         return self.flags
 
@@ -227,12 +344,20 @@ class BatchedRollout:
         # range guard: only the opt-in split-f16 arithmetic has an input domain
         r.range_flag = _p(model._flag(self.device)) if prec == _native.PREC_SPLIT_F16 else None
         r.currentstep = self.t + 1
+        self._check_room(nsteps)
         with _native.device_guard(self.device):
-            rc = _native.lib().gnnpp_rollout_policy_steps(ctypes.byref(r), enc, taps, gb, aw, ab, K, nsteps, prec,
-                                                          _native.stream_ptr(self.device))
+            if self.trace is not None:              # the same launches, a record launch behind each
+                what = 'gnnpp_rollout_policy_steps_traced'
+                rc = _native.lib().gnnpp_rollout_policy_steps_traced(ctypes.byref(r), enc, taps, gb, aw, ab, K, nsteps, prec,
+                                                                     ctypes.byref(self.trace._s),
+                                                                     _native.stream_ptr(self.device))
+            else:
+                what = 'gnnpp_rollout_policy_steps'
+                rc = _native.lib().gnnpp_rollout_policy_steps(ctypes.byref(r), enc, taps, gb, aw, ab, K, nsteps, prec,
+                                                              _native.stream_ptr(self.device))
         if rc == _native.ERR_UNSUPPORTED:           # shape not supported by the fused kernel
             return False
-        _native.check(rc, 'gnnpp_rollout_policy_steps')
+        _native.check(rc, what)
         self.t += nsteps
         self._state_step = self.t
         return True
@@ -243,6 +368,7 @@ class BatchedRollout:
         fused move kernel."""
         if self.graph == 'lists':
             self._check_lists_model(model)
+        self._check_room()
         if self.t == 0:                                      # step 0 may grow the radius
             self.observe()
             self.gso()
@@ -275,6 +401,7 @@ class BatchedRollout:
     def steps(self, model, n):
         """n rollout steps.  Small teams (the one-launch step): the launches of all n steps are enqueued by ONE
         C call (gnnpp_rollout_policy_steps) -- no interpreter between two steps."""
+        self._check_room(n)
         done = 0
         if n > 1 and (self._state_step != self.t or self.t == 0):
             self.step(model)                                 # (the first step may grow the radius)
@@ -335,15 +462,18 @@ class GroupedRollout:
     overlap with the other group's kernel.  Measured at C2 (512 episodes of 10 agents, one-launch steps): 44-49 us
     per step of all 512 episodes with two groups against 52-55 us on one stream.
 
-    Same interface as BatchedRollout for what a rollout driver needs: steps(), run(), results().  tie_mode
+    Same interface as BatchedRollout for what a rollout driver needs: steps(), run(), results(), and with record=... the
+    groups' traces as one (`trace`).  tie_mode
     'lowest' and 'mt19937' give exactly the single-batch results (episode b keeps its generator seed + b);
     'hashed' hashes the episode's index inside its group, i.e. draws a different -- equally arbitrary -- stream."""
 
-    def __init__(self, grid, starts, goals, maxstep, device, groups=2, seed=0, **kw):
+    def __init__(self, grid, starts, goals, maxstep, device, groups=2, seed=0, record=False, **kw):
         starts, goals = torch.as_tensor(starts), torch.as_tensor(goals)
         g = torch.as_tensor(grid)
         B = int(starts.shape[0])
         ms = torch.as_tensor(maxstep)
+        if record is True:                                   # one T_cap for every group: the slices form one trace
+            record = int(ms.max())
         groups = max(1, min(int(groups), B))
         bounds = [round(i * B / groups) for i in range(groups + 1)]
         self.envs, self.streams, self.slices = [], [], []
@@ -351,7 +481,7 @@ class GroupedRollout:
         for lo, hi in zip(bounds[:-1], bounds[1:]):
             sd = seed[lo:hi] if hasattr(seed, '__len__') else int(seed) + lo
             self.envs.append(BatchedRollout(g[lo:hi] if g.dim() == 3 else g, starts[lo:hi], goals[lo:hi],
-                                            ms[lo:hi] if ms.dim() else ms, dev, seed=sd, **kw))
+                                            ms[lo:hi] if ms.dim() else ms, dev, seed=sd, record=record, **kw))
             self.streams.append(torch.cuda.Stream(device=dev))
             self.slices.append((lo, hi))
         self.device, self.B, self.N = dev, B, self.envs[0].N
@@ -374,6 +504,20 @@ class GroupedRollout:
     @property
     def t(self):
         return self.envs[0].t                                # (all groups step together)
+
+    @property
+    def trace(self):
+        """record: the groups' traces as ONE RolloutTrace, their slices concatenated in episode order (a copy, made behind
+        a join()); None for an unrecorded rollout."""
+        parts = [e.trace for e in self.envs]
+        if parts[0] is None:
+            return None
+        self.join()
+        e0 = self.envs[0]
+        cat = lambda name: torch.cat([getattr(p, name) for p in parts], 0)                       # noqa: E731
+        grid = torch.cat([e.grid for e in self.envs], 0) if e0.grid_batched else e0.grid
+        return RolloutTrace(self, grid, e0.grid_batched, torch.cat([e.goal for e in self.envs], 0), parts[0].T_cap,
+                            tuple(cat(k) for k in ('path', 'action', 'moves', 'shielded', 'steps', 'seen_done')))
 
     def join(self):
         """Make the caller's stream wait for every group's work."""
