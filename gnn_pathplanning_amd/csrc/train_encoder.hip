@@ -994,7 +994,11 @@ struct TrainWs {
 // batch: 128 up to 1 280 agent-samples, 256 beyond -- with the five layers in ONE launch the parallelism comes from
 // the layers (r06b, graphed step, `profiles/r06_train_wgrad_sweep.jsonl`: 64 x 10: 64: 0.370, 96: 0.358, 128: 0.350,
 // 192: 0.354, 256: 0.359, 320: 0.363, 448: 0.373 ms; 512 x 10: 128: 1.335, 256: 1.317, 512: 1.332, 1024: 1.377 ms;
-// one launch per layer, r06a: 256 was best at 64 x 10).  Set it BEFORE a forward call: the workspace size depends on it.
+// one launch per layer, r06a: 256 was best at 64 x 10).  train_ws_layout reads it in the size query, in the forward AND in
+// the backward call, and wpart[], nsplit and ips move with it: the caller holds ONE value from the size query until the
+// backward call on that workspace has returned (another value there = weight-gradient partials written outside the
+// allocation; nothing in these calls can check it, the workspace carries no header).  decentralplanner.py's autograd
+// function records the value at the size query and raises before any launch when forward or backward finds another.
 std::atomic<int> g_train_wgrad_wgs{0};
 std::atomic<int> g_train_running_fused{1};      // GNNPP_TUNE_TRAIN_RUNNING_FUSED
 

@@ -96,6 +96,10 @@ class _EncoderTrainFunction(torch.autograd.Function):
         ps = [t.detach() if (t.dtype is torch.float32 and t.is_contiguous()) else t.detach().contiguous().float()
               for t in tensors]
         p = _encoder_params(ps, buffers, eps)
+        # The library lays the workspace out under GNNPP_TUNE_TRAIN_WGRAD_WGS in the size query, in the forward call and
+        # again in the backward call (the launch geometry is computed on the host): the value the workspace was sized
+        # under is read ONCE here, must still hold when the forward call returns, and is carried to backward().
+        wgs = L.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS)
         ws = torch.empty(L.gnnpp_encoder_train_workspace_floats(N, B), dtype=torch.float32, device=dev)
         feat = torch.empty(B, N, 128, dtype=torch.float32, device=dev)     # sample-major: node-major rows
         with _native.device_guard(dev):
@@ -104,7 +108,12 @@ class _EncoderTrainFunction(torch.autograd.Function):
                                                     (ctypes.c_void_p * 5)(*[c.data_ptr() for c in counters])
                                                     if counters is not None else None, 1, _ptr(enc_pack),
                                                     _native.stream_ptr(dev)), 'gnnpp_encoder_train_fwd')
+        now = L.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS)
+        if now != wgs:
+            raise _native.GnnppError('GNNPP_TUNE_TRAIN_WGRAD_WGS changed from %d to %d during the train-mode encoder '
+                                     'forward: its workspace was sized under %d' % (wgs, now, wgs))
         ctx.save_for_backward(obs, ws, *ps)
+        ctx.wgrad_wgs = wgs
         ctx.eps = float(eps)
         ctx.enc_pack = enc_pack                    # (the pack of THESE weights: the backward call reads its other half)
         return feat
@@ -112,6 +121,13 @@ class _EncoderTrainFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dfeat):
         L = _native.lib()
+        # before anything is allocated or launched: under another split count the weight-gradient kernels would address
+        # partial slabs that the forward's workspace does not hold
+        now = L.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS)
+        if now != ctx.wgrad_wgs:
+            raise _native.GnnppError('GNNPP_TUNE_TRAIN_WGRAD_WGS is %d, but the forward call sized and laid out this '
+                                     'workspace under %d: set the knob back, or run forward and backward under one '
+                                     'value' % (now, ctx.wgrad_wgs))
         obs, ws = ctx.saved_tensors[0], ctx.saved_tensors[1]
         ps = ctx.saved_tensors[2:]
         B, N = obs.shape[0], obs.shape[1]

@@ -126,8 +126,14 @@ const char* gnnpp_error_string(int code);
 #define GNNPP_TUNE_TRAIN_WGRAD_WGS   17  /* workgroups per layer of the training step's weight-gradient kernel (ONE launch for all
                                          five layers behind the backward chain; image splits x output-channel tiles): 0 (default) = by the batch (128 up to 1 280 agent-samples, 256
                                          beyond), or 16 .. 2048: more splits = shorter workgroups, more partial sums to add.
-                                         Set before gnnpp_encoder_train_workspace_floats / _train_fwd: the workspace size
-                                         depends on it.  Same gradients to rounding (v330)                              */
+                                         The workspace size AND its layout depend on it, and the size query, _train_fwd and
+                                         _train_bwd each read it again (the launch geometry is computed on the host): a C
+                                         caller must hold ONE value from gnnpp_encoder_train_workspace_floats until the
+                                         _train_bwd call on that workspace has returned -- under another value _train_bwd
+                                         writes partial sums outside the allocation, and no call checks this.  The Python
+                                         side enforces it: the autograd function of the train-mode encoder records the value
+                                         it sized the workspace under and raises before any launch if the forward or the
+                                         backward finds another.  Same gradients to rounding (v330)                    */
 #define GNNPP_TUNE_TRAIN_RUNNING_FUSED 19 /* 1 (default): gnnpp_encoder_train_fwd updates the BatchNorm running statistics inside
                                          its last BatchNorm launch (the workgroups of a channel tile publish their statistics
                                          with an agent-scope release / ticket / acquire hand-off and the last one to arrive
