@@ -30,6 +30,7 @@ MAPF_DISTANCE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_ma
 CASEGEN_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_casegen.h')
 MAPF_AUDIT_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_audit.h')
 ROLLOUT_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_trace.h')
+SCHEDULE_DRAW_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_schedule_draw.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
@@ -96,7 +97,8 @@ def precision_code(p):
 
 def _sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [HEADER, MAPF_DISTANCE_HEADER, CASEGEN_HEADER,
-                                                                          MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER]
+                                                                          MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER,
+                                                                          SCHEDULE_DRAW_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -354,18 +356,24 @@ ROLLOUT_TRACE_SIGNATURES = {
     'gnnpp_rollout_trace_record': (_ci, [_rollout, _trace, _vp]),
     'gnnpp_rollout_policy_steps_traced': (_ci, [_rollout] + [_vp] * 5 + [_ci, _ci, _ci, _trace, _vp]),
 }
+# include/gnnpp_schedule_draw.h, the companion header of the draw from stored schedules: a table of its own for the same
+# reason (tests/test_schedule_draw_abi.py)
+SCHEDULE_DRAW_SIGNATURES = {
+    'gnnpp_schedule_draw_workspace_bytes': (_cs, [_ci, _ci]),
+    'gnnpp_schedule_draw': (_ci, [_sched, _vp, _ci, _vp, _vp, _vp, _vp, _cs, _vp, _cs, _vp]),
+}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
 MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 
 
 def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
-    build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES and
-    ROLLOUT_TRACE_SIGNATURES; returns the library."""
+    build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES,
+    ROLLOUT_TRACE_SIGNATURES and SCHEDULE_DRAW_SIGNATURES; returns the library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
             list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + \
-            list(ROLLOUT_TRACE_SIGNATURES.items()) + optional:
+            list(ROLLOUT_TRACE_SIGNATURES.items()) + list(SCHEDULE_DRAW_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

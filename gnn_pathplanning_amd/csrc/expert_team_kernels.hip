@@ -102,16 +102,13 @@ __global__ __launch_bounds__(1024) void expert_team_scan_kernel(const ScheduleAr
     if (a == 0) p.step_info[t] = k | (status << 16);
 }
 
-// Pass 3: degrees with the case's final radius -> inv_ws[t, n] = sqrt(1.0 / deg) (fp64), and the expert action:
-// one-hot of next - current in the order [-1,0] [0,-1] [1,0] [0,1] [0,0] (legal: pass 1).  A flagged case is left
-// unwritten (here and in the two kernels below).
-__global__ __launch_bounds__(1024) void expert_team_degree_kernel(const ScheduleArgs p, double* inv_ws) {
-    extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
-    const int N = p.N, t = blockIdx.x, a = threadIdx.x;
-    const int c = schedule_case_of(p.case_start, p.C, t);
-    if (p.status[c] != 0) return;                                // (workgroup-uniform)
-    int* px = reinterpret_cast<int*>(gnnpp_smem);
-    int* py = px + N;
+// The degree pass of step t of case c for agent a (a thread per agent, the whole workgroup calls it; LDS px | py [N]):
+// inv[n] = sqrt(1.0 / deg) (fp64) under the case's final radius and tgt[n, 0..4] = the expert action, the one-hot of
+// next - current in the order [-1,0] [0,-1] [1,0] [0,1] [0,0] (legal: pass 1).  inv / tgt: the step's rows of the
+// caller's arrays -- row t of the sample calls, row b of a draw (schedule_draw_kernels.hip).
+__device__ __forceinline__ void schedule_team_degree_step(const ScheduleArgs& p, int t, int c, int a, int* px, int* py,
+                                                          double* inv, float* tgt) {
+    const int N = p.N;
     const int* pos = p.pos + (size_t)t * N * 2;
     const bool live = a < N;
     int mx = 0, my = 0;
@@ -121,35 +118,39 @@ __global__ __launch_bounds__(1024) void expert_team_degree_kernel(const Schedule
     const unsigned Tu = dist2_bound(p.radius[c]);
     int deg = 0;
     for (int j = 0; j < N; ++j) deg += j != a && dist2(px[j], py[j], mx, my) <= Tu;
-    inv_ws[(size_t)t * N + a] = inv_sqrt_degree(deg);
+    inv[a] = inv_sqrt_degree(deg);
     const int* nxt = schedule_next_state(p, c, t, pos);
     const int dx = nxt[2 * a] - mx, dy = nxt[2 * a + 1] - my;
-    expert_target_store(p.target + ((size_t)t * N + a) * 5, dx, dy);
+    expert_target_store(tgt + (size_t)a * 5, dx, dy);
 }
 
-// Pass 4: rows [tile * kTeamGraphRows, ...) of S[t] (and S64[t]): S64 = s_i * s_j where d2 <= threshold and i != j,
-// else 0; S = (float)S64.  Consecutive threads store consecutive floats of a row; vec: four columns per thread and
-// 16-byte stores (the launcher sets it when N % 4 == 0 and the outputs are 16-byte aligned).  LDS: px | py | s of
-// all N agents.
-__global__ __launch_bounds__(256) void expert_team_graph_kernel(const ScheduleArgs p, const double* inv_ws, int tiles,
-                                                                 int vec) {
+// Pass 3: degrees with the case's final radius -> inv_ws[t, n] = sqrt(1.0 / deg) (fp64), and the expert action.  A
+// flagged case is left unwritten (here and in the two kernels below).
+__global__ __launch_bounds__(1024) void expert_team_degree_kernel(const ScheduleArgs p, double* inv_ws) {
     extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
-    const int N = p.N, tid = threadIdx.x;
-    const int t = blockIdx.x / tiles, tile = blockIdx.x - t * tiles;
+    const int N = p.N, t = blockIdx.x;
     const int c = schedule_case_of(p.case_start, p.C, t);
     if (p.status[c] != 0) return;                                // (workgroup-uniform)
+    int* px = reinterpret_cast<int*>(gnnpp_smem);
+    schedule_team_degree_step(p, t, c, threadIdx.x, px, px + N, inv_ws + (size_t)t * N, p.target + (size_t)t * N * 5);
+}
+
+// Rows [i0, i0 + kTeamGraphRows) of the S of step t of case c -> S (and S64 unless NULL), pointers to row i0 of the
+// caller's matrix: S64 = s_i * s_j where d2 <= threshold and i != j, else 0; S = (float)S64.  inv_g [N]: the step's s.
+// Consecutive threads store consecutive floats of a row; vec: four columns per thread and 16-byte stores (the launcher
+// sets it when N % 4 == 0 and the outputs are 16-byte aligned).  256 threads; LDS: px | py | s of all N agents.
+__device__ __forceinline__ void schedule_team_graph_tile(const ScheduleArgs& p, int t, int c, int i0, const double* inv_g,
+                                                         float* S, double* S64, int vec, char* smem) {
+    const int N = p.N, tid = threadIdx.x;
     const int np = (N + 3) & ~3;                                 // (the vector reads stay inside their array)
-    int* px = reinterpret_cast<int*>(gnnpp_smem);                // [np]
+    int* px = reinterpret_cast<int*>(smem);                      // [np]
     int* py = px + np;                                           // [np]
     double* inv = reinterpret_cast<double*>(py + np);            // [np]
     const int* pos = p.pos + (size_t)t * N * 2;
-    const double* inv_g = inv_ws + (size_t)t * N;
     for (int n = tid; n < N; n += 256) { px[n] = pos[2 * n]; py[n] = pos[2 * n + 1]; inv[n] = inv_g[n]; }
     __syncthreads();
     const unsigned Tu = dist2_bound(p.radius[c]);
-    const int i0 = tile * kTeamGraphRows, rows = min(N, i0 + kTeamGraphRows) - i0;
-    float* S = p.S + ((size_t)t * N + i0) * N;
-    double* S64 = p.S64 ? p.S64 + ((size_t)t * N + i0) * N : nullptr;
+    const int rows = min(N, i0 + kTeamGraphRows) - i0;
     // item = (row r, column unit u) in row-major order, 256 items per pass: stepped without a division
     const int units = vec ? N >> 2 : N;
     const int dr = 256 / units, du = 256 - dr * units;
@@ -188,15 +189,26 @@ __global__ __launch_bounds__(256) void expert_team_graph_kernel(const ScheduleAr
     }
 }
 
-// Pass 5: observations of 16 agents of one step; grid = groups x steps in one dimension.  LDS as
-// rollout_team_observe_kernel: goal_l [2N] | occupancy [H * W] | the stage of the output rows.
-__global__ __launch_bounds__(256) void expert_team_observe_kernel(const ScheduleArgs p, int groups) {
+// Pass 4: rows [tile * kTeamGraphRows, ...) of S[t] (and S64[t]).
+__global__ __launch_bounds__(256) void expert_team_graph_kernel(const ScheduleArgs p, const double* inv_ws, int tiles,
+                                                                 int vec) {
     extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
-    const int t = blockIdx.x / groups, n0 = (blockIdx.x - t * groups) * kObsAgentsPerWg;
+    const int N = p.N;
+    const int t = blockIdx.x / tiles, tile = blockIdx.x - t * tiles;
     const int c = schedule_case_of(p.case_start, p.C, t);
-    if (p.status[c] != 0) return;                                // (workgroup-uniform; its states may be off the map)
-    int* goal_l = reinterpret_cast<int*>(gnnpp_smem);                        // [2N]
-    unsigned char* cell = reinterpret_cast<unsigned char*>(gnnpp_smem + round16((size_t)8 * p.N));
+    if (p.status[c] != 0) return;                                // (workgroup-uniform)
+    const int i0 = tile * kTeamGraphRows;
+    schedule_team_graph_tile(p, t, c, i0, inv_ws + (size_t)t * N, p.S + ((size_t)t * N + i0) * N,
+                             p.S64 ? p.S64 + ((size_t)t * N + i0) * N : nullptr, vec, gnnpp_smem);
+}
+
+// Observations of agents [n0, n0 + 16) of step t of case c -> row `out` of p.obs (the step itself in the sample calls,
+// the pick of a draw).  256 threads; LDS as rollout_team_observe_kernel: goal_l [2N] | occupancy [H * W] | the stage of
+// the output rows.
+__device__ __forceinline__ void schedule_team_observe_group(const ScheduleArgs& p, int t, int c, int out, int n0,
+                                                            char* smem) {
+    int* goal_l = reinterpret_cast<int*>(smem);                              // [2N]
+    unsigned char* cell = reinterpret_cast<unsigned char*>(smem + round16((size_t)8 * p.N));
     float* stage = reinterpret_cast<float*>(cell + round16((size_t)p.H * p.W));
     const RolloutArgs q = schedule_as_rollout(p);
     const int* pos = p.pos + (size_t)t * p.N * 2;
@@ -205,9 +217,18 @@ __global__ __launch_bounds__(256) void expert_team_observe_kernel(const Schedule
     observe_prep(q, pos, cell, goal_l, threadIdx.x, 256);
     __syncthreads();
     const int n1 = min(p.N, n0 + kObsAgentsPerWg);
-    observe_rows(q, t, pos, n0, n1, cell, goal_l, threadIdx.x, 256, stage);
+    observe_rows(q, out, pos, n0, n1, cell, goal_l, threadIdx.x, 256, stage);
     __syncthreads();
-    observe_flush(q, t, n0, n1, stage, threadIdx.x, 256);
+    observe_flush(q, out, n0, n1, stage, threadIdx.x, 256);
+}
+
+// Pass 5: observations of 16 agents of one step; grid = groups x steps in one dimension.
+__global__ __launch_bounds__(256) void expert_team_observe_kernel(const ScheduleArgs p, int groups) {
+    extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
+    const int t = blockIdx.x / groups, n0 = (blockIdx.x - t * groups) * kObsAgentsPerWg;
+    const int c = schedule_case_of(p.case_start, p.C, t);
+    if (p.status[c] != 0) return;                                // (workgroup-uniform; its states may be off the map)
+    schedule_team_observe_group(p, t, c, t, n0, gnnpp_smem);
 }
 
 inline size_t schedule_team_workspace_bytes(int N, int T_total) { return round16((size_t)T_total * N * sizeof(double)); }

@@ -53,32 +53,26 @@ __global__ __launch_bounds__(1024) void expert_team_step_deg_kernel(const Schedu
     }
 }
 
-// Columns [tile * kListCols, ...) of step t.  LDS: (row, col) [N] | s [N] (fp64).
-__global__ __launch_bounds__(kListCols) void expert_team_lists_kernel(const ScheduleArgs p, const double* inv_ws, int tiles,
-                                                                      int* cnt_out, unsigned short* idx_out,
-                                                                      float* val_out, int cap) {
+// Column n of the lists of step t of case c (lane = the thread's index in its workgroup of kListCols, which calls this
+// as a whole) -> il / wl, the column's cap entries in the caller's arrays (il 8-byte, wl 16-byte aligned, cap % 4 == 0);
+// returns cnt, the true degree (unspecified for n >= N, which stores nothing).  LDS: (row, col) [N] | s [N] (fp64).
+__device__ __forceinline__ int schedule_team_list_column(const ScheduleArgs& p, int t, int c, int n, int lane,
+                                                         const double* inv_g, unsigned short* il, float* wl, int cap,
+                                                         char* smem) {
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
     typedef int v2i __attribute__((ext_vector_type(2)));
-    extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
-    const int N = p.N, lane = threadIdx.x;
-    const int t = blockIdx.x / tiles, n = (blockIdx.x - t * tiles) * kListCols + lane;
-    const int c = schedule_case_of(p.case_start, p.C, t);
-    if (p.status[c] != 0) return;                                // (workgroup-uniform)
-    v2i* pl = reinterpret_cast<v2i*>(gnnpp_smem);                                   // [N]
-    double* inv = reinterpret_cast<double*>(gnnpp_smem + round16((size_t)8 * N));   // [N]
+    const int N = p.N;
+    v2i* pl = reinterpret_cast<v2i*>(smem);                                         // [N]
+    double* inv = reinterpret_cast<double*>(smem + round16((size_t)8 * N));         // [N]
     const int* pos = p.pos + (size_t)t * N * 2;
-    const double* inv_g = inv_ws + (size_t)t * N;
     for (int i = lane; i < N; i += kListCols) {
         v2i q; q[0] = pos[2 * i]; q[1] = pos[2 * i + 1];
         pl[i] = q;
         inv[i] = inv_g[i];
     }
     __syncthreads();
-    if (n >= N) return;
+    if (n >= N) return 0;
     const unsigned Tu = dist2_bound(p.radius[c]);
-    const size_t col = (size_t)t * N + n;
-    unsigned short* il = idx_out + col * cap;                    // 8-byte aligned (cap % 4 == 0)
-    float* wl = val_out + col * cap;                             // 16-byte aligned
     const v2i me = pl[n];
     const double sn = inv[n];
     int cnt = 0;
@@ -107,7 +101,22 @@ __global__ __launch_bounds__(kListCols) void expert_team_lists_kernel(const Sche
         const v4f z = {r == 1 ? w[3] : r == 2 ? w[2] : w[1], r == 1 ? 0.f : r == 2 ? w[3] : w[2], r == 3 ? w[3] : 0.f, 0.f};
         *reinterpret_cast<v4f*>(wl + (cnt & ~3)) = z;
     }
-    cnt_out[col] = cnt;
+    return cnt;
+}
+
+// Columns [tile * kListCols, ...) of step t.
+__global__ __launch_bounds__(kListCols) void expert_team_lists_kernel(const ScheduleArgs p, const double* inv_ws, int tiles,
+                                                                      int* cnt_out, unsigned short* idx_out,
+                                                                      float* val_out, int cap) {
+    extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
+    const int N = p.N, lane = threadIdx.x;
+    const int t = blockIdx.x / tiles, n = (blockIdx.x - t * tiles) * kListCols + lane;
+    const int c = schedule_case_of(p.case_start, p.C, t);
+    if (p.status[c] != 0) return;                                // (workgroup-uniform)
+    const size_t col = (size_t)t * N + n;
+    const int cnt = schedule_team_list_column(p, t, c, n, lane, inv_ws + (size_t)t * N, idx_out + col * cap,
+                                              val_out + col * cap, cap, gnnpp_smem);
+    if (n < N) cnt_out[col] = cnt;
 }
 
 struct TeamGatherArgs {

@@ -27,6 +27,7 @@
 #include "lsigf_team_train_kernel.hip"   // ... its training calls: lists of S^T, the forward that keeps the tap signals
 #include "rollout_team_lists_kernel.hip"   // the rollout's communication graph as the team filter's neighbour lists
 #include "expert_team_lists_kernel.hip"    // the expert schedules' graphs as capped neighbour lists, and the draw from them
+#include "schedule_draw_kernels.hip"       // a training batch straight from stored schedules: only the picked steps are built
 #include "train_encoder.hip"
 #include "train_ops.hip"
 #include "rollout_trace_kernels.hip"       // the rollout's trace: a record launch behind each move, no simulator kernel touched
@@ -827,6 +828,34 @@ int gnnpp_team_lists_gather(const int* cnt, const unsigned short* idx, const flo
     if (graphs_src <= 0 || !index || !team_lists_block_ok(lists, lists_bytes, B, N) || !capped_lists_ok(cnt, idx, val, cap, N))
         return GNNPP_ERR_ARG;
     return team_lists_gather_launch(cnt, idx, val, graphs_src, cap, index, B, lists, N, static_cast<hipStream_t>(stream));
+}
+
+size_t gnnpp_schedule_draw_workspace_bytes(int N, int B) {
+    if (N <= 0 || N > GNNPP_ROLLOUT_MAX_TEAM || B <= 0) return 0;
+    return schedule_draw_workspace_bytes(N, B);
+}
+
+// pointers, alignments and sizes first (GNNPP_ERR_ARG), then the supported range: nothing is enqueued on an error
+int gnnpp_schedule_draw(const gnnpp_schedules* s, const int* index, int B, float* obs, float* target, float* S, void* lists,
+                        size_t lists_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!s || !s->grid || !s->goal || !s->pos || !s->case_start || !s->radius || !s->status || !index || !obs || !target ||
+        !workspace || (S != nullptr) == (lists != nullptr))
+        return GNNPP_ERR_ARG;
+    if (s->C <= 0 || s->T_total <= 0 || s->C > s->T_total || s->N <= 0 || s->N > GNNPP_ROLLOUT_MAX_TEAM || s->H <= 0 ||
+        s->W <= 0 || B <= 0)
+        return GNNPP_ERR_ARG;
+    const uintptr_t words = reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(obs) |
+                            reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(S) |
+                            reinterpret_cast<uintptr_t>(s->goal) | reinterpret_cast<uintptr_t>(s->pos) |
+                            reinterpret_cast<uintptr_t>(s->case_start) | reinterpret_cast<uintptr_t>(s->status);
+    const uintptr_t doubles = reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(s->radius);
+    if ((words & 3) || (doubles & 7) || workspace_bytes < schedule_draw_workspace_bytes(s->N, B) ||
+        (lists && !team_lists_block_ok(lists, lists_bytes, B, s->N)))
+        return GNNPP_ERR_ARG;
+    if (s->N < 2 || !schedule_draw_fits(s->N, s->H, s->W, B)) return GNNPP_ERR_UNSUPPORTED;
+    gnnpp_schedules a = *s;                              // the batch's tensors in the place of the set's
+    a.obs = obs; a.target = target; a.S = S; a.S64 = nullptr;
+    return schedule_draw_launch(a, index, B, lists, static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 size_t gnnpp_mapf_workspace_bytes(int C, int R, int H, int T_max) {

@@ -13,6 +13,10 @@ The prioritized expert itself runs on the device too (mapf.py): solve_failures p
 and samples_from_solutions turns the solved ones into samples (team=True: teams of any size up to MAX_TEAM).
 Large teams can keep their graphs as neighbour lists from the schedule to the training step, with no [N,N] matrix in
 between: samples_from_schedules_team(graph='lists') -> SampleListPool.draw -> training.train_step_lists.
+The pools above keep every step's tensors.  SchedulePool keeps the schedules and builds each batch when it is drawn
+(gnnpp_schedule_draw, csrc/schedule_draw_kernels.hip), the same bytes from a hundredth of the memory:
+
+    ... -> mapf.solve -> SchedulePool.append_solutions -> SchedulePool.draw -> train_step
 
 The schedule's communication radius is NOT the rollout's: it starts at commR (5 in both transformers), grows by
 * 1.1 until every step of the case is connected, and the final radius builds every step's graph.
@@ -544,3 +548,234 @@ class SampleListPool:
                                                     lists.numel(), N, _native.stream_ptr(dev)),
                           'gnnpp_team_lists_gather')
         return self.input.index_select(0, idx), self.target.index_select(0, idx), lists
+
+
+class SchedulePool:
+    """The sample pool that stores SCHEDULES: device-resident expert schedules of ONE team size on ONE map size, and every
+    batch is built when it is drawn (gnnpp_schedule_draw, include/gnnpp_schedule_draw.h: three launches, only the picked
+    steps).  Per step it keeps the positions (8 bytes per agent) and the step's largest degree; per case the first step,
+    the goals, the radius its graphs are built with, the plan's status and the map -- once for the whole pool when it is
+    constructed with grid= [H,W].  Nothing observation-shaped, [steps,N,N] or lists-shaped exists between the schedule
+    and the batch: 10 agents on a 20 x 20 map are 84 bytes per step here against 15 KB in a SamplePool.
+    The batches are byte for byte those of SamplePool / SampleListPool fed with samples_from_schedules_team of the same
+    cases, and the index rule of draw() is theirs, so the same generator state picks the same steps: a drop-in in front of
+    training.train_step, GraphedTrainStep.__call__ and training.train_step_lists(..., symmetric=True).
+    Arrays grow by capacity doubling: an append copies the new cases' compact arrays, and the old ones only when a
+    capacity is exceeded.  A HIP graph captured over enqueue_draw holds the arrays' addresses and the step count of its
+    capture: re-capture after an append (reserve() ahead keeps the addresses)."""
+
+    def __init__(self, device='cuda', grid=None):
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise _native.GnnppError('SchedulePool needs a HIP device (no CPU fallback)')
+        self.steps = self.cases = 0
+        self.N = self.H = self.W = None
+        self.max_degree = 0
+        self.pos = self.step_deg = self.case_start = self.goal = self.radius = self.status = self.grids = None
+        self.grid = None
+        if grid is not None:
+            g = torch.as_tensor(np.asarray(grid) if not torch.is_tensor(grid) else grid)
+            if g.dim() != 2:
+                raise _native.GnnppError('SchedulePool(grid=...): one shared map [H,W]')
+            self.grid = g.to(torch.uint8).contiguous().to(self.device)
+            self.H, self.W = int(g.shape[0]), int(g.shape[1])
+
+    def __len__(self):
+        return self.steps
+
+    def _tensors(self):
+        return [t for t in (self.pos, self.step_deg, self.case_start, self.goal, self.radius, self.status, self.grids,
+                            self.grid) if t is not None]
+
+    @property
+    def nbytes(self):
+        """Bytes allocated (capacities, not fill levels)."""
+        return sum(t.numel() * t.element_size() for t in self._tensors())
+
+    def reserve(self, steps, cases):
+        """Capacity for `steps` steps and `cases` cases in all (a pool that knows its team and map size: after the first
+        append); never shrinks."""
+        if self.N is None:
+            raise _native.GnnppError('reserve() after the first append: the pool takes its team size from it')
+        self._reserve(int(steps), int(cases))
+
+    def _reserve(self, steps, cases):
+        dev, N = self.device, self.N
+
+        def grown(old, used, need, shape, dtype):
+            have = 0 if old is None else int(old.shape[0])
+            if need <= have:
+                return old
+            new = torch.empty((max(2 * have, need),) + shape, dtype=dtype, device=dev)
+            if used:
+                new[:used].copy_(old[:used])
+            return new
+        self.pos = grown(self.pos, self.steps, steps, (N, 2), torch.int32)
+        self.step_deg = grown(self.step_deg, self.steps, steps, (), torch.int32)
+        self.goal = grown(self.goal, self.cases, cases, (N, 2), torch.int32)
+        self.radius = grown(self.radius, self.cases, cases, (), torch.float64)
+        self.status = grown(self.status, self.cases, cases, (), torch.int32)
+        if self.grid is None:
+            self.grids = grown(self.grids, self.cases, cases, (self.H, self.W), torch.uint8)
+        fresh = self.case_start is None
+        self.case_start = grown(self.case_start, 0 if fresh else self.cases + 1, cases + 1, (), torch.int32)
+        if fresh:
+            self.case_start[0] = 0
+
+    def append(self, grids, goals, schedules, commR=5.0, audit=False):
+        """The arguments of samples_from_schedules_team (grids may be None in a pool constructed with grid=).  Runs
+        gnnpp_schedule_team_plan on the NEW cases only and keeps its radius, status and step_deg; the plan's targets and
+        workspace are transient.  A flagged case raises what the sample builders raise, naming the case, and leaves the
+        pool as it was.  audit=True: the schedules go through mapf.audit first.  One host read (the plan's flags)."""
+        dev = self.device
+        L = _native.lib()
+        goal = torch.as_tensor(np.asarray(goals) if not torch.is_tensor(goals) else goals).to(torch.int32)
+        C = len(schedules)
+        if C == 0 or goal.dim() != 3 or goal.shape[0] != C or goal.shape[2] != 2:
+            raise _native.GnnppError('goals must be [C,N,2] with one entry per schedule (C = %d)' % C)
+        N = int(goal.shape[1])
+        if not 2 <= N <= MAX_TEAM:
+            raise _native.GnnppError('teams of 2 to %d agents (got %d)' % (MAX_TEAM, N))
+        if grids is None:
+            if self.grid is None:
+                raise _native.GnnppError('grids=None needs a pool constructed with grid=')
+            g = self.grid
+        else:
+            g = torch.as_tensor(np.asarray(grids) if not torch.is_tensor(grids) else grids)
+            if g.dim() not in (2, 3) or (g.dim() == 3 and g.shape[0] != C):
+                raise _native.GnnppError('grids must be [H,W] or [C,H,W]')
+            g = g.to(torch.uint8).contiguous().to(dev)
+            if self.grid is not None and (g.dim() != 2 or g.shape != self.grid.shape or not torch.equal(g, self.grid)):
+                raise _native.GnnppError('this SchedulePool holds ONE shared map (grid=): append its cases with that map, '
+                                         'or with grids=None')
+        H, W = int(g.shape[-2]), int(g.shape[-1])
+        if self.N is not None and N != self.N or self.H is not None and (H, W) != (self.H, self.W):
+            raise _native.GnnppError('a SchedulePool holds one team size and one map size (%s agents on %s x %s)'
+                                     % (self.N, self.H, self.W))
+        sched = [torch.as_tensor(np.asarray(s) if not torch.is_tensor(s) else s).to(torch.int32) for s in schedules]
+        for c, s in enumerate(sched):
+            if s.dim() != 3 or s.shape[0] < 1 or tuple(s.shape[1:]) != (N, 2):
+                raise _native.GnnppError('schedule %d must be [T,%d,2] with T >= 1 (got %s)' % (c, N, tuple(s.shape)))
+        if audit:
+            from . import mapf
+            _raise_if_audit_flagged(mapf.audit(g, None, goal, sched, dev), C)
+        bounds = [0]
+        for s in sched:
+            bounds.append(bounds[-1] + int(s.shape[0]))
+        T = bounds[-1]
+        goal = goal.contiguous().to(dev)
+        pos = torch.cat(sched, 0).contiguous().to(dev)
+        case_start = torch.tensor(bounds, dtype=torch.int32).to(dev)
+        flags = torch.empty(C + T, dtype=torch.int32, device=dev)        # status | step_deg: one read for both
+        plan = ScheduleSamples(
+            input=None, GSO=None, GSO64=None, target=torch.empty(T, N, 5, dtype=torch.float32, device=dev),
+            radius=torch.empty(C, dtype=torch.float64, device=dev), growth=torch.empty(C, dtype=torch.int32, device=dev),
+            status=flags[:C], step_deg=flags[C:], step_growth=torch.empty(T, dtype=torch.int32, device=dev),
+            workspace=torch.empty(L.gnnpp_schedule_team_workspace_bytes(N, T), dtype=torch.uint8, device=dev))
+        enqueue_schedule_team_plan(g, goal, pos, case_start, plan, commR)
+        host = flags.cpu()
+        _raise_if_flagged(host[:C], C)                  # (the pool is untouched up to here)
+        if self.N is None:
+            self.N, self.H, self.W = N, H, W
+        T0, C0 = self.steps, self.cases
+        self._reserve(T0 + T, C0 + C)
+        self.pos[T0:T0 + T].copy_(pos)
+        self.step_deg[T0:T0 + T].copy_(plan.step_deg)
+        self.goal[C0:C0 + C].copy_(goal)
+        self.radius[C0:C0 + C].copy_(plan.radius)
+        self.status[C0:C0 + C].copy_(plan.status)
+        self.case_start[C0 + 1:C0 + C + 1].copy_(case_start[1:] + T0)
+        if self.grid is None:
+            self.grids[C0:C0 + C].copy_(g if g.dim() == 3 else g.unsqueeze(0).expand(C, H, W))
+        self.steps, self.cases = T0 + T, C0 + C
+        self.max_degree = max(self.max_degree, int(host[C:].max()))
+
+    def append_solutions(self, solutions, grids, goals, commR=5.0, audit=False):
+        """The solved cases of a mapf.Solutions, selected as samples_from_solutions selects them (status 0, the schedule up
+        to the case's makespan); grids [C,H,W] or [H,W] and goals [C,N,2] as solve() was given them.  Returns their case
+        ids (numpy int64 [S]); with none solved the pool is unchanged."""
+        status = solutions.status.cpu().numpy()
+        ids = np.nonzero(status == 0)[0]
+        if len(ids) == 0:
+            return ids
+        dev = solutions.status.device
+        makespan = solutions.makespan.cpu().numpy()
+        idx = torch.as_tensor(ids, device=dev)
+        g = grids
+        if g is not None:
+            g = g if torch.is_tensor(g) else torch.as_tensor(np.asarray(g))
+            g = g.to(dev).index_select(0, idx) if g.dim() == 3 else g
+        gl = (goals if torch.is_tensor(goals) else torch.as_tensor(np.asarray(goals))).to(dev).index_select(0, idx)
+        self.append(g, gl, [solutions.schedules[c, :int(makespan[c]) + 1] for c in ids], commR=commR, audit=audit)
+        return ids
+
+    def draw_buffers(self, batch_size, graph='dense'):
+        """Caller-owned tensors for enqueue_draw: a ScheduleSamples with input [B,N,3,11,11], target [B,N,5], workspace,
+        and GSO [B,N,N] (graph='dense') or lists, a standard block of B graphs (graph='lists')."""
+        if graph not in ('dense', 'lists'):
+            raise _native.GnnppError("unknown graph %r (one of ['dense', 'lists'])" % (graph,))
+        if self.N is None:
+            raise _native.GnnppError('the pool is empty')
+        L, dev, B, N = _native.lib(), self.device, int(batch_size), self.N
+        out = ScheduleSamples(input=torch.empty(B, N, 3, 11, 11, dtype=torch.float32, device=dev),
+                              target=torch.empty(B, N, 5, dtype=torch.float32, device=dev), GSO=None, lists=None,
+                              workspace=torch.empty(L.gnnpp_schedule_draw_workspace_bytes(N, B), dtype=torch.uint8,
+                                                    device=dev))
+        if graph == 'dense':
+            out.GSO = torch.empty(B, N, N, dtype=torch.float32, device=dev)
+        else:
+            out.lists = torch.empty(L.gnnpp_team_lists_bytes(B, N), dtype=torch.uint8, device=dev)
+        return out
+
+    def enqueue_draw(self, index, out, graph='dense'):
+        """gnnpp_schedule_draw alone, on torch's current stream: index [B] int32 on the pool's device, out as
+        draw_buffers(B, graph) makes it (contiguous; out.GSO for 'dense', out.lists for 'lists').  No allocation, no host
+        read, capturable in a HIP graph; the contents of `index` may change between replays."""
+        if graph not in ('dense', 'lists'):
+            raise _native.GnnppError("unknown graph %r (one of ['dense', 'lists'])" % (graph,))
+        if self.steps == 0:
+            raise _native.GnnppError('the pool is empty')
+        B, N = int(index.numel()), self.N
+        graph_out = out.GSO if graph == 'dense' else out.lists
+        dev = _native.require_gpu(index, out.input, out.target, graph_out, out.workspace)
+        if (index.dtype is not torch.int32 or not index.is_contiguous() or tuple(out.input.shape) != (B, N, 3, 11, 11)
+                or tuple(out.target.shape) != (B, N, 5) or out.input.dtype is not torch.float32
+                or out.target.dtype is not torch.float32 or not (out.input.is_contiguous() and out.target.is_contiguous())
+                or not graph_out.is_contiguous()
+                or (graph == 'dense' and (tuple(graph_out.shape) != (B, N, N) or graph_out.dtype is not torch.float32))):
+            raise _native.GnnppError('a draw of %d steps of %d agents: index [B] int32, contiguous input [B,N,3,11,11], '
+                                     'target [B,N,5] and GSO [B,N,N] float32 (or a lists block)' % (B, N))
+        s = _native.ScheduleStruct()
+        grid = self.grid if self.grid is not None else self.grids
+        s.grid, s.grid_batched, s.goal, s.pos = grid.data_ptr(), int(self.grid is None), self.goal.data_ptr(), self.pos.data_ptr()
+        s.case_start, s.C, s.N, s.H, s.W, s.T_total = self.case_start.data_ptr(), self.cases, N, self.H, self.W, self.steps
+        s.radius, s.status = self.radius.data_ptr(), self.status.data_ptr()
+        ws = out.workspace
+        dense = graph == 'dense'
+        with _native.device_guard(dev):
+            _native.check(_native.lib().gnnpp_schedule_draw(
+                ctypes.byref(s), index.data_ptr(), B, out.input.data_ptr(), out.target.data_ptr(),
+                graph_out.data_ptr() if dense else None, None if dense else graph_out.data_ptr(),
+                0 if dense else graph_out.numel() * graph_out.element_size(), ws.data_ptr(), ws.numel() * ws.element_size(),
+                _native.stream_ptr(dev)), 'gnnpp_schedule_draw')
+
+    def draw(self, batch_size, generator=None, graph='dense'):
+        """(batch_input [B,N,3,11,11], batch_target [B,N,5], batch_GSO [B,N,N]) -- graph='lists': (batch_input,
+        batch_target, lists block of B graphs) -- of batch_size steps drawn as SamplePool.draw draws them: uniformly
+        without replacement, with replacement when the pool is smaller.  generator: a torch.Generator of the pool's device,
+        or of the CPU."""
+        n = len(self)
+        if n == 0:
+            raise _native.GnnppError('the pool is empty')
+        gdev = generator.device if generator is not None else self.device
+        if batch_size <= n:
+            idx = torch.randperm(n, generator=generator, device=gdev)[:batch_size]
+        else:
+            idx = torch.randint(n, (batch_size,), generator=generator, device=gdev)
+        return self.gather(idx, graph)
+
+    def gather(self, idx, graph='dense'):
+        index = torch.as_tensor(idx, dtype=torch.long).to(self.device).to(torch.int32).contiguous()
+        out = self.draw_buffers(int(index.numel()), graph)
+        self.enqueue_draw(index, out, graph)
+        return out.input, out.target, out.GSO if graph == 'dense' else out.lists
