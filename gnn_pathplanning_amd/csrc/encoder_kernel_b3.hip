@@ -307,7 +307,9 @@ __device__ __forceinline__ void b3_conv_preload(const WStreamB& ws, v4f (&ring)[
 //        tiles wave, wave + 4, ..: 4 / 4 / 4 / 4 instead of 7 / 6 / 6 / 6 positions;
 //   L2 (32 -> 64 @ 5x5, the 4x4 the pool reads)  one tile PER AGENT whose 16 columns are the 16 output positions, the four
 //        positions of a pool window in four adjacent lanes (the 2x2 max is two quad_perm DPP steps): N tiles x 9 taps
-//        instead of 16 position tiles x 7.56 (N = 10: 90 instead of 121 tile-taps).
+//        instead of 16 position tiles x 7.56 (N = 10: 90 instead of 121 tile-taps -- 84 where the team size is a compile-time
+//        constant: cp_layer2_fixed orders the columns by image ROWS, four agents to a tile, and drops the row-0 tiles under
+//        the dy = -1 taps; per 10-agent graph 7 560 -> 7 308 (L1) -> 7 164 MFMAs).
 // A tap is then a per-lane LDS address, not a compile-time fragment: a column whose tap leaves the image reads a cell
 // of zeros (its products are exact zeros: acc + 0 == acc, so every output keeps the value -- and the bits -- of the
 // agents-on-columns schedule, whose first reachable tap starts from a zero accumulator too).  L0 keeps agents on its
@@ -322,7 +324,8 @@ __device__ __forceinline__ void b3_conv_preload(const WStreamB& ws, v4f (&ring)[
 //   L2 input (L1's output)  agent n's 25 cells: slot (4 (y & 3) + (x & 3) + o(n)) & 15, o(n) = 4 (n & 3) + (n >> 2), in row
 //        n (y, x < 4) | 12 + (n >> 2) (y = 4) | 15 + (n & 3) (x = 4) | 19 (y = x = 4); row 20 = zeros.  Any 4x4 window of
 //        one agent's 5x5 image lies in 16 distinct slots (conflict-free tap reads), and the rows are shared between
-//        agents without collisions (the rotation o(n) interleaves them): 20 rows hold 12 x 25 cells.
+//        agents without collisions (the rotation o(n) interleaves them): 20 rows hold 12 x 25 cells.  (A compile-time team of
+//        ten moves agent 9 to o = 10: cp_l2in_rot.)
 constexpr int kCpMaxAgents = 12;
 constexpr int kCpRow = 3 * kB3Frag;                        // 3 072
 constexpr int kCpL1Tiles = 5;                              // column tiles of L1 per wave: ceil(ceil(25 * 12 / 16) / 4)
@@ -400,14 +403,15 @@ struct CpL1Sched {
     int tap[9 * NA + 1], tile[9 * NA + 1];
     int first_tap[NA > 0 ? NA : 1], last_tile[9], live_tiles[9];
 };
-template <int NFIX, int W, int NA>
-__host__ __device__ constexpr CpL1Sched<NA> cp_l1_sched() {
+// (LIVE(tap, i): unit (tap, the wave's i-th tile) is part of the sequence -- L2's constant-N form builds its own from this too)
+template <int NA, class Live>
+__host__ __device__ constexpr CpL1Sched<NA> cp_unit_sched(Live is_live) {
     CpL1Sched<NA> s{};
     for (int i = 0; i < NA; ++i) s.first_tap[i] = -1;
     for (int tap = 0; tap < 9; ++tap) {
         s.last_tile[tap] = -1;
         for (int i = 0; i < NA; ++i) {
-            const bool live = W < 0 || !cp_l1_unit_empty_n(NFIX, tap, W + 4 * i);
+            const bool live = is_live(tap, i);
             s.ord[tap][i] = live ? s.n : -1;
             if (!live) continue;
             s.tap[s.n] = tap;
@@ -419,6 +423,14 @@ __host__ __device__ constexpr CpL1Sched<NA> cp_l1_sched() {
         }
     }
     return s;
+}
+struct CpL1Live {
+    int N, W;
+    __host__ __device__ constexpr bool operator()(int tap, int i) const { return W < 0 || !cp_l1_unit_empty_n(N, tap, W + 4 * i); }
+};
+template <int NFIX, int W, int NA>
+__host__ __device__ constexpr CpL1Sched<NA> cp_l1_sched() {
+    return cp_unit_sched<NA>(CpL1Live{NFIX, W});
 }
 template <int NFIX, int W, int NA>
 struct CpL1S {
@@ -435,12 +447,49 @@ __host__ __device__ constexpr bool cp_l1_sched_ok() {
         if (s.first_tap[i] < 0) return false;
     return true;
 }
+// slot rotation o(n) of agent n in the L2-input layout.  The constant-team-size form of L2 (cp_layer2_fixed) reads agents 8
+// and 9 from ONE tile, two image rows of each: 4 (yy & 3) + o must then differ by 8 between the two agents, so agent 9 sits at
+// 10 (the rotation agent 10 would have -- a team of ten has none) instead of 6.  Row sharing is untouched: row 14 (y = 4)
+// holds agent 8 in slots 2 .. 5 and agent 9 in 10 .. 13, row 16 (x = 4) agents 1, 5, 9 at 4 k + {4, 5, 10}, row 19 ten
+// distinct rotations (cp_l2f_layout_ok below).
+__host__ __device__ constexpr int cp_l2in_rot(int NFIX, int n) {
+    return NFIX == 10 && n == 9 ? 10 : 4 * (n & 3) + (n >> 2);
+}
+// slot and row of cell (y, x) of agent n with rotation o (the slot rule also serves a source cell outside the image, y or
+// x = -1, which reads its OWN slot of the zero row)
+__host__ __device__ constexpr int cp_l2in_slot(int y, int x, int o) { return (4 * (y & 3) + (x & 3) + o) & 15; }
+__host__ __device__ constexpr int cp_l2in_row(int y, int x, int n) {
+    return y == 4 ? (x == 4 ? 19 : 12 + (n >> 2)) : (x == 4 ? 15 + (n & 3) : n);
+}
 // byte offset of cell (y, x) of agent n inside a (plane, q) block of the L2-input layout
-__device__ __forceinline__ int cp_l2in_cell(int y, int x, int n) {
-    const int o = 4 * (n & 3) + (n >> 2);
+// (cp_l2in_rot / cp_l2in_slot / cp_l2in_row written out: as calls the nested choices became divergent branches in front of
+// L1's switch, and tools/check_ring_isa.py then no longer tells the switch's arms apart.  MUL: the device's 24-bit multiply,
+// or a plain one for the static_assert below that holds this arithmetic to those three functions.)
+template <int NFIX, class Mul>
+__host__ __device__ __forceinline__ constexpr int cp_l2in_cell_as(int y, int x, int n, Mul mul) {
+    int o = 4 * (n & 3) + (n >> 2);
+    if constexpr (NFIX == 10) o += n == 9 ? 4 : 0;
     const int slot = (4 * (y & 3) + (x & 3) + o) & 15;
     const int row = y == 4 ? (x == 4 ? 19 : 12 + (n >> 2)) : (x == 4 ? 15 + (n & 3) : n);
-    return __mul24(row, kCpRow) + slot * 16;
+    return mul(row, kCpRow) + slot * 16;
+}
+struct CpMulPlain {
+    __host__ __device__ constexpr int operator()(int a, int b) const { return a * b; }
+};
+template <int NFIX>
+__host__ __device__ constexpr bool cp_l2in_cell_is_the_rule() {
+    for (int n = 0; n < kCpMaxAgents; ++n)
+        for (int y = 0; y < 5; ++y)
+            for (int x = 0; x < 5; ++x)
+                if (cp_l2in_cell_as<NFIX>(y, x, n, CpMulPlain{}) !=
+                    cp_l2in_row(y, x, n) * kCpRow + cp_l2in_slot(y, x, cp_l2in_rot(NFIX, n)) * 16)
+                    return false;
+    return true;
+}
+static_assert(cp_l2in_cell_is_the_rule<0>() && cp_l2in_cell_is_the_rule<10>(), "cp_l2in_cell is cp_l2in_row / _slot / _rot");
+template <int NFIX = 0>
+__device__ __forceinline__ int cp_l2in_cell(int y, int x, int n) {
+    return cp_l2in_cell_as<NFIX>(y, x, n, [](int a, int b) { return __mul24(a, b); });
 }
 // L0's pooled window `win` (three plane fragments of lane (q, agent a)): fragment win of R, or -- CP -- cell win * N + a of
 // the L1-input layout (lanes beyond the graph's agents hold nothing)
@@ -925,7 +974,7 @@ __device__ __forceinline__ void cp_layer1(const WStreamB& ws, v4f (&ring)[kRingH
         unsigned f = (y == 0 ? 1u : 0u) | (y == 4 ? 2u : 0u) | (x == 0 ? 4u : 0u) | (x == 4 ? 8u : 0u);
         if (c >= g.ncol) f = 15u;                                   // no such column: every shifted tap reads zeros
         ln.fl |= f << (4 * i);
-        l2dst[i] = c < g.ncol ? cp_l2in_cell(y, x, n) + q * 256 : -1;
+        l2dst[i] = c < g.ncol ? cp_l2in_cell<NFIX>(y, x, n) + q * 256 : -1;
     }
     ln.zaddr = g.l1in + g.T1 * kCpRow + q * 256;                    // the row of zeros (slot 0 of this lane's q)
     ln.tile0 = g.l1in + wave * kCpRow + q * 256;
@@ -1067,9 +1116,240 @@ __device__ __forceinline__ void cp_layer2_main(const WStreamB& ws, v4f (&ring)[k
     }
 }
 
+// ---- L2 for a COMPILE-TIME team of kCpTeamFixed = 10 agents: a ROW-WISE column order -------------------------------------
+// With one agent's 16 positions on a tile no tile lies inside one image row and no (tap, tile) unit is all zeros, although 23
+// of every 144 (position, tap) products multiply the zero cell.  The 160 columns of ten agents in ROWS instead -- ten tiles:
+//   tile 2 y + g (y = 0 .. 3, g = 0, 1)   column j = agent 4 g + (j >> 2) at x = j & 3 of output row y;
+//   tile 8 + h (h = 0, 1)                 column j = agent 8 + ((j >> 2) & 1) at x = j & 3 of row 2 h + (j >> 3);
+// wave (mp, pair) keeps its two channel tiles and takes the four row tiles of g = pair plus tile 8 + pair (five tiles, as
+// before).  Under the three dy = -1 taps every lane of the tiles of row 0 reads the zero row: 6 of the 90 units, 144 of L2's
+// 2 160 MFMAs per graph, 42 units per wave instead of 45 -- the same units for both pairs, so one copy of the layer serves
+// all four waves.  The ring sees the steps of the run-time form (cp_layer1_main's rules: the wait in front of a tap's first
+// live unit, the refills on its last, tile 0's accumulators start at tap 3).
+// Addresses: a row tile's source row y + dy is a constant, so its address depends on (y + dy, dx) alone -- 15 per lane for
+// the 33 live units of the four row tiles -- plus 9 for the tail tile: 24 pinned registers instead of 45.  Reads stay
+// conflict-free: the four agents of a row tile are 4 g + aa with rotations 4 aa + g, so 4 ((yy & 3) + aa) + (xx & 3) + g takes
+// sixteen values over (aa, x); the tail tile is what cp_l2in_rot moves agent 9 for.
+// Pool: the y-pair of a window is two accumulator tiles of the SAME lane on the row tiles (a register-wise max) and lane ^ 8
+// on the tail tile; the x-pair is lane ^ 1 everywhere.  Each max is a reduce-scatter, so a row-tile lane ends with the two
+// channel pairs of its channel tile x & 1 (two conversions per tile pair, one 8-byte store per plane), a tail-tile lane with
+// one pair: five conversions per lane, as in the run-time form, and none repeated.
+static_assert(kCpTeamFixed == 10, "the row-wise order of L2 and cp_l2in_rot are written for ten agents");
+constexpr int kCpL2FTiles = 5;                                      // tiles of a wave
+struct CpL2Col { int n, y, x; };
+__host__ __device__ constexpr CpL2Col cp_l2f_col(int t, int j) {
+    if (t < 8) return CpL2Col{4 * (t & 1) + (j >> 2), t >> 1, j & 3};
+    return CpL2Col{8 + ((j >> 2) & 1), 2 * (t - 8) + (j >> 3), j & 3};
+}
+__host__ __device__ constexpr int cp_l2f_tile(int pair, int i) { return i < 4 ? 2 * i + pair : 8 + pair; }
+// the per-lane rule of cp_l2f_addr: the source cell (y + dy, x + dx) of a 4x4 output position leaves the 5x5 input upwards or
+// to the left only
+__host__ __device__ constexpr bool cp_l2f_lane_outside(int tap, int y, int x) { return y + tap / 3 - 1 < 0 || x + tap % 3 - 1 < 0; }
+__host__ __device__ constexpr bool cp_l2f_unit_empty(int tap, int t) {
+    for (int j = 0; j < 16; ++j)
+        if (!cp_l2f_lane_outside(tap, cp_l2f_col(t, j).y, cp_l2f_col(t, j).x)) return false;
+    return true;
+}
+__host__ __device__ constexpr int cp_l2f_empty_units() {
+    int cnt = 0;
+    for (int tap = 0; tap < 9; ++tap)
+        for (int t = 0; t < 10; ++t) cnt += cp_l2f_unit_empty(tap, t) ? 1 : 0;
+    return cnt;
+}
+// the order holds every (agent, y, x) once, both pairs drop the same units, and the sixteen lanes of every unit read sixteen
+// distinct slots; the 250 cells of the ten agents keep (row, slot) of their own
+__host__ __device__ constexpr bool cp_l2f_layout_ok() {
+    bool seen[160] = {};
+    for (int t = 0; t < 10; ++t)
+        for (int j = 0; j < 16; ++j) {
+            const CpL2Col c = cp_l2f_col(t, j);
+            if (c.n < 0 || c.n >= 10 || c.y < 0 || c.y > 3 || seen[(c.n * 4 + c.y) * 4 + c.x]) return false;
+            seen[(c.n * 4 + c.y) * 4 + c.x] = true;
+        }
+    for (int tap = 0; tap < 9; ++tap)
+        for (int i = 0; i < kCpL2FTiles; ++i) {
+            if (cp_l2f_unit_empty(tap, cp_l2f_tile(0, i)) != cp_l2f_unit_empty(tap, cp_l2f_tile(1, i))) return false;
+            for (int pair = 0; pair < 2; ++pair) {
+                unsigned slots = 0;
+                for (int j = 0; j < 16; ++j) {
+                    const CpL2Col c = cp_l2f_col(cp_l2f_tile(pair, i), j);
+                    slots |= 1u << cp_l2in_slot(c.y + tap / 3 - 1, c.x + tap % 3 - 1, cp_l2in_rot(kCpTeamFixed, c.n));
+                }
+                if (slots != 0xffffu) return false;
+            }
+        }
+    bool cell[20][16] = {};
+    for (int n = 0; n < 10; ++n)
+        for (int y = 0; y < 5; ++y)
+            for (int x = 0; x < 5; ++x) {
+                const int r = cp_l2in_row(y, x, n), s = cp_l2in_slot(y, x, cp_l2in_rot(kCpTeamFixed, n));
+                if (r < 0 || r >= 20 || cell[r][s]) return false;
+                cell[r][s] = true;
+            }
+    return true;
+}
+static_assert(cp_l2f_empty_units() == 6 && cp_l2f_unit_empty(0, 0) && cp_l2f_unit_empty(1, 0) && cp_l2f_unit_empty(2, 0) &&
+                  cp_l2f_unit_empty(0, 1) && cp_l2f_unit_empty(1, 1) && cp_l2f_unit_empty(2, 1),
+              "N = 10, row-wise order: the two tiles of output row 0 under the three dy = -1 taps");
+static_assert(cp_l2f_layout_ok(), "the row-wise order covers the team, reads without bank conflicts, cells do not collide");
+struct CpL2FLive {
+    __host__ __device__ constexpr bool operator()(int tap, int i) const { return !cp_l2f_unit_empty(tap, cp_l2f_tile(0, i)); }
+};
+struct CpL2FS {
+    static constexpr CpL1Sched<kCpL2FTiles> v = cp_unit_sched<kCpL2FTiles>(CpL2FLive{});
+};
+__host__ __device__ constexpr bool cp_l2f_sched_ok() {
+    constexpr CpL1Sched<kCpL2FTiles> s = cp_unit_sched<kCpL2FTiles>(CpL2FLive{});
+    for (int tap = 0; tap < 9; ++tap)
+        if (s.live_tiles[tap] < 2 || s.last_tile[tap] != kCpL2FTiles - 1) return false;
+    for (int i = 0; i < kCpL2FTiles; ++i)
+        if (s.first_tap[i] < 0) return false;
+    return s.n == 42;
+}
+static_assert(cp_l2f_sched_ok(), "42 units per wave; every tap keeps two units and ends on the tail tile, every tile starts");
+
+struct CpL2FLane {
+    int q256, x;
+    int n, o;                     // row tiles: agent 4 pair + (j >> 2) and its rotation
+    int ty, tn, to;               // tail tile: output row, agent, rotation
+};
+// LDS address of the planes of source cell (yy, xx) of agent n (rotation o); a cell outside the image is the lane's slot of
+// the zero row.  cp_l2in_row / cp_l2in_slot as masks, branch-free on purpose: see cp_l1_addr (yy is a constant on the row tiles)
+__device__ __forceinline__ int cp_l2f_addr(int q256, int yy, int xx, int n, int o) {
+    const int slot = (4 * (yy & 3) + (xx & 3) + o) & 15;
+    const int x4 = -(int)(xx == 4), y4 = -(int)(yy == 4), outside = -(int)((yy | xx) < 0);     // all ones / zero
+    const int bottom = 12 + (n >> 2);
+    int row = n ^ ((n ^ (15 + (n & 3))) & x4);                      // interior | right edge
+    row ^= (row ^ (bottom ^ ((bottom ^ 19) & x4))) & y4;            // bottom edge | corner
+    row ^= (row ^ 20) & outside;
+    return __mul24(row, kCpRow) + slot * 16 + q256;
+}
 template <int END>
-__device__ __forceinline__ void cp_layer2(const WStreamB& ws, v4f (&ring)[kRingH], char* smem, const float* sstab,
-                                          const CpGeom& g, int wave, int lane) {
+__device__ __forceinline__ void cp_layer2_fixed_main(const WStreamB& ws, v4f (&ring)[kRingH], const char* smem,
+                                                     const CpL2FLane& ln, bool stamp_lane, v4f (&acc)[kCpL2FTiles][2]) {
+    using S = CpL2FS;
+    constexpr int NA = kCpL2FTiles, NU = S::v.n;
+    v4f Bb[2][3];
+    int addr_r[15], addr_t[9];                                      // row tiles: [yy 0 .. 4][dx]; tail tile: [tap]
+    [&]<int... U>(std::integer_sequence<int, U...>) {
+        ((addr_r[U] = cp_l2f_addr(ln.q256, U / 3, ln.x + U % 3 - 1, ln.n, ln.o), cp_pin(addr_r[U])), ...);
+    }(std::make_integer_sequence<int, 15>{});
+    [&]<int... T>(std::integer_sequence<int, T...>) {
+        ((addr_t[T] = cp_l2f_addr(ln.q256, ln.ty + T / 3 - 1, ln.x + T % 3 - 1, ln.tn, ln.to), cp_pin(addr_t[T])), ...);
+    }(std::make_integer_sequence<int, 9>{});
+    auto unit_addr = [&](auto uc) -> int {
+        constexpr int u = decltype(uc)::value, tap = S::v.tap[u], i = S::v.tile[u];
+        if constexpr (i < 4) return addr_r[(i + tap / 3 - 1) * 3 + tap % 3];
+        else return addr_t[tap];
+    };
+    __builtin_amdgcn_sched_barrier(0);
+    GNNPP_STAMP(blockIdx.x, 15, stamp_lane);
+    cp_l2_load(smem, unit_addr(std::integral_constant<int, 0>{}), Bb[0]);
+    // (ordered refills in the last two steps: L3 takes its fragments one by one, its waits count loads in issue order)
+    b3_stream_steps_direct<END, kb_L2>(ws, ring, [&](auto itc, auto basec, auto&& refill) {
+        constexpr int tap = decltype(itc)::value, base = decltype(basec)::value;
+        constexpr bool ordered = tap >= 7;
+        auto unit = [&](auto ic) {
+            constexpr int i = decltype(ic)::value, u = S::v.ord[tap][i];
+            if constexpr (u >= 0) {
+                cp_unit_direct<base, tap == S::v.first_tap[i], i == S::v.last_tile[tap], ordered>(
+                    ring, Bb[u & 1], acc[i][0], acc[i][1],
+                    [&](int p) {
+                        if constexpr (u + 1 < NU)
+                            Bb[(u + 1) & 1][p] = *reinterpret_cast<const v4f*>(
+                                smem + unit_addr(std::integral_constant<int, (u + 1 < NU ? u + 1 : u)>{}) + p * kB3Frag);
+                    }, refill);
+            }
+        };
+        [&]<int... I>(std::integer_sequence<int, I...>) { (unit(std::integral_constant<int, I>{}), ...); }(
+            std::make_integer_sequence<int, NA>{});
+    }, std::make_integer_sequence<int, 9>{});
+    ring_mfma_fence();
+}
+template <int END>
+__device__ __forceinline__ void cp_layer2_fixed(const WStreamB& ws, v4f (&ring)[kRingH], char* smem, const float* sstab,
+                                                int wave, int lane) {
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    const int mp = wave & 1, pair = wave >> 1;
+    const int j = lane & 15, q = lane >> 4, x = j & 3;
+    CpL2FLane ln;
+    ln.q256 = q * 256;
+    ln.x = x;
+    ln.n = 4 * pair + (j >> 2);
+    ln.o = (j & 12) + pair;                                         // cp_l2in_rot of agents 0 .. 7: 4 (n & 3) + (n >> 2)
+    ln.ty = 2 * pair + (j >> 3);
+    ln.tn = 8 + ((j >> 2) & 1);
+    ln.to = 2 + 2 * (j & 4);                                        // cp_l2in_rot(10, 8) = 2, (10, 9) = 10
+    v4f acc[kCpL2FTiles][2];
+#pragma unroll
+    for (int i = 0; i < kCpL2FTiles; ++i) acc[i][0] = acc[i][1] = vzero();
+    cp_layer2_fixed_main<END>(ws, ring, smem, ln, pair == 0 && lane == 0, acc);
+    v4f sc[2], shf[2];
+    load_ss(sstab + EncLayout::kBssL2, 64, 2 * mp, q, sc[0], shf[0]);
+    load_ss(sstab + EncLayout::kBssL2, 64, 2 * mp + 1, q, sc[1], shf[1]);
+    // x-pair, partner lane ^ 1: even x keeps channel tile 0 (channel pairs 0, 1 of the fragment's four), odd x tile 1 (2, 3)
+    const bool odd = (x & 1) != 0, low = (j & 8) != 0;
+    auto max_x = [&](const v4f& v0, const v4f& v1) {
+        v4f keep;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) keep[c] = fmaxf(odd ? v1[c] : v0[c], quad_xor1(odd ? v0[c] : v1[c]));
+        return keep;
+    };
+    v4f pooled[2];                                                  // window row Y of the row tiles
+#pragma unroll
+    for (int Y = 0; Y < 2; ++Y) {
+        v4f m[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const v4f a = vfma(acc[2 * Y][t], sc[t], shf[t]), b = vfma(acc[2 * Y + 1][t], sc[t], shf[t]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) m[t][c] = fmaxf(a[c], b[c]);                    // the y-pair: two tiles of this lane
+        }
+        pooled[Y] = max_x(m[0], m[1]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) pooled[Y][c] = fmaxf(pooled[Y][c], 0.f);            // + ReLU (commutes with the max)
+    }
+    // tail tile: the y-pair is lane ^ 8 -- the upper row keeps registers 0, 1 (the even pair of its channel tile), the lower 2, 3
+    float tail[2];
+    {
+        const v4f keep = max_x(vfma(acc[4][0], sc[0], shf[0]), vfma(acc[4][1], sc[1], shf[1]));
+        const float k0 = low ? keep[2] : keep[0], k1 = low ? keep[3] : keep[1];
+        const float s0 = low ? keep[0] : keep[2], s1 = low ? keep[1] : keep[3];
+        tail[0] = fmaxf(fmaxf(k0, __shfl_xor(s0, 8)), 0.f);
+        tail[1] = fmaxf(fmaxf(k1, __shfl_xor(s1, 8)), 0.f);
+    }
+    __syncthreads();                                               // everyone is done reading L1's output
+    // fragment (window w, block mp, plane) of L3's input, lane slot (q, agent n), dword = channel pair: the bytes of cp_layer2
+    char* const frag = smem + kB3L2out + mp * 3 * kB3Frag + q * 256;
+#pragma unroll
+    for (int Y = 0; Y < 2; ++Y) {
+        unsigned h[2], m[2], l[2];
+        b3_split2(pooled[Y][0], pooled[Y][1], h[0], m[0], l[0]);
+        b3_split2(pooled[Y][2], pooled[Y][3], h[1], m[1], l[1]);
+        char* const dst = frag + (2 * Y + (x >> 1)) * 6 * kB3Frag + ln.n * 16 + (x & 1) * 8;
+        *reinterpret_cast<v2u*>(dst) = v2u{h[0], h[1]};
+        *reinterpret_cast<v2u*>(dst + kB3Frag) = v2u{m[0], m[1]};
+        *reinterpret_cast<v2u*>(dst + 2 * kB3Frag) = v2u{l[0], l[1]};
+    }
+    {
+        unsigned h, m, l;
+        b3_split2(tail[0], tail[1], h, m, l);
+        char* const dst = frag + (2 * pair + (x >> 1)) * 6 * kB3Frag + ln.tn * 16 + (2 * (x & 1) + (j >> 3)) * 4;
+        *reinterpret_cast<unsigned*>(dst) = h;
+        *reinterpret_cast<unsigned*>(dst + kB3Frag) = m;
+        *reinterpret_cast<unsigned*>(dst + 2 * kB3Frag) = l;
+    }
+    // the lane slots of agents the graph does not have: zeros, as in cp_layer2
+    if (j >= kCpTeamFixed) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            *reinterpret_cast<v4f*>(smem + kB3L2out + (wave + 4 * k) * kB3Frag + lane * 16) = vzero();
+    }
+}
+
+template <int END>
+__device__ __forceinline__ void cp_layer2_any(const WStreamB& ws, v4f (&ring)[kRingH], char* smem, const float* sstab,
+                                              const CpGeom& g, int wave, int lane) {
     constexpr int NT = kCpL2Tiles;
     const int mp = wave & 1, pair = wave >> 1;
     const int na = min(max((g.N - pair + 1) >> 1, 0), NT);         // agents of this wave (wave-uniform)
@@ -1138,6 +1418,14 @@ __device__ __forceinline__ void cp_layer2(const WStreamB& ws, v4f (&ring)[kRingH
         for (int k = 0; k < 6; ++k)
             *reinterpret_cast<v4f*>(smem + kB3L2out + (wave + 4 * k) * kB3Frag + lane * 16) = vzero();
     }
+}
+// NFIX = 0: any team size at run time; NFIX = kCpTeamFixed: the row-wise order (the launcher's rule, as for cp_layer1)
+template <int END, int NFIX = 0>
+__device__ __forceinline__ void cp_layer2(const WStreamB& ws, v4f (&ring)[kRingH], char* smem, const float* sstab,
+                                          const CpGeom& g, int wave, int lane) {
+    static_assert(NFIX == 0 || NFIX == kCpTeamFixed, "one constant team size");
+    if constexpr (NFIX != 0) cp_layer2_fixed<END>(ws, ring, smem, sstab, wave, lane);
+    else cp_layer2_any<END>(ws, ring, smem, sstab, g, wave, lane);
 }
 
 template <bool FUSED, int KT, bool CP = false, int NFIX = 0>
@@ -1451,7 +1739,7 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
 
     // ---- L2: 32 -> 64 @ 5x5 (the 4x4 the pool reads), pool -> [4][kb 2], in place (front of R) --------
     if constexpr (CP) {
-        cp_layer2<END>(ws, ring, gnnpp_smem, sstab, geom, wave, lane);
+        cp_layer2<END, NFIX>(ws, ring, gnnpp_smem, sstab, geom, wave, lane);
     } else {
         const int mp = wave & 1, pair = wave >> 1;         // channel tiles 2 mp, 2 mp + 1 = block mp
         v4f acc[8][2];                                    // first touched by a zero-source MFMA (b3_mfma_chunk)
@@ -1732,7 +2020,8 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
 
 std::atomic<int> g_policy_column_packing{1};   // GNNPP_TUNE_POLICY_CP: 0 = agents on the MFMA columns for every team size
 // 1 (default): a team of kCpTeamFixed agents runs the instantiation whose team size is a constant; 0: the run-time-N
-// packed form, as every other team size (same logits to the bit: the dropped units add exact zeros).  A key of the
+// packed form OF BOTH packed layers, as every other team size (same logits to the bit: the dropped units add exact zeros,
+// the row-wise order of L2 sums every output's products in the same order and the max of a window is the same set).  A key of the
 // tests and the A/B tools, stated here and in _native.py rather than in include/gnnpp.h, like gnnpp_measure.h's.
 #define GNNPP_TUNE_POLICY_CP_TEAM 21
 std::atomic<int> g_policy_cp_team{1};
@@ -1792,7 +2081,7 @@ static int policy_launch_fused_b3_form(const float* obs, const float* packed, co
 
 // pt.filt_h2 must point at the b3 region of the filter pack.  Teams of <= kCpMaxAgents agents take the column-packed
 // front half (same logits to the bit: tests/test_gpu_parity.py::test_column_packed_policy_kernel_is_bit_identical), a
-// team of kCpTeamFixed agents its compile-time form (again the same bits: tests/test_gpu_policy_team10.py).
+// team of kCpTeamFixed agents its compile-time form (again the same bits: tests/test_gpu_policy_team10.py, test_gpu_policy_team10_l2.py).
 int policy_launch_fused_b3(const float* obs, const float* packed, const PolicyTail& pt, int K, hipStream_t st) {
     switch (K) {
         case 2: return policy_launch_fused_b3_form<2>(obs, packed, pt, st);
