@@ -31,6 +31,7 @@ CASEGEN_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_casegen.
 MAPF_AUDIT_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_audit.h')
 ROLLOUT_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_trace.h')
 SCHEDULE_DRAW_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_schedule_draw.h')
+ROLLOUT_STREAM_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_stream.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
@@ -98,7 +99,7 @@ def precision_code(p):
 def _sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [HEADER, MAPF_DISTANCE_HEADER, CASEGEN_HEADER,
                                                                           MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER,
-                                                                          SCHEDULE_DRAW_HEADER]
+                                                                          SCHEDULE_DRAW_HEADER, ROLLOUT_STREAM_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -263,6 +264,18 @@ class RolloutTraceStruct(ctypes.Structure):
                 ('T_cap', ctypes.c_int)]
 
 
+class RolloutStreamStruct(ctypes.Structure):
+    """struct gnnpp_rollout_stream (include/gnnpp_rollout_stream.h)."""
+    _fields_ = [('case_grid', ctypes.c_void_p), ('case_grid_batched', ctypes.c_int), ('case_start', ctypes.c_void_p),
+                ('case_goal', ctypes.c_void_p), ('case_maxstep', ctypes.c_void_p), ('C', ctypes.c_int),
+                ('commR', ctypes.c_double), ('cursor', ctypes.c_void_p), ('slot_case', ctypes.c_void_p),
+                ('slot_t0', ctypes.c_void_p), ('assign', ctypes.c_void_p), ('slot_grid', ctypes.c_void_p),
+                ('goal', ctypes.c_void_p), ('maxstep', ctypes.c_void_p), ('reached', ctypes.c_void_p),
+                ('start_step', ctypes.c_void_p), ('end_step', ctypes.c_void_p), ('pos', ctypes.c_void_p),
+                ('radius', ctypes.c_void_p), ('stats', ctypes.c_void_p), ('lived', ctypes.c_void_p),
+                ('slot', ctypes.c_void_p), ('t0', ctypes.c_void_p)]
+
+
 _vp, _ci, _cs, _ll, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_float
 _enc, _rollout = ctypes.POINTER(EncoderParams), ctypes.POINTER(RolloutStruct)
 _sched, _mapf, _gemm = ctypes.POINTER(ScheduleStruct), ctypes.POINTER(MapfStruct), ctypes.POINTER(GemmDesc)
@@ -362,6 +375,13 @@ SCHEDULE_DRAW_SIGNATURES = {
     'gnnpp_schedule_draw_workspace_bytes': (_cs, [_ci, _ci]),
     'gnnpp_schedule_draw': (_ci, [_sched, _vp, _ci, _vp, _vp, _vp, _vp, _cs, _vp, _cs, _vp]),
 }
+# include/gnnpp_rollout_stream.h, the companion header of streamed rollouts: a table of its own for the same reason
+# (tests/test_rollout_stream_abi.py)
+_rstream = ctypes.POINTER(RolloutStreamStruct)
+ROLLOUT_STREAM_SIGNATURES = {
+    'gnnpp_rollout_stream_begin': (_ci, [_rollout, _rstream, _vp]),
+    'gnnpp_rollout_stream_reseat': (_ci, [_rollout, _rstream, _ci, _vp]),
+}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
 MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 
@@ -369,11 +389,12 @@ MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
     build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES,
-    ROLLOUT_TRACE_SIGNATURES and SCHEDULE_DRAW_SIGNATURES; returns the library."""
+    ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES and ROLLOUT_STREAM_SIGNATURES; returns the library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
             list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + \
-            list(ROLLOUT_TRACE_SIGNATURES.items()) + list(SCHEDULE_DRAW_SIGNATURES.items()) + optional:
+            list(ROLLOUT_TRACE_SIGNATURES.items()) + list(SCHEDULE_DRAW_SIGNATURES.items()) + \
+            list(ROLLOUT_STREAM_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

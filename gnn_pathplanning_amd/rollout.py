@@ -193,6 +193,7 @@ class BatchedRollout:
         self.seed = int(seed) & 0xffffffff
         self.t = 0                                            # steps taken so far
         self._state_step = -1                                 # step whose positions obs / S describe
+        self._seated = False                                  # RolloutStream: every slot's step-0 state comes from its seat
         # teams up to this size run move -> graph -> observations as ONE launch (gnnpp_rollout_step, one workgroup
         # per episode); larger ones as move, then graph || observations in a second launch (gnnpp_rollout_gso_observe:
         # more workgroups than episodes).  Measured per simulator step: N = 10 16.1 (one launch) vs 17.3 us,
@@ -369,7 +370,7 @@ class BatchedRollout:
         if self.graph == 'lists':
             self._check_lists_model(model)
         self._check_room()
-        if self.t == 0:                                      # step 0 may grow the radius
+        if self.t == 0 and not self._seated:                 # step 0 may grow the radius
             self.observe()
             self.gso()
         elif self._state_step != self.t:                     # stale state: graph and observations side by side
@@ -453,6 +454,176 @@ class BatchedRollout:
                 'makespan': self.stats[:, 0].cpu(), 'flowtime': self.stats[:, 1].cpu(),
                 'end_step': self.end_step.cpu(), 'start_step': self.start_step.cpu(),
                 'positions': self.pos.cpu(), 'radius': self.radius.cpu(), 'done': self.done.bool().cpu()}
+
+
+class RolloutStream:
+    """C cases through `slots` resident episode slots: when a slot's episode ends, its result goes to a per-CASE table and
+    the next case of the queue is seated in that slot -- on the device, between two steps, with no host synchronisation
+    (include/gnnpp_rollout_stream.h).  BatchedRollout.run() steps a fixed batch until its slowest episode
+    ends and every frozen episode still costs its share of each launch; here a finished slot goes back to work.
+
+    grids [C,H,W] or [H,W]; starts, goals [C,N,2]; maxstep int or [C]: each case's own limit.  The stream owns a
+    BatchedRollout of min(slots, C) slots (`env`) and drives it on the rollout's own routes: the one-launch step for
+    N <= 16, move_and_observe up to 32 agents, move + gso_observe beyond.  The slots share one global step count; a case
+    seated at step count t0 runs its step k as global step t0 + k, and its records are stored relative to t0, so every
+    per-case value is what a plain rollout of that case alone reports.  reseat_every: steps between two reseats (1: a slot
+    is refilled at the first step after its episode ended).
+
+    Scope: teams of 1 .. MAX_AGENTS agents, the dense graph, tie_mode 'lowest' or 'hashed'.  'hashed' hashes (seed, slot,
+    global step), so a case draws a different -- equally arbitrary -- stream than in a plain rollout.  'replay', 'mt19937',
+    record=..., graph='lists' and N > MAX_AGENTS are refused by name before anything is enqueued.
+
+    For expert.solve_failures / write_failure_cases the stream looks like a finished rollout of B = C episodes: `.grid`,
+    `.grid_batched`, `.pos` (final positions [C,N,2]), `.goal`, `.B`, `.N`, `.device`, results()."""
+
+    def __init__(self, grids, starts, goals, maxstep, device, slots=512, commR=6.0, tie_mode='lowest', seed=0,
+                 reseat_every=1, record=False, graph='dense'):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise _native.GnnppError('RolloutStream needs a HIP device (no CPU fallback)')
+        if tie_mode not in _TIE:
+            raise _native.GnnppError('unknown tie_mode %r (one of %s)' % (tie_mode, sorted(_TIE)))
+        if tie_mode in ('replay', 'mt19937'):
+            raise _native.GnnppError("RolloutStream: tie_mode %r keeps per-episode state that a seat would have to rewind; "
+                                     "use 'lowest' or 'hashed'" % tie_mode)
+        if record is not False and record is not None:
+            raise _native.GnnppError('RolloutStream: record=... is not supported (a trace is laid out per episode of a '
+                                     'fixed batch); use BatchedRollout(record=...)')
+        if graph != 'dense':
+            raise _native.GnnppError("RolloutStream: graph=%r is not supported (a seat builds the dense GSO); use "
+                                     "graph='dense'" % (graph,))
+        starts_t, goals_t = torch.as_tensor(starts), torch.as_tensor(goals)
+        C, N = int(starts_t.shape[0]), int(starts_t.shape[1])
+        if N > MAX_AGENTS:
+            raise _native.GnnppError('RolloutStream: N > %d (got N = %d) is not supported: the seat runs the one-wave '
+                                     'graph build' % (MAX_AGENTS, N))
+        if C < 1 or int(slots) < 1 or int(reseat_every) < 1:
+            raise _native.GnnppError('RolloutStream: at least one case, one slot and reseat_every >= 1')
+        assert goals_t.shape == starts_t.shape and starts_t.shape[2] == 2
+        _native.lib()
+        self.device, self.C, self.N = dev, C, N
+        self.B = C                                            # a finished rollout of C episodes, to its readers
+        self.slots = min(int(slots), C)
+        self.reseat_every = int(reseat_every)
+        self.commR = float(commR)
+        g = torch.as_tensor(grids)
+        self.grid_batched = int(g.dim() == 3)
+        assert not self.grid_batched or g.shape[0] == C
+        self.grid = g.to(torch.uint8).contiguous().to(dev)
+        self.start = starts_t.to(torch.int32).contiguous().to(dev)
+        self.goal = goals_t.to(torch.int32).contiguous().to(dev)
+        ms = torch.as_tensor(maxstep, dtype=torch.int32)
+        self.case_maxstep = (ms if ms.dim() else ms.repeat(C)).contiguous().to(dev)
+        assert self.case_maxstep.shape == (C,)
+        self._limit = int(self.case_maxstep.sum().item())     # (host bound of run(): no stream is longer than that)
+        B = self.slots
+        # the slots start as copies of the first cases (valid cells everywhere), all marked empty by begin()
+        self.env = BatchedRollout(self.grid[:B].clone() if self.grid_batched else self.grid, self.start[:B].clone(),
+                                  self.goal[:B].clone(), self.case_maxstep[:B].clone(), dev, commR=commR,
+                                  tie_mode=tie_mode, seed=seed)
+        self.env._seated = True
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.cursor = torch.zeros(1, **i32)
+        self.case = torch.empty(B, **i32)                     # the case each slot holds (-1: empty) ...
+        self.t0 = torch.empty(B, **i32)                       # ... and the step count at which it was seated
+        self.assign = torch.empty(B, **i32)
+        self.reached = torch.empty(C, N, **i32)
+        self.start_step = torch.empty(C, N, **i32)
+        self.end_step = torch.empty(C, N, **i32)
+        self.pos = torch.empty(C, N, 2, **i32)
+        self.radius = torch.empty(C, dtype=torch.float64, device=dev)
+        self.stats = torch.empty(C, 2, **i32)
+        self.lived = torch.empty(C, **i32)
+        self.case_slot = torch.empty(C, **i32)
+        self.case_t0 = torch.empty(C, **i32)
+        e = self.env
+        s = _native.RolloutStreamStruct()
+        s.case_grid, s.case_grid_batched = _p(self.grid), self.grid_batched
+        s.case_start, s.case_goal, s.case_maxstep, s.C, s.commR = _p(self.start), _p(self.goal), _p(self.case_maxstep), C, \
+            self.commR
+        s.cursor, s.slot_case, s.slot_t0, s.assign = _p(self.cursor), _p(self.case), _p(self.t0), _p(self.assign)
+        s.slot_grid = _p(e.grid) if self.grid_batched else None
+        s.goal, s.maxstep = _p(e.goal), _p(e.maxstep)
+        s.reached, s.start_step, s.end_step, s.pos = _p(self.reached), _p(self.start_step), _p(self.end_step), _p(self.pos)
+        s.radius, s.stats, s.lived, s.slot, s.t0 = _p(self.radius), _p(self.stats), _p(self.lived), _p(self.case_slot), \
+            _p(self.case_t0)
+        self._s = s
+        with _native.device_guard(dev):
+            _native.check(_native.lib().gnnpp_rollout_stream_begin(ctypes.byref(e._r), ctypes.byref(s),
+                                                                   _native.stream_ptr(dev)), 'gnnpp_rollout_stream_begin')
+        self._reseated_at = -1                                # step count of the last reseat
+
+    @property
+    def t(self):
+        return self.env.t                                     # the global step count
+
+    def reseat(self):
+        """Harvest every finished slot into the per-case tables and seat the next cases of the queue, at the current step
+        count: two launches on the current stream, nothing read on the host.  Seated slots get their step-0 state
+        (radius growth, S, observations) from the seat itself."""
+        e = self.env
+        with _native.device_guard(self.device):
+            _native.check(_native.lib().gnnpp_rollout_stream_reseat(ctypes.byref(e._r), ctypes.byref(self._s), e.t,
+                                                                    _native.stream_ptr(self.device)),
+                          'gnnpp_rollout_stream_reseat')
+        self._reseated_at = e.t
+        if e.t == 0:
+            e._state_step = 0         # every slot was just seated: S and the observations describe step 0
+
+    def _due(self):
+        return self._reseated_at != self.env.t and self.env.t % self.reseat_every == 0
+
+    def move(self, actions=None, logits=None):
+        """One scripted step of every slot: a reseat when one is due, then the rollout's move.  actions [slots,N] / logits
+        [N,slots,5] are per SLOT: gather them from `case` and `t0` (device tensors) after reseat()."""
+        if self._due():
+            self.reseat()
+        return self.env.move(logits=logits, actions=actions)
+
+    def steps(self, model, n):
+        """n policy steps of every slot, a reseat every `reseat_every` of them."""
+        left = int(n)
+        while left > 0:
+            if self._due():
+                self.reseat()
+            burst = min(left, self.reseat_every - self.env.t % self.reseat_every)
+            self.env.steps(model, burst)
+            left -= burst
+        return self.env.flags
+
+    def finished(self):
+        """Every case has been seated and every slot's episode has ended (ONE host read of the cursor and the done count)."""
+        state = torch.stack([self.cursor[0], (self.env.done != 0).sum().to(torch.int32)]).tolist()
+        return state[0] >= self.C and state[1] == self.slots
+
+    def run(self, model, check_every=8):
+        """Step until every case is harvested; the host reads the cursor and the done count once per check_every steps."""
+        bound = self._limit + (self.C + 1) * self.reseat_every + check_every
+        while True:
+            self.steps(model, check_every - self.env.t % check_every)
+            if hasattr(model, 'check_range'):
+                model.check_range()
+            if self.finished():
+                break
+            if self.env.t > bound:
+                raise _native.GnnppError('RolloutStream.run: %d steps and the queue has not drained' % self.env.t)
+        return self.results()
+
+    def results(self):
+        """Per CASE, the keys BatchedRollout.results() gives per episode (step records relative to the case's seat), plus
+        `slot`, `t0`, `lived` and `occupancy` = live slot-steps / all slot-steps so far.  Finished slots that were not
+        harvested yet are harvested first; a case that has not ended reads -1 (done: False)."""
+        self.reseat()
+        torch.cuda.synchronize(self.device)
+        lived = self.lived.cpu()
+        done = lived >= 0
+        reached = self.reached.cpu() > 0
+        total = self.slots * self.env.t
+        return {'steps': self.env.t, 'reached': reached, 'success': reached.all(dim=1) & done,
+                'makespan': self.stats[:, 0].cpu(), 'flowtime': self.stats[:, 1].cpu(), 'end_step': self.end_step.cpu(),
+                'start_step': self.start_step.cpu(), 'positions': self.pos.cpu(), 'radius': self.radius.cpu(), 'done': done,
+                'slot': self.case_slot.cpu(), 't0': self.case_t0.cpu(), 'lived': lived,
+                'occupancy': float(lived[done].sum()) / total if total else 0.0}
 
 
 class GroupedRollout:
