@@ -28,6 +28,7 @@ H2_UNSAFE_MARK = LIB_PATH + '.split_f16_disabled'
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp.h')
 MAPF_DISTANCE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_distance.h')
 CASEGEN_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_casegen.h')
+CASEGEN_MAZE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_casegen_maze.h')
 MAPF_AUDIT_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_audit.h')
 ROLLOUT_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_trace.h')
 SCHEDULE_DRAW_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_schedule_draw.h')
@@ -99,7 +100,8 @@ def precision_code(p):
 def _sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [HEADER, MAPF_DISTANCE_HEADER, CASEGEN_HEADER,
                                                                           MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER,
-                                                                          SCHEDULE_DRAW_HEADER, ROLLOUT_STREAM_HEADER]
+                                                                          SCHEDULE_DRAW_HEADER, ROLLOUT_STREAM_HEADER,
+                                                                          CASEGEN_MAZE_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -382,6 +384,11 @@ ROLLOUT_STREAM_SIGNATURES = {
     'gnnpp_rollout_stream_begin': (_ci, [_rollout, _rstream, _vp]),
     'gnnpp_rollout_stream_reseat': (_ci, [_rollout, _rstream, _ci, _vp]),
 }
+# include/gnnpp_casegen_maze.h, the companion header of the maze maps: a table of its own for the same reason
+# (tests/test_casegen_maze_abi.py)
+CASEGEN_MAZE_SIGNATURES = {
+    'gnnpp_casegen_maze': (_ci, [_vp, ctypes.c_uint, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
+}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
 MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 
@@ -389,12 +396,13 @@ MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
     build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES,
-    ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES and ROLLOUT_STREAM_SIGNATURES; returns the library."""
+    ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES, ROLLOUT_STREAM_SIGNATURES and CASEGEN_MAZE_SIGNATURES; returns the
+    library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
             list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + \
             list(ROLLOUT_TRACE_SIGNATURES.items()) + list(SCHEDULE_DRAW_SIGNATURES.items()) + \
-            list(ROLLOUT_STREAM_SIGNATURES.items()) + optional:
+            list(ROLLOUT_STREAM_SIGNATURES.items()) + list(CASEGEN_MAZE_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

@@ -8,8 +8,14 @@ connected free region (img_fill), start and goal pairs from the free space witho
 (include/gnnpp_casegen.h, csrc/casegen_kernels.hip) states that generator as a contract on counter hashes -- a case
 depends on (seed, case index) alone -- and runs one workgroup per case: the hashed map (or the caller's own), its largest
 4-connected free component, N distinct starts and N distinct goals of that component, no agent on its own goal.  Every
-agent of a generated case has a path.  The reference's maze-style generator (mapGen: sequential random walks) is not
-restated.  There is no CPU fallback.  Positions are (row, col) integers.
+agent of a generated case has a path.  There is no CPU fallback.  Positions are (row, col) integers.
+
+The reference's own maps -- CasesGen.mapGen: wall segments grown by random walks on the even lattice, on numpy's legacy
+stream -- come from gnnpp_casegen_maze (include/gnnpp_casegen_maze.h, csrc/casegen_maze_kernels.hip), bit for bit what
+mapGen draws after np.random.seed(s): maze_maps / enqueue_maze_maps, or generate(..., maps='maze'), which hands them to
+the unchanged gnnpp_casegen as the caller's maps.  The closure stays this module's (the largest component), not the
+reference's img_fill (a flood from the corner cell); the two agree wherever the corner is free and lies in the largest
+free region.
 """
 import numpy as np
 import torch
@@ -93,14 +99,105 @@ def enqueue_generate(out, density=0.1, seed=0, grids=None):
             out.goal.data_ptr(), out.cells.data_ptr(), out.status.data_ptr(), _native.stream_ptr(dev)), 'gnnpp_casegen')
 
 
-def generate(C, N, H, W, device, density=0.1, seed=0, grids=None):
+def maze_counts(H, W, density, complexity):
+    """(walls, steps) of an H x W maze: the reference's own float expressions (mapGen), so the rounding is its own."""
+    return int(density * ((int(H) // 2) * (int(W) // 2))), int(complexity * (5 * (int(H) + int(W))))
+
+
+def _check_maze(H, W, density, complexity):
+    if not (3 <= int(H) <= MAX_SIDE and 3 <= int(W) <= MAX_SIDE):
+        raise _native.GnnppError('maze maps of 3 x 3 to %d x %d cells (got %d x %d; below 3 the reference itself raises)'
+                                 % (MAX_SIDE, MAX_SIDE, H, W))
+    if not 0.0 <= float(density) <= 1.0:
+        raise _native.GnnppError('density must be in 0 .. 1 (got %r)' % (density,))
+    if not 0.0 <= float(complexity) <= 1.0:
+        raise _native.GnnppError('complexity must be in 0 .. 1 (got %r)' % (complexity,))
+
+
+def enqueue_maze_maps(out, density, complexity, seed=0, seeds=None, words=None):
+    """gnnpp_casegen_maze alone, on torch's current stream of the tensor's device: one launch, no allocation, no host
+    synchronisation, capturable in a HIP graph.  out: contiguous uint8 device tensor [C,H,W], every byte is written (1 =
+    wall).  Map c is what the reference's mapGen(width=W, height=H, complexity, density) returns after
+    np.random.seed(seed + c mod 2^32), or after np.random.seed(seeds[c]) with seeds, a contiguous device tensor [C] whose
+    32-bit elements are read as unsigned (int32 or uint32).  words: None or a contiguous int32 device tensor [C] that
+    receives the number of 32-bit words each map took from its stream."""
+    dev = _native.require_gpu(out, seeds, words)
+    if dev is None or out.dim() != 3 or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise _native.GnnppError('out must be a contiguous uint8 device tensor [C,H,W] (no CPU fallback)')
+    C, H, W = (int(v) for v in out.shape)
+    _check_maze(H, W, density, complexity)
+    if C < 1:
+        raise _native.GnnppError('C >= 1 maps (got C = %d)' % C)
+    for name, t, kinds in (('seeds', seeds, (torch.int32, getattr(torch, 'uint32', torch.int32))),
+                           ('words', words, (torch.int32,))):
+        if t is not None and (t.dtype not in kinds or not t.is_contiguous() or tuple(t.shape) != (C,)):
+            raise _native.GnnppError('%s must be a contiguous 32-bit integer tensor [%d] (got %s %s)'
+                                     % (name, C, t.dtype, tuple(t.shape)))
+    walls, steps = maze_counts(H, W, float(density), float(complexity))
+    with _native.device_guard(dev):
+        _native.check(_native.lib().gnnpp_casegen_maze(
+            seeds.data_ptr() if seeds is not None else None, int(seed) & 0xffffffff, C, H, W, walls, steps,
+            out.data_ptr(), words.data_ptr() if words is not None else None, _native.stream_ptr(dev)),
+            'gnnpp_casegen_maze')
+
+
+def _device_seeds(seeds, C, dev):
+    """seeds (any integers in 0 .. 2^32 - 1, host or device) as the int32 device tensor [C] of their low 32 bits."""
+    if seeds is None:
+        return None
+    if torch.is_tensor(seeds) and seeds.is_cuda and seeds.dtype == torch.int32:
+        s = seeds
+    else:
+        a = np.asarray(seeds.cpu() if torch.is_tensor(seeds) else seeds).astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() > 2 ** 32 - 1):
+            raise _native.GnnppError('seeds must lie in 0 .. 2^32 - 1, as np.random.seed takes them')
+        s = torch.from_numpy(a.astype(np.uint32).view(np.int32)).to(dev)
+    if tuple(s.shape) != (int(C),):
+        raise _native.GnnppError('seeds must hold one seed per map, [%d] (got %s)' % (C, tuple(s.shape)))
+    return s.contiguous()
+
+
+def maze_maps(C, H, W, device, density=0.1, complexity=0.01, seed=0, seeds=None):
+    """C maps of H x W cells as the reference draws them (CasesGen.mapGen), uint8 [C,H,W] on the device, 1 = wall: map c
+    from np.random.seed(seed + c mod 2^32), or from seeds[c].  Raw mazes: not closed, see generate(maps='maze')."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise _native.GnnppError('casegen needs a HIP device (no CPU fallback)')
+    _check_maze(H, W, density, complexity)
+    if int(C) < 1:
+        raise _native.GnnppError('C >= 1 maps (got C = %d)' % C)
+    _native.lib()
+    out = torch.empty((int(C), int(H), int(W)), dtype=torch.uint8, device=dev)
+    s = _device_seeds(seeds, C, out.device)
+    enqueue_maze_maps(out, density, complexity, seed, s)
+    out._keep = s                                        # input of the enqueued launch
+    return out
+
+
+def generate(C, N, H, W, device, density=0.1, seed=0, grids=None, maps='uniform', complexity=0.01):
     """C cases of N agents on H x W maps: hashed maps with obstacle density `density`, or, with grids ([C,H,W] or
-    [H,W], host or device, nonzero = obstacle), cases drawn on the caller's own maps.  Every map is closed to its largest
-    4-connected free component; a case whose component holds fewer than max(N, 2) cells is reported in .status
-    (TOO_SMALL), never raised.  The same (seed, arguments) give the same bytes.  Returns Cases."""
+    [H,W], host or device, nonzero = obstacle), cases drawn on the caller's own maps, or, with maps='maze', on the
+    reference's own mazes of (density, complexity), map c from np.random.seed(seed + c mod 2^32) (maze_maps).  Every map
+    is closed to its largest 4-connected free component; a case whose component holds fewer than max(N, 2) cells is
+    reported in .status (TOO_SMALL), never raised.  The same (seed, arguments) give the same bytes.  Returns Cases."""
+    if maps not in ('uniform', 'maze'):
+        raise _native.GnnppError("maps must be 'uniform' or 'maze' (got %r)" % (maps,))
+    if maps == 'maze':
+        if grids is not None:
+            raise _native.GnnppError("grids= and maps='maze' are two sources of the raw map: pass one of them")
+        _check_shape(C, N, H, W)
+        _check_maze(H, W, density, complexity)
     out = empty_cases(C, N, H, W, device)
     if not 0.0 <= float(density) <= 1.0:
         raise _native.GnnppError('density must be in 0 .. 1 (got %r)' % (density,))
+    if maps == 'maze':
+        _native.lib()
+        raw = torch.empty_like(out.grid)
+        enqueue_maze_maps(raw, density, complexity, seed)
+        enqueue_generate(out, density, seed, raw)
+        out._keep = raw                                  # input of the enqueued launch
+        out.raw = raw                                    # the maze before the closure
+        return out
     if grids is not None:
         g = grids if torch.is_tensor(grids) else torch.as_tensor(np.asarray(grids))
         if g.dim() not in (2, 3) or tuple(g.shape[-2:]) != (int(H), int(W)) or (g.dim() == 3 and g.shape[0] != int(C)):

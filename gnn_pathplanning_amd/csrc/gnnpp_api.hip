@@ -17,6 +17,7 @@
 #include "mapf_team_kernels.hip"     // ... for teams of up to 1024 agents on maps of up to 256 x 256 (one workgroup per case)
 #include "mapf_distance_kernels.hip" // ... its planning orders: true goal distances and the orders ranked from them
 #include "casegen_kernels.hip"       // ... its cases: connected random maps with start and goal pairs, from a seed
+#include "casegen_maze_kernels.hip"  // ... their raw maps as the reference draws them: numpy's stream and the wall walk
 #include "mapf_audit_kernels.hip"    // ... its checker: conflicts, arrivals and costs of any schedule
 #include "encoder_kernel_h2.hip"
 #include "encoder_kernel_b3.hip"
@@ -953,6 +954,25 @@ int gnnpp_casegen(const unsigned char* grid_in, int grid_in_batched, unsigned ob
     a.cells = cells;
     a.status = status;
     return casegen_launch(a, static_cast<hipStream_t>(stream));
+}
+
+// include/gnnpp_casegen_maze.h: the pointer, the sizes, the supported map size; nothing is enqueued on an error
+int gnnpp_casegen_maze(const unsigned* seeds, unsigned seed0, int C, int H, int W, int walls, int steps,
+                       unsigned char* grid, int* words, void* stream) {
+    if (!grid || C <= 0 || H < 3 || W < 3 || walls < 0 || steps < 0 || (long long)walls * steps > 0x7fffffffLL)
+        return GNNPP_ERR_ARG;
+    if (H > GNNPP_MAPF_TEAM_MAX_SIDE || W > GNNPP_MAPF_TEAM_MAX_SIDE) return GNNPP_ERR_UNSUPPORTED;
+    CasegenMazeArgs a;
+    a.seeds = seeds;
+    a.seed0 = seed0;
+    a.C = C;
+    a.H = H;
+    a.W = W;
+    a.walls = walls;
+    a.steps = steps;
+    a.grid = grid;
+    a.words = words;
+    return casegen_maze_launch(a, static_cast<hipStream_t>(stream));
 }
 
 // include/gnnpp_mapf_audit.h: sizes (GNNPP_ERR_ARG), the supported map size, the horizon, pointers, the workspace; nothing
