@@ -33,6 +33,7 @@ MAPF_AUDIT_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_mapf_
 ROLLOUT_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_trace.h')
 SCHEDULE_DRAW_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_schedule_draw.h')
 ROLLOUT_STREAM_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_stream.h')
+ROLLOUT_STREAM_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_stream_trace.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
@@ -101,7 +102,7 @@ def _sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [HEADER, MAPF_DISTANCE_HEADER, CASEGEN_HEADER,
                                                                           MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER,
                                                                           SCHEDULE_DRAW_HEADER, ROLLOUT_STREAM_HEADER,
-                                                                          CASEGEN_MAZE_HEADER]
+                                                                          CASEGEN_MAZE_HEADER, ROLLOUT_STREAM_TRACE_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -278,6 +279,13 @@ class RolloutStreamStruct(ctypes.Structure):
                 ('slot', ctypes.c_void_p), ('t0', ctypes.c_void_p)]
 
 
+class RolloutStreamTraceStruct(ctypes.Structure):
+    """struct gnnpp_rollout_stream_trace (include/gnnpp_rollout_stream_trace.h)."""
+    _fields_ = [('path', ctypes.c_void_p), ('action', ctypes.c_void_p), ('moves', ctypes.c_void_p),
+                ('shielded', ctypes.c_void_p), ('steps', ctypes.c_void_p), ('seen_done', ctypes.c_void_p),
+                ('T_cap', ctypes.c_int)]
+
+
 _vp, _ci, _cs, _ll, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_float
 _enc, _rollout = ctypes.POINTER(EncoderParams), ctypes.POINTER(RolloutStruct)
 _sched, _mapf, _gemm = ctypes.POINTER(ScheduleStruct), ctypes.POINTER(MapfStruct), ctypes.POINTER(GemmDesc)
@@ -389,6 +397,14 @@ ROLLOUT_STREAM_SIGNATURES = {
 CASEGEN_MAZE_SIGNATURES = {
     'gnnpp_casegen_maze': (_ci, [_vp, ctypes.c_uint, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp]),
 }
+# include/gnnpp_rollout_stream_trace.h, the companion header of a streamed rollout's trace: a table of its own for the same
+# reason (tests/test_rollout_stream_trace_abi.py)
+_rstrace = ctypes.POINTER(RolloutStreamTraceStruct)
+ROLLOUT_STREAM_TRACE_SIGNATURES = {
+    'gnnpp_rollout_stream_trace_begin': (_ci, [_rollout, _rstream, _rstrace, _vp]),
+    'gnnpp_rollout_stream_trace_record': (_ci, [_rollout, _rstream, _rstrace, _vp]),
+    'gnnpp_rollout_stream_policy_steps_traced': (_ci, [_rollout] + [_vp] * 5 + [_ci, _ci, _ci, _rstream, _rstrace, _vp]),
+}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
 MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 
@@ -396,13 +412,14 @@ MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
     build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES,
-    ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES, ROLLOUT_STREAM_SIGNATURES and CASEGEN_MAZE_SIGNATURES; returns the
-    library."""
+    ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES, ROLLOUT_STREAM_SIGNATURES, CASEGEN_MAZE_SIGNATURES and
+    ROLLOUT_STREAM_TRACE_SIGNATURES; returns the library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
             list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + \
             list(ROLLOUT_TRACE_SIGNATURES.items()) + list(SCHEDULE_DRAW_SIGNATURES.items()) + \
-            list(ROLLOUT_STREAM_SIGNATURES.items()) + list(CASEGEN_MAZE_SIGNATURES.items()) + optional:
+            list(ROLLOUT_STREAM_SIGNATURES.items()) + list(CASEGEN_MAZE_SIGNATURES.items()) + \
+            list(ROLLOUT_STREAM_TRACE_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

@@ -33,6 +33,7 @@
 #include "train_ops.hip"
 #include "rollout_trace_kernels.hip"       // the rollout's trace: a record launch behind each move, no simulator kernel touched
 #include "rollout_stream_kernels.hip"      // streamed rollouts: finished episode slots refilled from a case queue
+#include "rollout_stream_trace_kernels.hip"   // ... their trace: per-case tables, rows relative to the seat
 
 using namespace gnnpp;
 
@@ -1092,6 +1093,58 @@ int gnnpp_rollout_stream_reseat(const gnnpp_rollout* r, const gnnpp_rollout_stre
     const int rc = rollout_stream_check(r, s, true, now);
     if (rc != GNNPP_OK) return rc;
     return rollout_stream_reseat_launch(*r, *s, now, static_cast<hipStream_t>(stream));
+}
+
+// include/gnnpp_rollout_stream_trace.h: pointers and sizes first (GNNPP_ERR_ARG), then what a stream does not cover
+// (GNNPP_ERR_UNSUPPORTED, where gnnpp_rollout_stream_reseat answers it); `count` steps from r->currentstep are to be recorded
+// (count = 0: begin).  Nothing is enqueued and no HIP call is made on an error
+static int rollout_stream_trace_check(const gnnpp_rollout* r, const gnnpp_rollout_stream* s,
+                                      const gnnpp_rollout_stream_trace* tr, bool record, int count) {
+    if (!r || !s || !tr) return GNNPP_ERR_ARG;
+    if (!r->pos || !r->done || !r->maxstep || !s->slot_case || !s->slot_t0 || !s->case_start || !tr->path || !tr->steps ||
+        !tr->seen_done)
+        return GNNPP_ERR_ARG;
+    if (r->B <= 0 || r->N < 1 || s->C <= 0 || (long long)r->B * r->N > 0x7fffffffLL ||
+        (long long)s->C * r->N > 0x7fffffffLL || tr->T_cap < 1)
+        return GNNPP_ERR_ARG;
+    if (record) {
+        if (r->currentstep < 1 || count < 1) return GNNPP_ERR_ARG;
+        if (!r->logits && !r->actions && (tr->action || tr->shielded)) return GNNPP_ERR_ARG;
+    }
+    if (r->N > GNNPP_ROLLOUT_MAX_AGENTS) return GNNPP_ERR_UNSUPPORTED;
+    if (r->tie_mode == GNNPP_TIE_REPLAY || r->tie_mode == GNNPP_TIE_MT19937) return GNNPP_ERR_UNSUPPORTED;
+    return GNNPP_OK;
+}
+
+int gnnpp_rollout_stream_trace_begin(const gnnpp_rollout* r, const gnnpp_rollout_stream* s,
+                                     const gnnpp_rollout_stream_trace* tr, void* stream) {
+    const int rc = rollout_stream_trace_check(r, s, tr, false, 0);
+    if (rc != GNNPP_OK) return rc;
+    return rollout_stream_trace_begin_launch(*r, *s, *tr, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_rollout_stream_trace_record(const gnnpp_rollout* r, const gnnpp_rollout_stream* s,
+                                      const gnnpp_rollout_stream_trace* tr, void* stream) {
+    const int rc = rollout_stream_trace_check(r, s, tr, true, 1);
+    if (rc != GNNPP_OK) return rc;
+    return rollout_stream_trace_record_launch(*r, *s, *tr, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_rollout_stream_policy_steps_traced(const gnnpp_rollout* r, const float* enc_packed, const float* filt_packed,
+                                             const float* gf_bias, const float* act_w, const float* act_b, int K,
+                                             int nsteps, int precision, const gnnpp_rollout_stream* s,
+                                             const gnnpp_rollout_stream_trace* tr, void* stream) {
+    int rc = rollout_stream_trace_check(r, s, tr, true, nsteps);
+    if (rc != GNNPP_OK) return rc;
+    gnnpp_rollout rs = *r;
+    for (int i = 0; i < nsteps; ++i) {
+        rs.currentstep = r->currentstep + i;
+        rc = gnnpp_rollout_policy_step(&rs, enc_packed, filt_packed, gf_bias, act_w, act_b, K, precision, stream);
+        if (rc != GNNPP_OK) return rc;                   // (argument / shape errors surface at i = 0)
+        rc = rollout_stream_trace_record_launch(rs, *s, *tr, static_cast<hipStream_t>(stream));
+        if (rc != GNNPP_OK) return rc;
+    }
+    return GNNPP_OK;
 }
 
 }  // extern "C"

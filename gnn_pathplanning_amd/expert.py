@@ -368,7 +368,8 @@ def write_failure_cases(directory, rollout, ids=None, results=None):
 
 
 def write_prediction_cases(directory, rollout, ids=None, results=None):
-    """The predicted schedule of every episode of a RECORDED rollout (BatchedRollout / GroupedRollout with record=...) next
+    """The predicted schedule of every episode of a RECORDED rollout (BatchedRollout / GroupedRollout with record=..., or a
+    RolloutStream with trace=...: its cases are the episodes, its per-case results() the statistics) next
     to the input file of its ORIGINAL starts, as save_success_cases writes them for the reference's movies
     (multirobotsim_dcenlocal_onlineExpert.py:732-799): `directory`/input/{mode}Cases_ID{:05d}.yaml and
     `directory`/predict_{mode}/{mode}Cases_ID{:05d}.yaml with mode = success | failure.  ids: the dataset ID of each
@@ -376,7 +377,7 @@ def write_prediction_cases(directory, rollout, ids=None, results=None):
     input path, prediction path); read_solution(input path, prediction path) reads a pair back."""
     trace = getattr(rollout, 'trace', None)
     if trace is None:
-        raise _native.GnnppError('write_prediction_cases needs a recorded rollout (record=True)')
+        raise _native.GnnppError('write_prediction_cases needs a recorded rollout (record=True; RolloutStream: trace=True)')
     res = rollout.results() if results is None else results
     grid, goal = trace.grid.cpu().numpy(), trace.goal.cpu().numpy()
     starts = trace.path[:, 0].cpu().numpy()

@@ -119,6 +119,49 @@ class RolloutTrace:
         return ''.join(out)
 
 
+class StreamTrace(RolloutTrace):
+    """What a traced stream did, per CASE of its queue (include/gnnpp_rollout_stream_trace.h): the RolloutTrace interface
+    with B = C, rows RELATIVE to each case's seat.
+
+        path      int32 [C,T_cap+1,N,2]  row 0 = the case's starts, row k = the positions after its step k
+        action    int8  [C,T_cap,N]      the action each agent asked for at the case's step k + 1, -1 = nothing recorded
+        moves     int32 [C,N]            steps at which the agent's position changed
+        shielded  int32 [C,N]            steps at which the agent asked to move and stood still instead
+        steps     int32 [C]              the case's last step that was not frozen; -1 = no move of the case recorded yet
+
+    Unlike a RolloutTrace, a frozen case writes nothing: the rows beyond steps[c] stay 0 and `action` stays -1 there.
+    `seen_done` [slots] is the recorder's own word per SLOT.  `grid`, `grid_batched` and `goal` are the case queue's.
+    schedule(c), prediction_yaml(c, results=None) and audit() are keyed by case."""
+
+    def __init__(self, owner, T_cap):
+        self._owner = owner                                   # the stream: results() per case for the files' statistics
+        self.grid, self.grid_batched, self.goal = owner.grid, owner.grid_batched, owner.goal
+        self.B, self.N = owner.C, owner.N
+        self.T_cap, self.device = int(T_cap), owner.device
+        C, N, T, dev = self.B, self.N, self.T_cap, self.device
+        self.path = torch.empty(C, T + 1, N, 2, dtype=torch.int32, device=dev)   # (all of it is set by begin)
+        self.action = torch.empty(C, T, N, dtype=torch.int8, device=dev)
+        self.moves = torch.empty(C, N, dtype=torch.int32, device=dev)
+        self.shielded = torch.empty(C, N, dtype=torch.int32, device=dev)
+        self.steps = torch.empty(C, dtype=torch.int32, device=dev)
+        self.seen_done = torch.empty(owner.slots, dtype=torch.int32, device=dev)
+        s = _native.RolloutStreamTraceStruct()
+        s.path, s.action, s.moves, s.shielded = _p(self.path), _p(self.action), _p(self.moves), _p(self.shielded)
+        s.steps, s.seen_done, s.T_cap = _p(self.steps), _p(self.seen_done), self.T_cap
+        self._s = s
+
+    def audit(self):
+        """RolloutTrace.audit per case: rows 0 .. steps[c] of `path` against the case queue's maps and goals, row 0 as the
+        starts, with the same map and step limits.  Refused while a case has no recorded move yet (steps[c] < 0: the audit
+        would skip it silently) -- run the stream to its end first."""
+        self._sync()
+        missing = (self.steps < 0).nonzero().flatten()
+        if missing.numel():
+            raise _native.GnnppError('StreamTrace.audit: %d case(s) have no recorded move yet (steps[c] < 0; first: case %d): '
+                                     'run the stream until its queue has drained' % (missing.numel(), int(missing[0])))
+        return RolloutTrace.audit(self)
+
+
 class BatchedRollout:
     def __init__(self, grid, starts, goals, maxstep, device, commR=6.0, tie_mode='lowest', seed=0,
                  rng_words=None, graph='dense', record=False):
@@ -194,6 +237,7 @@ class BatchedRollout:
         self.t = 0                                            # steps taken so far
         self._state_step = -1                                 # step whose positions obs / S describe
         self._seated = False                                  # RolloutStream: every slot's step-0 state comes from its seat
+        self._stream_trace = None                             # RolloutStream(trace=...): the stream whose recorder follows a move
         # teams up to this size run move -> graph -> observations as ONE launch (gnnpp_rollout_step, one workgroup
         # per episode); larger ones as move, then graph || observations in a second launch (gnnpp_rollout_gso_observe:
         # more workgroups than episodes).  Measured per simulator step: N = 10 16.1 (one launch) vs 17.3 us,
@@ -232,6 +276,8 @@ class BatchedRollout:
         """The trace's row of the move just enqueued (its logits / actions are still in the struct)."""
         if self.trace is not None:
             self._trace_call(_native.lib().gnnpp_rollout_trace_record, 'gnnpp_rollout_trace_record')
+        elif self._stream_trace is not None:                 # the slots of a traced stream: its per-case recorder
+            self._stream_trace._record()
 
     def _check_room(self, n=1, currentstep=None):
         """record: the next n steps must fit the trace, and be the rollout's own next steps -- before anything is enqueued."""
@@ -352,6 +398,12 @@ class BatchedRollout:
                 rc = _native.lib().gnnpp_rollout_policy_steps_traced(ctypes.byref(r), enc, taps, gb, aw, ab, K, nsteps, prec,
                                                                      ctypes.byref(self.trace._s),
                                                                      _native.stream_ptr(self.device))
+            elif self._stream_trace is not None:    # the slots of a traced stream: a per-case record behind each launch
+                what = 'gnnpp_rollout_stream_policy_steps_traced'
+                st = self._stream_trace
+                rc = _native.lib().gnnpp_rollout_stream_policy_steps_traced(ctypes.byref(r), enc, taps, gb, aw, ab, K, nsteps,
+                                                                            prec, ctypes.byref(st._s), ctypes.byref(st.trace._s),
+                                                                            _native.stream_ptr(self.device))
             else:
                 what = 'gnnpp_rollout_policy_steps'
                 rc = _native.lib().gnnpp_rollout_policy_steps(ctypes.byref(r), enc, taps, gb, aw, ab, K, nsteps, prec,
@@ -473,11 +525,18 @@ class RolloutStream:
     global step), so a case draws a different -- equally arbitrary -- stream than in a plain rollout.  'replay', 'mt19937',
     record=..., graph='lists' and N > MAX_AGENTS are refused by name before anything is enqueued.
 
+    trace: True keeps a StreamTrace (`self.trace`) of max(maxstep) steps per case, an integer one of that many steps (refused
+    when below max(maxstep): rows would be lost silently).  It is what BatchedRollout(record=...) keeps, per CASE and with
+    rows relative to the case's seat: one small launch behind every move on every route (the one-launch burst included,
+    still enqueued by one C call), nothing else about the stream changes and results() is the same.  record= stays refused:
+    its trace is laid out per slot of a fixed batch and repeats a frozen episode's last row, this one writes nothing for a
+    frozen slot.
+
     For expert.solve_failures / write_failure_cases the stream looks like a finished rollout of B = C episodes: `.grid`,
     `.grid_batched`, `.pos` (final positions [C,N,2]), `.goal`, `.B`, `.N`, `.device`, results()."""
 
     def __init__(self, grids, starts, goals, maxstep, device, slots=512, commR=6.0, tie_mode='lowest', seed=0,
-                 reseat_every=1, record=False, graph='dense'):
+                 reseat_every=1, record=False, graph='dense', trace=False):
         dev = torch.device(device)
         if dev.type != 'cuda':
             raise _native.GnnppError('RolloutStream needs a HIP device (no CPU fallback)')
@@ -488,7 +547,8 @@ class RolloutStream:
                                      "use 'lowest' or 'hashed'" % tie_mode)
         if record is not False and record is not None:
             raise _native.GnnppError('RolloutStream: record=... is not supported (a trace is laid out per episode of a '
-                                     'fixed batch); use BatchedRollout(record=...)')
+                                     'fixed batch); use trace=... for the per-case trace of a stream, or '
+                                     'BatchedRollout(record=...)')
         if graph != 'dense':
             raise _native.GnnppError("RolloutStream: graph=%r is not supported (a seat builds the dense GSO); use "
                                      "graph='dense'" % (graph,))
@@ -516,6 +576,13 @@ class RolloutStream:
         self.case_maxstep = (ms if ms.dim() else ms.repeat(C)).contiguous().to(dev)
         assert self.case_maxstep.shape == (C,)
         self._limit = int(self.case_maxstep.sum().item())     # (host bound of run(): no stream is longer than that)
+        T_cap = None
+        if trace is not False and trace is not None:
+            longest = int(self.case_maxstep.max().item())
+            T_cap = longest if trace is True else int(trace)
+            if T_cap < max(longest, 1):
+                raise _native.GnnppError('RolloutStream: trace=%d is below the longest case limit, max(maxstep) = %d: a '
+                                         'shorter trace would silently lose rows' % (T_cap, longest))
         B = self.slots
         # the slots start as copies of the first cases (valid cells everywhere), all marked empty by begin()
         self.env = BatchedRollout(self.grid[:B].clone() if self.grid_batched else self.grid, self.start[:B].clone(),
@@ -552,6 +619,20 @@ class RolloutStream:
             _native.check(_native.lib().gnnpp_rollout_stream_begin(ctypes.byref(e._r), ctypes.byref(s),
                                                                    _native.stream_ptr(dev)), 'gnnpp_rollout_stream_begin')
         self._reseated_at = -1                                # step count of the last reseat
+        self.trace = None
+        if T_cap is not None:
+            self.trace = StreamTrace(self, T_cap)
+            self._trace_call(_native.lib().gnnpp_rollout_stream_trace_begin, 'gnnpp_rollout_stream_trace_begin')
+            e._stream_trace = self                            # every move of the slots is followed by _record()
+
+    def _trace_call(self, fn, what):
+        with _native.device_guard(self.device):
+            _native.check(fn(ctypes.byref(self.env._r), ctypes.byref(self._s), ctypes.byref(self.trace._s),
+                             _native.stream_ptr(self.device)), what)
+
+    def _record(self):
+        """trace=...: the per-case rows of the move just enqueued (its logits / actions are still in the slots' struct)."""
+        self._trace_call(_native.lib().gnnpp_rollout_stream_trace_record, 'gnnpp_rollout_stream_trace_record')
 
     @property
     def t(self):
