@@ -77,6 +77,10 @@ TUNE_FILTER_ABLATE, TUNE_ENCODER_STOP = 3, 4
 # csrc/encoder_kernel_b3.hip: 1 (default) = a team of 10 agents runs the packed policy kernel's compile-time-N form, 0 = the
 # run-time-N form like every other team size (same logits to the bit); a key of the tests and the A/B tools, in every build
 TUNE_POLICY_CP_TEAM = 21
+# csrc/encoder_kernel_b3.hip: inside that form, 1 (default) = a one-plane tile runs the first conv layer with (window, agent)
+# pairs on the MFMA columns, 0 = with agents on the columns as every other form (same logits to the bit); key 21 = 0
+# selects the whole run-time form whatever this key says
+TUNE_POLICY_CP_TEAM_L0 = 22
 PRECISIONS = {'fp32': PREC_FP32, 'fp32_mfma': PREC_FP32_MFMA, 'split_f16': PREC_SPLIT_F16}
 
 

@@ -63,6 +63,7 @@ constexpr int kPkChan = 73;
 constexpr int kPkAgent = 231;
 constexpr int kPkBytes = kTileAgents * kPkAgent * 4;      // 14 784
 constexpr int kB3ForcePlanes = 256;                        // kernel argument stop_flags, bit 8
+constexpr int kB3L0ByAgent = 512;                          // ... bit 9: a 10-agent team's L0 keeps agents on the columns
 constexpr int kL0Held = 2;                                 // windows per wave whose output waits for the pixels' last read
 static_assert(kPkChan >= kPadHW * kPadHW / 2 && kPkAgent >= 3 * kPkChan && (kPkAgent & 1) && kPkBytes % 16 == 0 &&
               kPkBytes <= 2 * kObsFloatsLds * 4, "packed pixel image");
@@ -313,7 +314,8 @@ __device__ __forceinline__ void b3_conv_preload(const WStreamB& ws, v4f (&ring)[
 // A tap is then a per-lane LDS address, not a compile-time fragment: a column whose tap leaves the image reads a cell
 // of zeros (its products are exact zeros: acc + 0 == acc, so every output keeps the value -- and the bits -- of the
 // agents-on-columns schedule, whose first reachable tap starts from a zero accumulator too).  L0 keeps agents on its
-// columns (it is VALU- / latency-bound, not pipe-bound) and only writes its pooled windows in L1's input layout;
+// columns and only writes its pooled windows in L1's input layout (a compile-time team of ten packs it too, one-plane
+// tiles only: b3_l0_stream_fixed);
 // L3 / L4 / FC / the filter tail are unchanged (2x2 images: tap skipping beats packing there).
 //
 // LDS layouts (both inside region R; a "row" = 16 cells x [plane 3][q 4] x 16 bytes = 3 KiB, cell slot s at
@@ -743,6 +745,200 @@ __device__ __forceinline__ void b3_l0_stream(const float* __restrict__ pk, const
     };
     stream(std::integral_constant<int, 0>{}, std::integral_constant<int, 24>{});
     if (wave == 0) stream(std::integral_constant<int, 24>{}, std::integral_constant<int, 28>{});   // window 24
+}
+
+// ---- L0 of a one-plane tile for a COMPILE-TIME team of kCpTeamFixed = 10 agents: (window, agent) PAIRS on the columns ------
+// b3_l0_stream spends a whole fragment -- five LDS instructions per half-window, four v_perm, six MFMAs, a share of the
+// epilogue -- on the 10 agents of one position: 6 of its 16 columns belong to agents the team does not have.  With N a
+// constant the columns are c = w * N + n (window w = 0 .. 24, agent n): 250 columns in 16 tiles, wave v takes tiles v, v +
+// 4, v + 8, v + 12 (4 / 4 / 4 / 4 where the windows split 7 / 6 / 6 / 6), a lane walks the four positions (oy, ox) of ITS
+// window as before: 64 (tile, position) fragments instead of 100, 384 MFMAs instead of 600.  Column 16 t + j IS cell u of
+// L1's input (cp_layer1: c = pos * N + n, row u >> 4, slot u & 15): tile t's pooled planes are row t, lane by lane -- one
+// linear 16-byte store per plane.  Row 0 lies at l1in = 24 576 >= kPkBytes: NO tile's output overlaps the pixels, none
+// waits in registers, and the barrier between the stream and the held stores goes (cp_l0f_rows_clear_pixels below).
+// A lane's five addresses are those of b3_l0_stream with agent n and window w of ITS column: per (tile, lane) the base
+// n kPkAgent + 12 wy + wx (dwords) plus the lane's role offset, all 4 x 5 computed once in front of the stream and pinned
+// as cp_layer1 pins its: a request is address register + immediate (the oy step is 24 bytes), no VALU.  Columns 250 .. 255 (tile 15,
+// j >= 10) read window 0 of the absent agents 10 .. 15, whose images the staging zeroes; they are not stored.
+// Every B fragment is b3_l0_stream's for that (agent, position), the q = 3 lanes' weightless k-slots included (their Z is
+// channel 0, row A, dword c0 of the column's own agent and window); the epilogue is the same code.
+// LDS banks: a tile's lanes span two or three windows, whose offsets 12 wy + wx shift one window's agents (banks 39 n mod
+// 64) against the next one's -- cp_l0f_banks() counts, for every tile, the lanes of each of a half-window's seven dword
+// accesses per bank: never more than 3 lanes on a bank (b3_l0_stream: 2), at most 115 doubled lanes in a half-window's 448
+// (43), 3 030 in the layer's 32 half-windows (b3_l0_stream's 50: 2 150).  Conflict freedom is not reachable in this form:
+// the strides kPkChan / kPkAgent are b3_l0_stream's (and were the best found for IT), the column order is L1's input order.
+__host__ __device__ constexpr int cp_l0f_window(int c) { return c < 25 * kCpTeamFixed ? c / kCpTeamFixed : 0; }
+__host__ __device__ constexpr int cp_l0f_agent(int c) {
+    return c < 25 * kCpTeamFixed ? c % kCpTeamFixed : c - 25 * kCpTeamFixed + kCpTeamFixed;
+}
+// the window's first dword in a channel image: rows 2 wy .., dwords wx, wx + 1
+__host__ __device__ constexpr int cp_l0f_base(int c) {
+    return cp_l0f_agent(c) * kPkAgent + (2 * (cp_l0f_window(c) / 5)) * (kPadHW / 2) + cp_l0f_window(c) % 5;
+}
+// role offsets (dwords) of lane group q: reads a (+ 7: e) | b | c | d | f (+ 1: g), as adr[] of b3_l0_stream
+__host__ __device__ constexpr int cp_l0f_role(int q, int k) {
+    return q < 3 ? q * kPkChan + (k == 0 ? 0 : k < 3 ? 1 : k == 3 ? 6 : 12) : k < 3 ? k * kPkChan + 13 : 0;
+}
+// the run-time form of cp_l0f_window: c / 10 as a multiply and a shift, w / 5 likewise
+__host__ __device__ constexpr bool cp_l0f_divisions_ok() {
+    for (int c = 0; c < 256; ++c)
+        if (((c * 205) >> 11) != c / 10) return false;
+    for (int w = 0; w <= 25; ++w)
+        if (((w * 52) >> 8) != w / 5) return false;
+    return true;
+}
+struct CpL0fBanks { int worst, doubled_max, doubled_all; };
+__host__ __device__ constexpr CpL0fBanks cp_l0f_banks() {
+    // (lanes per bank; no two lanes of an access share a dword -- the CPU test of this layer restates that --, so every
+    // lane beyond a bank's first is a conflict.  The oy step moves all 64 lanes alike: both half-windows of a tile count the same.)
+    CpL0fBanks r = {0, 0, 0};
+    for (int t = 0; t < 16; ++t) {
+        int base[16] = {};
+        for (int j = 0; j < 16; ++j) base[j] = cp_l0f_base(16 * t + j);
+        int doubled = 0;
+        for (int acc = 0; acc < 7; ++acc) {                // a e b c d f g
+            const int k = acc < 2 ? 0 : acc > 4 ? 4 : acc - 1, plus = acc == 1 ? 7 : acc == 6 ? 1 : 0;
+            int cnt[64] = {};
+            for (int l = 0; l < 64; ++l) ++cnt[(base[l & 15] + cp_l0f_role(l >> 4, k) + plus) & 63];
+            for (int b = 0; b < 64; ++b) {
+                if (cnt[b] > r.worst) r.worst = cnt[b];
+                if (cnt[b] > 1) doubled += cnt[b] - 1;
+            }
+        }
+        if (doubled > r.doubled_max) r.doubled_max = doubled;
+        r.doubled_all += 2 * doubled;
+    }
+    return r;
+}
+constexpr CpL0fBanks kCpL0fBanks = cp_l0f_banks();
+// every row of L1's input lies behind the packed pixels, and the zero images the columns >= 250 read exist
+__host__ __device__ constexpr bool cp_l0f_rows_clear_pixels() {
+    constexpr int T1 = (25 * kCpTeamFixed + 15) >> 4, l1in = kB3Region - (T1 + 1) * kCpRow;
+    return T1 == 16 && l1in >= kPkBytes && 16 * T1 - 25 * kCpTeamFixed <= kTileAgents - kCpTeamFixed;
+}
+
+template <int NFIX>
+__device__ __forceinline__ void b3_l0_stream_fixed(const float* __restrict__ pk, const float* sstab, char* smem,
+                                                   int wave, int lane) {
+    static_assert(NFIX == kCpTeamFixed && kCpTeamFixed == 10, "the column order and its divisions are written for ten agents");
+    static_assert(cp_l0f_divisions_ok(), "c / 10 and w / 5 as multiply-shift");
+    static_assert(cp_l0f_rows_clear_pixels(), "every tile is stored while other waves still read pixels");
+    static_assert(kCpL0fBanks.worst == 3 && kCpL0fBanks.doubled_max == 115 && kCpL0fBanks.doubled_all == 3030,
+                  "LDS banks of the packed L0's reads (not conflict-free: see above)");
+    constexpr int DEPTH = 2;                              // half-windows the pixel requests run ahead
+    constexpr int l1in = kB3Region - 17 * kCpRow;
+    const int j = lane & 15, q = lane >> 4;
+    v8b A0[2][3];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+            A0[i][p] = as_b8(*reinterpret_cast<const v4f*>(pk + EncLayout::kB0 + ((i * 3 + p) * 64 + lane) * 4));
+    // byte addresses of the five reads of every tile of this wave (cp_l0f_base + cp_l0f_role, at run time)
+    int role[5];
+    role[0] = q < 3 ? q * kPkChan : 13;
+    role[1] = q < 3 ? q * kPkChan + 1 : kPkChan + 13;
+    role[2] = q < 3 ? q * kPkChan + 1 : 2 * kPkChan + 13;
+    role[3] = q < 3 ? q * kPkChan + 6 : 0;
+    role[4] = q < 3 ? q * kPkChan + 12 : 0;
+    int adr[4][5];
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti) {
+        const int c = 16 * (wave + 4 * ti) + j;
+        const bool real = c < 25 * NFIX;
+        const int w = real ? (c * 205) >> 11 : 0, n = real ? c - w * NFIX : c - 24 * NFIX;
+        const int wy = (w * 52) >> 8, wx = w - 5 * wy;
+        const int base = n * kPkAgent + wy * (2 * (kPadHW / 2)) + wx;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) adr[ti][k] = 4 * (base + role[k]);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // (pinned: an address is complete HERE, nothing of it is recomputed next to its read)
+        asm volatile("" : "+v"(adr[ti][0]), "+v"(adr[ti][1]), "+v"(adr[ti][2]), "+v"(adr[ti][3]), "+v"(adr[ti][4]));
+#endif
+    }
+    unsigned selA[2], selC[2], selD[2];                   // [ox]: as b3_l0_stream
+    selA[0] = q < 3 ? 0x03020100u : 0x05040100u;  selA[1] = q < 3 ? 0x05040302u : 0x07060302u;
+    selC[0] = q < 3 ? 0x05040302u : 0x01000100u;  selC[1] = q < 3 ? 0x07060504u : 0x03020302u;
+    selD[0] = q < 3 ? 0x03020100u : 0x01000100u;  selD[1] = q < 3 ? 0x05040302u : 0x03020302u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(selA[0]), "+v"(selA[1]), "+v"(selC[0]), "+v"(selC[1]), "+v"(selD[0]), "+v"(selD[1]));
+#endif
+    v4f sc[2], sh[2];
+    load_ss(sstab + EncLayout::kBssL0, 32, 0, q, sc[0], sh[0]);
+    load_ss(sstab + EncLayout::kBssL0, 32, 1, q, sc[1], sh[1]);
+    unsigned d[DEPTH + 1][7];                             // roles a b c d e f g
+    v4f acc[2][2];
+    v4f run[2];
+    auto request = [&](unsigned (&dd)[7], auto hc) {       // the pixels of half-window H: tile H / 2 of this wave, oy = H & 1
+        constexpr int ti = decltype(hc)::value >> 1, oy = (decltype(hc)::value & 1) * (kPadHW / 2);
+        auto at = [&](int k) { return reinterpret_cast<const unsigned*>(smem + adr[ti][k]); };
+        dd[0] = at(0)[oy];
+        dd[4] = at(0)[oy + 7];
+        dd[1] = at(1)[oy];
+        dd[2] = at(2)[oy];
+        dd[3] = at(3)[oy];
+        dd[5] = at(4)[oy];
+        dd[6] = at(4)[oy + 1];
+    };
+    auto compute = [&](const unsigned (&dd)[7], auto oxc, v4f (&ac)[2]) {
+        constexpr int ox = decltype(oxc)::value;
+        const v4u bhv = {__builtin_amdgcn_perm(dd[1], dd[0], selA[ox]),
+                         __builtin_amdgcn_perm(dd[3], dd[2], ox ? 0x07060302u : 0x05040100u),
+                         __builtin_amdgcn_perm(dd[4], dd[3], selC[ox]),
+                         __builtin_amdgcn_perm(dd[6], dd[5], selD[ox])};
+        const v8b Bh = __builtin_bit_cast(v8b, bhv);
+#pragma unroll
+        for (int p = 2; p >= 0; --p)                          // small planes first: wl xh, wm xh, wh xh
+#pragma unroll
+            for (int i = 0; i < 2; ++i) ac[i] = mfma16b(A0[i][p], Bh, p == 2 ? vzero() : ac[i]);
+    };
+    auto epilogue = [&](const v4f (&ac)[2], int P) {       // running 2x2 max on the raw accumulators, BatchNorm (|scale|)
+#pragma unroll                                             // + ReLU + clamp once per tile; pinned where it stands
+        for (int i = 0; i < 2; ++i) {                      // (b3_l0_stream explains both)
+            run[i] = (P & 3) == 0 ? ac[i] : vmax(run[i], ac[i]);
+            if ((P & 3) == 3) {
+                run[i] = vfma(run[i], sc[i], sh[i]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) run[i][c] = b3_relu_clamp(run[i][c]);
+            }
+        }
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(run[0]), "+v"(run[1]));
+#endif
+    };
+    auto tile_done = [&](auto tic) {                       // the pooled tile ti of this wave: row wave + 4 ti of L1's input
+        const int t = wave + 4 * decltype(tic)::value;
+        v4f pl[3];
+        b3_split8_clamped(run[0], run[1], pl);
+        if (16 * t + j < 25 * NFIX) {
+            char* const dst = smem + l1in + t * kCpRow + lane * 16;
+#pragma unroll
+            for (int p = 0; p < 3; ++p) *reinterpret_cast<v4f*>(dst + p * kB3Frag) = pl[p];
+        }
+    };
+    // positions 0 .. 15 = (tile P >> 2, oy, ox); every index is a compile-time constant, as in b3_l0_stream
+    constexpr int NP = 16;
+    auto body = [&](auto kc) {
+        constexpr int P = decltype(kc)::value, H = P >> 1;
+        if constexpr ((P & 1) == 0 && H + DEPTH < NP / 2)
+            request(d[(H + DEPTH) % (DEPTH + 1)], std::integral_constant<int, H + DEPTH>{});
+        __builtin_amdgcn_sched_barrier(0);
+        compute(d[H % (DEPTH + 1)], std::integral_constant<int, (P & 1)>{}, acc[P & 1]);
+        if constexpr (P > 0) {
+            epilogue(acc[(P - 1) & 1], P - 1);
+            if constexpr (((P - 1) & 3) == 3) tile_done(std::integral_constant<int, ((P - 1) >> 2)>{});
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (P == NP - 1) {
+            epilogue(acc[P & 1], P);
+            tile_done(std::integral_constant<int, (P >> 2)>{});
+        }
+    };
+    [&]<int... K>(std::integer_sequence<int, K...>) {
+        (request(d[K % (DEPTH + 1)], std::integral_constant<int, K>{}), ...);
+    }(std::make_integer_sequence<int, DEPTH>{});
+    [&]<int... K>(std::integer_sequence<int, K...>) { (body(std::integral_constant<int, K>{}), ...); }(
+        std::make_integer_sequence<int, NP>{});
 }
 
 // ---- L1, column-packed: 32 -> 32 @ 5x5, columns c = pos * N + n; this wave's tiles are wave, wave + 4, .. ---------------
@@ -1435,7 +1631,8 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
                                                                  const PolicyTail pt) {
     constexpr int END = FUSED ? kb_FILT + 24 * KT : kb_END;
     // stop_flags: bits 0..7 = the measure build's early exit (GNNPP_STOP_AT), bit 8 = GNNPP_TUNE_ENCODER_ONE_PLANE is 0:
-    // every tile takes the three-plane word path (b3_l0_generic), whatever its pixels
+    // every tile takes the three-plane word path (b3_l0_generic), whatever its pixels; bit 9 = GNNPP_TUNE_POLICY_CP_TEAM_L0
+    // is 0: a one-plane tile of the constant team takes b3_l0_stream, not b3_l0_stream_fixed
     [[maybe_unused]] const int stop = stop_flags & 255;
     const bool force_planes = (stop_flags & kB3ForcePlanes) != 0;
     extern __shared__ __attribute__((aligned(16))) char gnnpp_smem[];
@@ -1671,7 +1868,13 @@ __global__ GNNPP_H2_VGPR_BUDGET __launch_bounds__(kThreads, 2) void encoder_kern
     // MFMAs of position P are issued, the BatchNorm / ReLU / max epilogue of position P - 1 runs beside them.  The
     // pooled outputs stay in registers until every wave is done with the pixels.
     {
-        if (one_plane) {
+        // a constant team of kCpTeamFixed: (window, agent) pairs on the columns, unless GNNPP_TUNE_POLICY_CP_TEAM_L0 is 0
+        bool packed_l0 = false;
+        if constexpr (CP && NFIX == kCpTeamFixed) packed_l0 = one_plane && (stop_flags & kB3L0ByAgent) == 0;
+        if (packed_l0) {
+            // (no output overlaps the pixels: nothing is held, the barrier below is the layer's only one)
+            if constexpr (CP && NFIX == kCpTeamFixed) b3_l0_stream_fixed<NFIX>(pk, sstab, gnnpp_smem, wave, lane);
+        } else if (one_plane) {
             // Window win's output fragments live at R + 3 KiB * win; the packed pixels occupy the first 14.4 KiB of R: a
             // window beyond them is written as soon as it is pooled, only a wave's first two windows wait in registers
             // for the barrier.
@@ -2025,6 +2228,13 @@ std::atomic<int> g_policy_column_packing{1};   // GNNPP_TUNE_POLICY_CP: 0 = agen
 // tests and the A/B tools, stated here and in _native.py rather than in include/gnnpp.h, like gnnpp_measure.h's.
 #define GNNPP_TUNE_POLICY_CP_TEAM 21
 std::atomic<int> g_policy_cp_team{1};
+// 1 (default): inside that instantiation a one-plane tile runs L0 with (window, agent) pairs on the MFMA columns
+// (b3_l0_stream_fixed); 0: L0 as b3_l0_stream runs it -- agents on the columns --, L1 and L2 unchanged (same logits to the
+// bit: every B fragment, every accumulator and every stored byte is the same).  Key 21 = 0 still selects the whole run-time
+// form, whatever this key says.  Stated here and in _native.py, like key 21.
+#define GNNPP_TUNE_POLICY_CP_TEAM_L0 22
+std::atomic<int> g_policy_cp_team_l0{1};
+static int b3_l0_flag() { return g_policy_cp_team_l0.load(std::memory_order_relaxed) ? 0 : kB3L0ByAgent; }
 std::atomic<int> g_encoder_one_plane{1};      // GNNPP_TUNE_ENCODER_ONE_PLANE: 0 = the three-plane word path for every tile
 static int b3_plane_flag() { return g_encoder_one_plane.load(std::memory_order_relaxed) ? 0 : kB3ForcePlanes; }
 std::atomic<int> g_encoder_cp_tile{0};   // GNNPP_TUNE_ENCODER_CP_TILE: 0 = heuristic, 1 .. 12 = agents per tile, 16 = never
@@ -2066,7 +2276,7 @@ static int policy_launch_fused_b3_k(const float* obs, const float* packed, const
     static LdsAttrOnce once;
     set_lds_attr_once(once, reinterpret_cast<const void*>(&encoder_kernel_b3<true, KT, CP, NFIX>), (int)kB3SmemFused);
     hipLaunchKernelGGL((encoder_kernel_b3<true, KT, CP, NFIX>), dim3(pt.B), dim3(kThreads), kB3SmemFused, st, obs, packed,
-                       static_cast<float*>(nullptr), pt.B * pt.N, b3_plane_flag(), pt);
+                       static_cast<float*>(nullptr), pt.B * pt.N, b3_plane_flag() | b3_l0_flag(), pt);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 template <int KT>

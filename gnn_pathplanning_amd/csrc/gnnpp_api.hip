@@ -578,6 +578,7 @@ int gnnpp_get_tuning(int key) {
         case GNNPP_TUNE_FILTER_PIPE_GRID: return g_filter_pipe_grid.load();
         case GNNPP_TUNE_POLICY_CP: return g_policy_column_packing.load();
         case GNNPP_TUNE_POLICY_CP_TEAM: return g_policy_cp_team.load();
+        case GNNPP_TUNE_POLICY_CP_TEAM_L0: return g_policy_cp_team_l0.load();
         case GNNPP_TUNE_ENCODER_CP_TILE: return g_encoder_cp_tile.load();
         case GNNPP_TUNE_FILTER_PLANE_ALIAS: return g_filter_plane_alias.load();
         case GNNPP_TUNE_TRAIN_WGRAD_WGS: return g_train_wgrad_wgs.load();
@@ -628,6 +629,10 @@ int gnnpp_set_tuning(int key, int value) {
         case GNNPP_TUNE_POLICY_CP_TEAM:
             if (value != 0 && value != 1) return GNNPP_ERR_ARG;
             g_policy_cp_team.store(value);
+            return GNNPP_OK;
+        case GNNPP_TUNE_POLICY_CP_TEAM_L0:
+            if (value != 0 && value != 1) return GNNPP_ERR_ARG;
+            g_policy_cp_team_l0.store(value);
             return GNNPP_OK;
         case GNNPP_TUNE_ENCODER_CP_TILE:
             if (value != 0 && value != 16 && (value < 1 || value > 12)) return GNNPP_ERR_ARG;
