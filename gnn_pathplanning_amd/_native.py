@@ -34,6 +34,7 @@ ROLLOUT_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_ro
 SCHEDULE_DRAW_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_schedule_draw.h')
 ROLLOUT_STREAM_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_stream.h')
 ROLLOUT_STREAM_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_stream_trace.h')
+ROLLOUT_TEAM_STREAM_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_team_stream.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
@@ -106,7 +107,8 @@ def _sources():
     return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [HEADER, MAPF_DISTANCE_HEADER, CASEGEN_HEADER,
                                                                           MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER,
                                                                           SCHEDULE_DRAW_HEADER, ROLLOUT_STREAM_HEADER,
-                                                                          CASEGEN_MAZE_HEADER, ROLLOUT_STREAM_TRACE_HEADER]
+                                                                          CASEGEN_MAZE_HEADER, ROLLOUT_STREAM_TRACE_HEADER,
+                                                                          ROLLOUT_TEAM_STREAM_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -409,6 +411,12 @@ ROLLOUT_STREAM_TRACE_SIGNATURES = {
     'gnnpp_rollout_stream_trace_record': (_ci, [_rollout, _rstream, _rstrace, _vp]),
     'gnnpp_rollout_stream_policy_steps_traced': (_ci, [_rollout] + [_vp] * 5 + [_ci, _ci, _ci, _rstream, _rstrace, _vp]),
 }
+# include/gnnpp_rollout_team_stream.h, the companion header of streamed rollouts of large teams: a table of its own for the
+# same reason (tests/test_rollout_team_stream_abi.py); it adds no struct
+ROLLOUT_TEAM_STREAM_SIGNATURES = {
+    'gnnpp_rollout_team_stream_begin': (_ci, [_rollout, _rstream, _vp]),
+    'gnnpp_rollout_team_stream_reseat': (_ci, [_rollout, _rstream, _ci, _vp, _cs, _vp]),
+}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
 MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 
@@ -416,14 +424,14 @@ MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
     build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES,
-    ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES, ROLLOUT_STREAM_SIGNATURES, CASEGEN_MAZE_SIGNATURES and
-    ROLLOUT_STREAM_TRACE_SIGNATURES; returns the library."""
+    ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES, ROLLOUT_STREAM_SIGNATURES, CASEGEN_MAZE_SIGNATURES,
+    ROLLOUT_STREAM_TRACE_SIGNATURES and ROLLOUT_TEAM_STREAM_SIGNATURES; returns the library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
             list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + \
             list(ROLLOUT_TRACE_SIGNATURES.items()) + list(SCHEDULE_DRAW_SIGNATURES.items()) + \
             list(ROLLOUT_STREAM_SIGNATURES.items()) + list(CASEGEN_MAZE_SIGNATURES.items()) + \
-            list(ROLLOUT_STREAM_TRACE_SIGNATURES.items()) + optional:
+            list(ROLLOUT_STREAM_TRACE_SIGNATURES.items()) + list(ROLLOUT_TEAM_STREAM_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

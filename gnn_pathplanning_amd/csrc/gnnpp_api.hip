@@ -34,6 +34,7 @@
 #include "rollout_trace_kernels.hip"       // the rollout's trace: a record launch behind each move, no simulator kernel touched
 #include "rollout_stream_kernels.hip"      // streamed rollouts: finished episode slots refilled from a case queue
 #include "rollout_stream_trace_kernels.hip"   // ... their trace: per-case tables, rows relative to the seat
+#include "rollout_team_stream_kernels.hip"    // ... for teams of up to GNNPP_ROLLOUT_MAX_TEAM agents, dense graph or lists
 
 using namespace gnnpp;
 
@@ -1066,14 +1067,16 @@ int gnnpp_rollout_policy_steps_traced(const gnnpp_rollout* r, const float* enc_p
 
 // include/gnnpp_rollout_stream.h: pointers and sizes first (GNNPP_ERR_ARG), then what the streamed path does not cover
 // (GNNPP_ERR_UNSUPPORTED); nothing is enqueued and no HIP call is made on an error
-static int rollout_stream_check(const gnnpp_rollout* r, const gnnpp_rollout_stream* s, bool reseat, int now) {
+// the GNNPP_ERR_ARG half, shared with gnnpp_rollout_team_stream.h (whose lists form needs no r->S)
+static int rollout_stream_args_check(const gnnpp_rollout* r, const gnnpp_rollout_stream* s, bool reseat, int now,
+                                     bool need_S = true) {
     if (!r || !s || !r->pos || !r->done || r->B <= 0 || r->N < 1 || r->H <= 0 || r->W <= 0 || s->C <= 0)
         return GNNPP_ERR_ARG;
     if (!s->case_grid || !s->case_start || !s->case_goal || !s->case_maxstep || !s->cursor || !s->slot_case ||
         !s->slot_t0 || !s->assign || !s->goal || !s->maxstep || !s->reached || !s->start_step || !s->end_step || !s->pos ||
         !s->radius || !s->stats || !s->lived || !s->slot || !s->t0)
         return GNNPP_ERR_ARG;
-    if (reseat && (!r->grid || !r->goal || !r->obs || !r->radius || !r->S || !r->reached || !r->start_step ||
+    if (reseat && (!r->grid || !r->goal || !r->obs || !r->radius || (need_S && !r->S) || !r->reached || !r->start_step ||
                    !r->end_step || !r->maxstep || !r->flags || !r->stats))
         return GNNPP_ERR_ARG;
     if ((r->grid_batched != 0) != (s->case_grid_batched != 0)) return GNNPP_ERR_ARG;
@@ -1083,6 +1086,12 @@ static int rollout_stream_check(const gnnpp_rollout* r, const gnnpp_rollout_stre
         if (!(s->commR > 0.0) || !(s->commR < 1.0e300) || now < 0 || now > (1 << 30)) return GNNPP_ERR_ARG;
     }
     if (r->tie_mode < 0 || r->tie_mode > 3) return GNNPP_ERR_ARG;
+    return GNNPP_OK;
+}
+
+static int rollout_stream_check(const gnnpp_rollout* r, const gnnpp_rollout_stream* s, bool reseat, int now) {
+    const int rc = rollout_stream_args_check(r, s, reseat, now);
+    if (rc != GNNPP_OK) return rc;
     if (r->N > GNNPP_ROLLOUT_MAX_AGENTS || (size_t)r->H * (size_t)r->W > kOneWaveMaxCells) return GNNPP_ERR_UNSUPPORTED;
     if (r->tie_mode == GNNPP_TIE_REPLAY || r->tie_mode == GNNPP_TIE_MT19937) return GNNPP_ERR_UNSUPPORTED;
     return GNNPP_OK;
@@ -1098,6 +1107,32 @@ int gnnpp_rollout_stream_reseat(const gnnpp_rollout* r, const gnnpp_rollout_stre
     const int rc = rollout_stream_check(r, s, true, now);
     if (rc != GNNPP_OK) return rc;
     return rollout_stream_reseat_launch(*r, *s, now, static_cast<hipStream_t>(stream));
+}
+
+// include/gnnpp_rollout_team_stream.h: the same order -- pointers and sizes, the lists block among them, then the scope
+static int rollout_team_stream_check(const gnnpp_rollout* r, const gnnpp_rollout_stream* s, bool reseat, int now,
+                                     const void* lists, size_t lists_bytes) {
+    const int rc = rollout_stream_args_check(r, s, reseat, now, lists == nullptr);
+    if (rc != GNNPP_OK) return rc;
+    if (lists && r->N <= GNNPP_ROLLOUT_MAX_TEAM && !team_lists_block_ok(lists, lists_bytes, r->B, r->N)) return GNNPP_ERR_ARG;
+    if (r->N <= GNNPP_ROLLOUT_MAX_AGENTS || r->N > GNNPP_ROLLOUT_MAX_TEAM ||
+        (size_t)r->H * (size_t)r->W > (size_t)GNNPP_ROLLOUT_TEAM_MAX_CELLS)
+        return GNNPP_ERR_UNSUPPORTED;
+    if (r->tie_mode == GNNPP_TIE_REPLAY || r->tie_mode == GNNPP_TIE_MT19937) return GNNPP_ERR_UNSUPPORTED;
+    return GNNPP_OK;
+}
+
+int gnnpp_rollout_team_stream_begin(const gnnpp_rollout* r, const gnnpp_rollout_stream* s, void* stream) {
+    const int rc = rollout_team_stream_check(r, s, false, 0, nullptr, 0);
+    if (rc != GNNPP_OK) return rc;
+    return rollout_stream_begin_launch(*r, *s, static_cast<hipStream_t>(stream));
+}
+
+int gnnpp_rollout_team_stream_reseat(const gnnpp_rollout* r, const gnnpp_rollout_stream* s, int now, void* lists,
+                                     size_t lists_bytes, void* stream) {
+    const int rc = rollout_team_stream_check(r, s, true, now, lists, lists_bytes);
+    if (rc != GNNPP_OK) return rc;
+    return rollout_team_stream_reseat_launch(*r, *s, now, lists, static_cast<hipStream_t>(stream));
 }
 
 // include/gnnpp_rollout_stream_trace.h: pointers and sizes first (GNNPP_ERR_ARG), then what a stream does not cover

@@ -413,6 +413,83 @@ __global__ __launch_bounds__(1024) void rollout_team_gso_kernel(const RolloutArg
     }
 }
 
+// rollout_team_gso_kernel as a device body (as gso_body of rollout_kernels.hip is for small teams), for the streamed seat
+// of rollout_team_stream_kernels.hip: the same statement, the same order of fp64 operations, the same stores.  Thread t of
+// nt = team_threads(N), every thread of the workgroup calls it, `smem` = team_gso_smem(N) bytes of LDS.  Reads pos[b] and
+// radius[b]; writes S[b], radius[b], connected[b].  The kernel above keeps its own text: called through this body it
+// measured 3.7 % slower at 8 x 1024 agents, so only the new kernel calls it.  A change to one is a change
+// to both; the streamed seat's tests (CPU and GPU) hold the body to the kernel bit for bit.
+__device__ __forceinline__ void team_gso_body(const RolloutArgs& p, int b, int t, int nt, int grow, char* smem) {
+    const int N = p.N, nw = nt >> 6;
+    int* px = reinterpret_cast<int*>(smem);                                         // [N]
+    int* py = px + N;                                                               // [N]
+    double* inv = reinterpret_cast<double*>(smem + round16((size_t)8 * N));         // [N]
+    unsigned long long* fr[2] = {reinterpret_cast<unsigned long long*>(inv + N), nullptr};
+    fr[1] = fr[0] + kTeamWords;
+    unsigned long long* words = fr[1] + kTeamWords;                                 // [kTeamWords]
+    const int* pos = p.pos + (size_t)b * N * 2;
+    const bool live = t < N;
+    int mx = 0, my = 0;
+    if (live) { mx = pos[2 * t]; my = pos[2 * t + 1]; px[t] = mx; py[t] = my; }
+    __syncthreads();
+    double r = p.radius[b];
+    if (grow) r = r / 1.1;
+    unsigned Tu = 0u;
+    bool connected = false;
+    // Termination with grow: r grows by 1.1 per trip, so the bound reaches 65535^2 (the largest d2 of two cells, below
+    // the clamp of dist2_bound) after finitely many trips; from then on every pair is an edge and the graph is connected.
+    for (;;) {
+        if (grow) r = r * 1.1;
+        Tu = dist2_bound(r);                             // d2 < 2^32 - 1: a map of 65 536 cells can be 1 x 65 536
+        bool in_r = t == 0;                              // reached set; the frontier starts as {0}
+        int cur = 0;
+        {
+            const unsigned long long m = __ballot(in_r);
+            if ((t & 63) == 0) fr[0][t >> 6] = m;
+        }
+        __syncthreads();
+        for (;;) {
+            bool join = false;
+            if (live && !in_r) {
+                for (int w = 0; w < nw && !join; ++w) {
+                    for (unsigned long long f = fr[cur][w]; f; f &= f - 1) {
+                        const int j = w * 64 + __ffsll((long long)f) - 1;
+                        if (dist2(px[j], py[j], mx, my) <= Tu) { join = true; break; }
+                    }
+                }
+            }
+            in_r |= join;
+            const unsigned long long m = __ballot(join);
+            if ((t & 63) == 0) fr[cur ^ 1][t >> 6] = m;
+            __syncthreads();
+            bool any = false;
+            for (int w = 0; w < nw; ++w) any |= fr[cur ^ 1][w] != 0ull;
+            cur ^= 1;                                    // (the old frontier is rewritten only after a barrier)
+            if (!any) break;
+        }
+        connected = !team_any(live && !in_r, words, t, nw);
+        if (connected || !grow) break;
+    }
+    if (live) {
+        int deg = 0;
+        for (int j = 0; j < N; ++j) deg += j != t && dist2(px[j], py[j], mx, my) <= Tu;
+        inv[t] = inv_sqrt_degree(deg);
+    }
+    __syncthreads();
+    // S: thread t owns columns t, t + nt, ...; rows go by (consecutive threads store consecutive floats)
+    float* S = p.S + (size_t)b * N * N;
+    for (int j = t; j < N; j += nt) {
+        const int jx = px[j], jy = py[j];
+        const double ij = inv[j];
+        for (int i = 0; i < N; ++i)
+            S[(size_t)i * N + j] = (i != j && dist2(px[i], py[i], jx, jy) <= Tu) ? (float)(inv[i] * ij) : 0.f;
+    }
+    if (t == 0) {
+        p.radius[b] = r;
+        if (p.connected) p.connected[b] = connected;
+    }
+}
+
 // ---- observation builder -----------------------------------------------------------------------------------------
 // rollout_observe_kernel with room for the goals of N agents: grid (ceil(N / 16), B), 16 agents per workgroup.
 __host__ __device__ inline size_t team_observe_smem(int N, int H, int W) {
@@ -435,6 +512,23 @@ __global__ __launch_bounds__(256) void rollout_team_observe_kernel(const Rollout
     observe_rows(p, b, pos, n0, n1, cell, goal_l, threadIdx.x, 256, stage);
     __syncthreads();
     observe_flush(p, b, n0, n1, stage, threadIdx.x, 256);
+}
+
+// rollout_team_observe_kernel's four stages for agents [n0, n0 + 16) of episode b, for the streamed seat: 256 threads,
+// `smem` = team_observe_smem(N, H, W) bytes of LDS
+__device__ __forceinline__ void team_observe_body(const RolloutArgs& p, int b, int n0, int tid, char* smem) {
+    int* goal_l = reinterpret_cast<int*>(smem);                              // [2N]
+    unsigned char* cell = reinterpret_cast<unsigned char*>(smem + round16((size_t)8 * p.N));
+    float* stage = reinterpret_cast<float*>(cell + round16((size_t)p.H * p.W));
+    const int* pos = p.pos + (size_t)b * p.N * 2;
+    observe_stage(p, b, cell, goal_l, tid, 256);
+    __syncthreads();
+    observe_prep(p, pos, cell, goal_l, tid, 256);
+    __syncthreads();
+    const int n1 = min(p.N, n0 + kObsAgentsPerWg);
+    observe_rows(p, b, pos, n0, n1, cell, goal_l, tid, 256, stage);
+    __syncthreads();
+    observe_flush(p, b, n0, n1, stage, tid, 256);
 }
 
 // ---- launchers (N > GNNPP_ROLLOUT_MAX_AGENTS) ---------------------------------------------------------------------

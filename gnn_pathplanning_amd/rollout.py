@@ -523,7 +523,8 @@ class RolloutStream:
 
     Scope: teams of 1 .. MAX_AGENTS agents, the dense graph, tie_mode 'lowest' or 'hashed'.  'hashed' hashes (seed, slot,
     global step), so a case draws a different -- equally arbitrary -- stream than in a plain rollout.  'replay', 'mt19937',
-    record=..., graph='lists' and N > MAX_AGENTS are refused by name before anything is enqueued.
+    record=..., graph='lists' and N > MAX_AGENTS are refused by name before anything is enqueued (larger teams, on the dense
+    graph or on lists: TeamRolloutStream).
 
     trace: True keeps a StreamTrace (`self.trace`) of max(maxstep) steps per case, an integer one of that many steps (refused
     when below max(maxstep): rows would be lost silently).  It is what BatchedRollout(record=...) keeps, per CASE and with
@@ -551,14 +552,33 @@ class RolloutStream:
                                      'BatchedRollout(record=...)')
         if graph != 'dense':
             raise _native.GnnppError("RolloutStream: graph=%r is not supported (a seat builds the dense GSO); use "
-                                     "graph='dense'" % (graph,))
+                                     "graph='dense', or TeamRolloutStream for teams of more than %d agents"
+                                     % (graph, MAX_AGENTS))
         starts_t, goals_t = torch.as_tensor(starts), torch.as_tensor(goals)
         C, N = int(starts_t.shape[0]), int(starts_t.shape[1])
         if N > MAX_AGENTS:
             raise _native.GnnppError('RolloutStream: N > %d (got N = %d) is not supported: the seat runs the one-wave '
-                                     'graph build' % (MAX_AGENTS, N))
+                                     'graph build; use TeamRolloutStream' % (MAX_AGENTS, N))
         if C < 1 or int(slots) < 1 or int(reseat_every) < 1:
             raise _native.GnnppError('RolloutStream: at least one case, one slot and reseat_every >= 1')
+        self._open_queue(grids, starts_t, goals_t, maxstep, dev, slots, commR, reseat_every)
+        T_cap = None
+        if trace is not False and trace is not None:
+            longest = int(self.case_maxstep.max().item())
+            T_cap = longest if trace is True else int(trace)
+            if T_cap < max(longest, 1):
+                raise _native.GnnppError('RolloutStream: trace=%d is below the longest case limit, max(maxstep) = %d: a '
+                                         'shorter trace would silently lose rows' % (T_cap, longest))
+        self._open_slots(tie_mode, seed, 'dense', _native.lib().gnnpp_rollout_stream_begin, 'gnnpp_rollout_stream_begin')
+        self.trace = None
+        if T_cap is not None:
+            self.trace = StreamTrace(self, T_cap)
+            self._trace_call(_native.lib().gnnpp_rollout_stream_trace_begin, 'gnnpp_rollout_stream_trace_begin')
+            self.env._stream_trace = self                     # every move of the slots is followed by _record()
+
+    def _open_queue(self, grids, starts_t, goals_t, maxstep, dev, slots, commR, reseat_every):
+        """The case queue on the device (nothing is enqueued but its copies)."""
+        C, N = int(starts_t.shape[0]), int(starts_t.shape[1])
         assert goals_t.shape == starts_t.shape and starts_t.shape[2] == 2
         _native.lib()
         self.device, self.C, self.N = dev, C, N
@@ -576,18 +596,14 @@ class RolloutStream:
         self.case_maxstep = (ms if ms.dim() else ms.repeat(C)).contiguous().to(dev)
         assert self.case_maxstep.shape == (C,)
         self._limit = int(self.case_maxstep.sum().item())     # (host bound of run(): no stream is longer than that)
-        T_cap = None
-        if trace is not False and trace is not None:
-            longest = int(self.case_maxstep.max().item())
-            T_cap = longest if trace is True else int(trace)
-            if T_cap < max(longest, 1):
-                raise _native.GnnppError('RolloutStream: trace=%d is below the longest case limit, max(maxstep) = %d: a '
-                                         'shorter trace would silently lose rows' % (T_cap, longest))
-        B = self.slots
+
+    def _open_slots(self, tie_mode, seed, graph, begin, what):
+        """The slots' BatchedRollout, the per-case tables, the struct, and `begin` (gnnpp_rollout_[team_]stream_begin)."""
+        dev, C, N, B = self.device, self.C, self.N, self.slots
         # the slots start as copies of the first cases (valid cells everywhere), all marked empty by begin()
         self.env = BatchedRollout(self.grid[:B].clone() if self.grid_batched else self.grid, self.start[:B].clone(),
-                                  self.goal[:B].clone(), self.case_maxstep[:B].clone(), dev, commR=commR,
-                                  tie_mode=tie_mode, seed=seed)
+                                  self.goal[:B].clone(), self.case_maxstep[:B].clone(), dev, commR=self.commR,
+                                  tie_mode=tie_mode, seed=seed, graph=graph)
         self.env._seated = True
         i32 = dict(dtype=torch.int32, device=dev)
         self.cursor = torch.zeros(1, **i32)
@@ -616,14 +632,8 @@ class RolloutStream:
             _p(self.case_t0)
         self._s = s
         with _native.device_guard(dev):
-            _native.check(_native.lib().gnnpp_rollout_stream_begin(ctypes.byref(e._r), ctypes.byref(s),
-                                                                   _native.stream_ptr(dev)), 'gnnpp_rollout_stream_begin')
+            _native.check(begin(ctypes.byref(e._r), ctypes.byref(s), _native.stream_ptr(dev)), what)
         self._reseated_at = -1                                # step count of the last reseat
-        self.trace = None
-        if T_cap is not None:
-            self.trace = StreamTrace(self, T_cap)
-            self._trace_call(_native.lib().gnnpp_rollout_stream_trace_begin, 'gnnpp_rollout_stream_trace_begin')
-            e._stream_trace = self                            # every move of the slots is followed by _record()
 
     def _trace_call(self, fn, what):
         with _native.device_guard(self.device):
@@ -687,7 +697,8 @@ class RolloutStream:
             if self.finished():
                 break
             if self.env.t > bound:
-                raise _native.GnnppError('RolloutStream.run: %d steps and the queue has not drained' % self.env.t)
+                raise _native.GnnppError('%s.run: %d steps and the queue has not drained'
+                                         % (type(self).__name__, self.env.t))
         return self.results()
 
     def results(self):
@@ -705,6 +716,83 @@ class RolloutStream:
                 'start_step': self.start_step.cpu(), 'positions': self.pos.cpu(), 'radius': self.radius.cpu(), 'done': done,
                 'slot': self.case_slot.cpu(), 't0': self.case_t0.cpu(), 'lived': lived,
                 'occupancy': float(lived[done].sum()) / total if total else 0.0}
+
+
+class TeamRolloutStream(RolloutStream):
+    """RolloutStream for teams of MAX_AGENTS + 1 .. MAX_TEAM agents (include/gnnpp_rollout_team_stream.h):
+    the same queue, slots, prefix rule of seating, per-case tables and results(), with the seat built by the large-team
+    kernels.  The stream owns a BatchedRollout(..., graph=graph) of min(slots, C) slots (`env`) and drives it on the
+    rollout's own large-team route:
+
+        graph='dense'   gso_observe, the planner's forward on S, move
+        graph='lists'   the lists launch and the observations, forward_logits_lists on the lists block, move: no dense S is
+                        ever allocated, and the planner is checked (BatchedRollout._check_lists_model) before anything is
+                        enqueued
+
+    A reseat is three launches (assign, harvest + seat with the step-0 radius search, the seated slots' observations); the
+    step after it builds every slot's graph again, a seated slot's at the radius its seat grew: the same bits.
+
+    Scope: tie_mode 'lowest' or 'hashed' (hashing (seed, slot, global step)), maps of at most MAX_TEAM_CELLS cells.
+    N <= MAX_AGENTS (use RolloutStream), N > MAX_TEAM, a larger map, 'replay', 'mt19937', record=... and trace=... (the
+    per-case trace of a large-team stream does not exist yet: gnnpp_rollout_stream_trace_* refuse N > MAX_AGENTS) are
+    refused by name before anything is enqueued."""
+
+    def __init__(self, grids, starts, goals, maxstep, device, slots=16, commR=6.0, tie_mode='lowest', seed=0,
+                 reseat_every=1, graph='dense', record=False, trace=False):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise _native.GnnppError('TeamRolloutStream needs a HIP device (no CPU fallback)')
+        if tie_mode not in _TIE:
+            raise _native.GnnppError('unknown tie_mode %r (one of %s)' % (tie_mode, sorted(_TIE)))
+        if tie_mode in ('replay', 'mt19937'):
+            raise _native.GnnppError("TeamRolloutStream: tie_mode %r keeps per-episode state that a seat would have to "
+                                     "rewind; use 'lowest' or 'hashed'" % tie_mode)
+        if record is not False and record is not None:
+            raise _native.GnnppError('TeamRolloutStream: record=... is not supported (a trace is laid out per episode of a '
+                                     'fixed batch); use BatchedRollout(record=...)')
+        if trace is not False and trace is not None:
+            raise _native.GnnppError('TeamRolloutStream: trace=... is not supported yet: the per-case trace of a stream '
+                                     'covers teams of at most %d agents (RolloutStream(trace=...))' % MAX_AGENTS)
+        if graph not in GRAPHS:
+            raise _native.GnnppError('unknown graph %r (one of %s)' % (graph, list(GRAPHS)))
+        starts_t, goals_t, g = torch.as_tensor(starts), torch.as_tensor(goals), torch.as_tensor(grids)
+        C, N = int(starts_t.shape[0]), int(starts_t.shape[1])
+        if N <= MAX_AGENTS:
+            raise _native.GnnppError('TeamRolloutStream: N <= %d (got N = %d) is not supported: use RolloutStream, whose '
+                                     'seat runs the one-wave kernels' % (MAX_AGENTS, N))
+        if N > MAX_TEAM:
+            raise _native.GnnppError('TeamRolloutStream: N > %d (got N = %d) is not supported: at most %d agents per '
+                                     'episode' % (MAX_TEAM, N, MAX_TEAM))
+        if int(g.shape[-2]) * int(g.shape[-1]) > MAX_TEAM_CELLS:
+            raise _native.GnnppError('TeamRolloutStream: a map of at most %d cells (got %d x %d)'
+                                     % (MAX_TEAM_CELLS, int(g.shape[-2]), int(g.shape[-1])))
+        if C < 1 or int(slots) < 1 or int(reseat_every) < 1:
+            raise _native.GnnppError('TeamRolloutStream: at least one case, one slot and reseat_every >= 1')
+        self.graph = graph
+        self._open_queue(g, starts_t, goals_t, maxstep, dev, slots, commR, reseat_every)
+        self._open_slots(tie_mode, seed, graph, _native.lib().gnnpp_rollout_team_stream_begin,
+                         'gnnpp_rollout_team_stream_begin')
+        self.trace = None
+
+    def reseat(self):
+        """RolloutStream.reseat with the large-team seat: three launches on the current stream, nothing read on the host.
+        Seated slots get their step-0 state (radius growth, S or their columns of the lists block, observations) from the
+        seat itself."""
+        e = self.env
+        lists, nbytes = (_p(e.lists), e.lists.numel()) if self.graph == 'lists' else (None, 0)
+        with _native.device_guard(self.device):
+            _native.check(_native.lib().gnnpp_rollout_team_stream_reseat(ctypes.byref(e._r), ctypes.byref(self._s), e.t, lists,
+                                                                         nbytes, _native.stream_ptr(self.device)),
+                          'gnnpp_rollout_team_stream_reseat')
+        self._reseated_at = e.t
+        if e.t == 0:
+            e._state_step = 0         # every slot was just seated: the graph and the observations describe step 0
+
+    def steps(self, model, n):
+        """n policy steps of every slot, a reseat every `reseat_every` of them."""
+        if self.graph == 'lists':
+            self.env._check_lists_model(model)               # (before the reseat: nothing is enqueued for a planner refused)
+        return RolloutStream.steps(self, model, n)
 
 
 class GroupedRollout:
