@@ -35,6 +35,7 @@ SCHEDULE_DRAW_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_sc
 ROLLOUT_STREAM_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_stream.h')
 ROLLOUT_STREAM_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_stream_trace.h')
 ROLLOUT_TEAM_STREAM_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_team_stream.h')
+TRAIN_B3_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_train_b3.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
@@ -108,7 +109,7 @@ def _sources():
                                                                           MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER,
                                                                           SCHEDULE_DRAW_HEADER, ROLLOUT_STREAM_HEADER,
                                                                           CASEGEN_MAZE_HEADER, ROLLOUT_STREAM_TRACE_HEADER,
-                                                                          ROLLOUT_TEAM_STREAM_HEADER]
+                                                                          ROLLOUT_TEAM_STREAM_HEADER, TRAIN_B3_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -417,6 +418,17 @@ ROLLOUT_TEAM_STREAM_SIGNATURES = {
     'gnnpp_rollout_team_stream_begin': (_ci, [_rollout, _rstream, _vp]),
     'gnnpp_rollout_team_stream_reseat': (_ci, [_rollout, _rstream, _ci, _vp, _cs, _vp]),
 }
+# include/gnnpp_train_b3.h, the companion header of the opt-in bf16x3 training precision: a table of its own for the same
+# reason (tests/test_train_b3_pack.py); it adds no struct.  The _prec calls take the argument lists of
+# gnnpp_encoder_train_fwd / _bwd + (int precision, const void* pack_b3)
+TRAIN_B3_SIGNATURES = {
+    'gnnpp_train_pack_b3_bytes': (_cs, []),
+    'gnnpp_train_pack_b3': (_ci, [_enc, _vp, _vp]),
+    'gnnpp_encoder_train_fwd_prec': (_ci, SIGNATURES['gnnpp_encoder_train_fwd'][1] + [_ci, _vp]),
+    'gnnpp_encoder_train_bwd_prec': (_ci, SIGNATURES['gnnpp_encoder_train_bwd'][1] + [_ci, _vp]),
+}
+# config field `trainPrecision` of DecentralPlannerNet -> the `precision` of the _prec calls (exact fp32 is the default)
+TRAIN_PRECISIONS = {'fp32': PREC_FP32_MFMA, 'bf16x3': PREC_FP32}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
 MEASURE_SIGNATURES = {'gnnpp_measure_read_stamps': (_ci, [_vp, _ci])}
 
@@ -425,13 +437,14 @@ def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
     build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES,
     ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES, ROLLOUT_STREAM_SIGNATURES, CASEGEN_MAZE_SIGNATURES,
-    ROLLOUT_STREAM_TRACE_SIGNATURES and ROLLOUT_TEAM_STREAM_SIGNATURES; returns the library."""
+    ROLLOUT_STREAM_TRACE_SIGNATURES, ROLLOUT_TEAM_STREAM_SIGNATURES and TRAIN_B3_SIGNATURES; returns the library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
             list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + \
             list(ROLLOUT_TRACE_SIGNATURES.items()) + list(SCHEDULE_DRAW_SIGNATURES.items()) + \
             list(ROLLOUT_STREAM_SIGNATURES.items()) + list(CASEGEN_MAZE_SIGNATURES.items()) + \
-            list(ROLLOUT_STREAM_TRACE_SIGNATURES.items()) + list(ROLLOUT_TEAM_STREAM_SIGNATURES.items()) + optional:
+            list(ROLLOUT_STREAM_TRACE_SIGNATURES.items()) + list(ROLLOUT_TEAM_STREAM_SIGNATURES.items()) + \
+            list(TRAIN_B3_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

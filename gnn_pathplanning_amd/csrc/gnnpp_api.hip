@@ -1,6 +1,7 @@
 // extern "C" surface of libgnnpp.so -- see include/gnnpp.h for the contract of every entry point.
 // Single translation unit: the kernels are included so hipcc builds one code object.
 #include "../../include/gnnpp.h"
+#include "../../include/gnnpp_train_b3.h"
 #ifdef GNNPP_MEASURE
 #include "gnnpp_measure.h"
 #endif
@@ -30,6 +31,7 @@
 #include "expert_team_lists_kernel.hip"    // the expert schedules' graphs as capped neighbour lists, and the draw from them
 #include "schedule_draw_kernels.hip"       // a training batch straight from stored schedules: only the picked steps are built
 #include "train_encoder.hip"
+#include "train_encoder_b3.hip"          // ... its convolutions on bf16x3 planes (opt-in training precision)
 #include "train_ops.hip"
 #include "rollout_trace_kernels.hip"       // the rollout's trace: a record launch behind each move, no simulator kernel touched
 #include "rollout_stream_kernels.hip"      // streamed rollouts: finished episode slots refilled from a case queue
@@ -447,10 +449,11 @@ int gnnpp_train_pack(const gnnpp_encoder_params* p, float* train_pack, const flo
     return train_pack_launch(p ? cw : nullptr, p ? train_pack : nullptr, fp, static_cast<hipStream_t>(stream));
 }
 
-int gnnpp_encoder_train_fwd(const gnnpp_encoder_params* p, const float* obs, float* workspace, float* feat,
-                            int B, int N, float momentum, int update_running,
-                            long long* const* bn_num_batches, int feat_sample_major, const float* train_pack,
-                            void* stream) {
+// pack_b3 != NULL: the nine convolution launches run on bf16x3 planes (gnnpp_train_b3.h); NULL: exact fp32
+static int encoder_train_fwd_call(const gnnpp_encoder_params* p, const float* obs, float* workspace, float* feat,
+                                  int B, int N, float momentum, int update_running,
+                                  long long* const* bn_num_batches, int feat_sample_major, const float* train_pack,
+                                  void* stream, const void* pack_b3) {
     EncRawParams rp;
     if (train_pack && (reinterpret_cast<size_t>(train_pack) & 15)) return GNNPP_ERR_ARG;
     if (!train_params_ok(p, rp) || !obs || !workspace || !feat || B <= 0 || N <= 0) return GNNPP_ERR_ARG;
@@ -463,19 +466,73 @@ int gnnpp_encoder_train_fwd(const gnnpp_encoder_params* p, const float* obs, flo
     }
     if (reinterpret_cast<size_t>(workspace) & 15) return GNNPP_ERR_ARG;      // (16-byte loads on its regions)
     return train_encoder_fwd(rp, rm, rv, update_running ? bn_num_batches : nullptr, momentum, obs, workspace, feat,
-                             N, B, feat_sample_major, static_cast<hipStream_t>(stream), train_pack);
+                             N, B, feat_sample_major, static_cast<hipStream_t>(stream), train_pack, pack_b3);
 }
 
-int gnnpp_encoder_train_bwd(const gnnpp_encoder_params* p, const float* obs, float* workspace,
-                            const float* dfeat, const gnnpp_encoder_grads* g, int B, int N,
-                            int feat_sample_major, const float* train_pack, void* stream) {
+static int encoder_train_bwd_call(const gnnpp_encoder_params* p, const float* obs, float* workspace,
+                                  const float* dfeat, const gnnpp_encoder_grads* g, int B, int N,
+                                  int feat_sample_major, const float* train_pack, void* stream, const void* pack_b3) {
     EncRawParams rp;
     if (train_pack && (reinterpret_cast<size_t>(train_pack) & 15)) return GNNPP_ERR_ARG;
     if (!train_params_ok(p, rp) || !obs || !workspace || !dfeat || !g || B <= 0 || N <= 0) return GNNPP_ERR_ARG;
     for (int i = 0; i < 5; ++i)
         if (!g->conv_w[i] || !g->conv_b[i] || !g->bn_w[i] || !g->bn_b[i]) return GNNPP_ERR_ARG;
     return train_encoder_bwd(rp, obs, workspace, dfeat, g->conv_w, g->conv_b, g->bn_w, g->bn_b, N, B,
-                             feat_sample_major, static_cast<hipStream_t>(stream), train_pack);
+                             feat_sample_major, static_cast<hipStream_t>(stream), train_pack, pack_b3);
+}
+
+int gnnpp_encoder_train_fwd(const gnnpp_encoder_params* p, const float* obs, float* workspace, float* feat,
+                            int B, int N, float momentum, int update_running,
+                            long long* const* bn_num_batches, int feat_sample_major, const float* train_pack,
+                            void* stream) {
+    return encoder_train_fwd_call(p, obs, workspace, feat, B, N, momentum, update_running, bn_num_batches,
+                                  feat_sample_major, train_pack, stream, nullptr);
+}
+
+int gnnpp_encoder_train_bwd(const gnnpp_encoder_params* p, const float* obs, float* workspace,
+                            const float* dfeat, const gnnpp_encoder_grads* g, int B, int N,
+                            int feat_sample_major, const float* train_pack, void* stream) {
+    return encoder_train_bwd_call(p, obs, workspace, dfeat, g, B, N, feat_sample_major, train_pack, stream, nullptr);
+}
+
+// ---- include/gnnpp_train_b3.h: the opt-in training precision ------------------------------------------------------
+size_t gnnpp_train_pack_b3_bytes(void) { return train_pack_b3_layout().total; }
+
+int gnnpp_train_pack_b3(const gnnpp_encoder_params* p, void* pack_b3, void* stream) {
+    if (!p || !pack_b3 || (reinterpret_cast<size_t>(pack_b3) & 15)) return GNNPP_ERR_ARG;
+    const float* cw[5];
+    for (int i = 0; i < 5; ++i) {
+        if (!p->conv_w[i]) return GNNPP_ERR_ARG;
+        cw[i] = p->conv_w[i];
+    }
+    return train_pack_b3_launch(cw, pack_b3, static_cast<hipStream_t>(stream));
+}
+
+// GNNPP_OK and the pack the launches read (NULL: exact fp32), or the refusal of (precision, pack_b3)
+static int train_prec_ok(int precision, const void*& pack_b3) {
+    if (precision == GNNPP_PREC_FP32_MFMA) { pack_b3 = nullptr; return GNNPP_OK; }
+    if (precision != GNNPP_PREC_FP32) return GNNPP_ERR_UNSUPPORTED;
+    if (!pack_b3 || (reinterpret_cast<size_t>(pack_b3) & 15)) return GNNPP_ERR_ARG;
+    return GNNPP_OK;
+}
+
+int gnnpp_encoder_train_fwd_prec(const gnnpp_encoder_params* p, const float* obs, float* workspace, float* feat,
+                                 int B, int N, float momentum, int update_running,
+                                 long long* const* bn_num_batches, int feat_sample_major, const float* train_pack,
+                                 void* stream, int precision, const void* pack_b3) {
+    const int rc = train_prec_ok(precision, pack_b3);
+    if (rc != GNNPP_OK) return rc;
+    return encoder_train_fwd_call(p, obs, workspace, feat, B, N, momentum, update_running, bn_num_batches,
+                                  feat_sample_major, train_pack, stream, pack_b3);
+}
+
+int gnnpp_encoder_train_bwd_prec(const gnnpp_encoder_params* p, const float* obs, float* workspace,
+                                 const float* dfeat, const gnnpp_encoder_grads* g, int B, int N,
+                                 int feat_sample_major, const float* train_pack, void* stream, int precision,
+                                 const void* pack_b3) {
+    const int rc = train_prec_ok(precision, pack_b3);
+    if (rc != GNNPP_OK) return rc;
+    return encoder_train_bwd_call(p, obs, workspace, dfeat, g, B, N, feat_sample_major, train_pack, stream, pack_b3);
 }
 
 size_t gnnpp_gemm_workspace_floats(int batch, int M, int N, int K) {

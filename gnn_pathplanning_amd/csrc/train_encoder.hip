@@ -1077,6 +1077,11 @@ static void conv_launch(int l, bool input_grad, const float* x, const float* wpa
 #undef GNNPP_CONV
 }
 
+// csrc/train_encoder_b3.hip: the same launch on bf16x3 planes (opt-in training precision); pack_b3 = the caller's
+// gnnpp_train_pack_b3 buffer of the current weights
+void conv_b3_launch(int l, bool input_grad, const float* x, const void* pack_b3, const float* bias, float* y,
+                    float* part, int N, int B, long sn, long sb, hipStream_t st);
+
 // obs: [B][N][3][11][11] (the reference's inputTensor, decentralplanner.py:278-286); feat = x_5 [N][B][128], or
 // [B][N][128] with feat_bn (sample-major: node-major rows for the graph filter, no transposing copy)
 // the ten packs of the encoder (+ the graph filter's two, fp.h != nullptr) in one launch
@@ -1096,7 +1101,7 @@ int train_pack_launch(const float* const* conv_w, float* enc_pack, const TrainFi
 int train_encoder_fwd(const EncRawParams& rp, float* const* rmean, float* const* rvar,
                       long long* const* num_batches, float momentum,
                       const float* obs, float* ws, float* feat, int N, int B, int feat_bn, hipStream_t st,
-                      const float* enc_pack = nullptr) {
+                      const float* enc_pack = nullptr, const void* pack_b3 = nullptr) {
     const TrainWs L = train_ws_layout(N, B);
     const TrainPackLayout PL = train_pack_layout();
     TrainPtrs5 pk = {}, run = {};
@@ -1129,7 +1134,8 @@ int train_encoder_fwd(const EncRawParams& rp, float* const* rmean, float* const*
         const float* xin = l == 0 ? obs : ws + L.xn[l - 1];
         const long sn = l == 0 ? (long)d.Cin * P : (long)B * d.Cin * P;        // obs is [B][N]: n is the inner index
         const long sb = l == 0 ? (long)N * d.Cin * P : (long)d.Cin * P;
-        conv_launch(l, false, xin, wt[l], rp.conv_b[l], ws + L.y[l], ws + L.part, N, B, sn, sb, st);
+        if (pack_b3) conv_b3_launch(l, false, xin, pack_b3, rp.conv_b[l], ws + L.y[l], ws + L.part, N, B, sn, sb, st);
+        else conv_launch(l, false, xin, wt[l], rp.conv_b[l], ws + L.y[l], ws + L.part, N, B, sn, sb, st);
         const BnTile t = bn_tile(l);
         BnRunningFuse f = {};
         const bool last = l == kTrainLayers - 1;
@@ -1153,7 +1159,8 @@ int train_encoder_fwd(const EncRawParams& rp, float* const* rmean, float* const*
 // dfeat: gradient w.r.t. x_5 [N][B][128]; writes d conv_w / d conv_b / d bn_w / d bn_b of every layer
 int train_encoder_bwd(const EncRawParams& rp, const float* obs, float* ws, const float* dfeat,
                       float* const* dconv_w, float* const* dconv_b, float* const* dbn_w, float* const* dbn_b,
-                      int N, int B, int feat_bn, hipStream_t st, const float* enc_pack = nullptr) {
+                      int N, int B, int feat_bn, hipStream_t st, const float* enc_pack = nullptr,
+                      const void* pack_b3 = nullptr) {
     const TrainWs L = train_ws_layout(N, B);
     const TrainPackLayout PL = train_pack_layout();
     const long NB = (long)N * B;
@@ -1192,8 +1199,11 @@ int train_encoder_bwd(const EncRawParams& rp, const float* obs, float* ws, const
             // dx [N][B][Cin][P] = conv(dy) with the flipped kernel; here "Cin" of the call = Cout of the layer
             float* dx = dx_buf[l & 1];
             // output channels of this call = d.Cin (a multiple of 16 for l >= 1)
-            conv_launch(l, true, dz, enc_pack ? enc_pack + PL.wtb[l] : ws + L.wtb[l], nullptr, dx, nullptr, N, B, (long)B * d.Cout * P,
-                        (long)d.Cout * P, st);
+            if (pack_b3)
+                conv_b3_launch(l, true, dz, pack_b3, nullptr, dx, nullptr, N, B, (long)B * d.Cout * P, (long)d.Cout * P, st);
+            else
+                conv_launch(l, true, dz, enc_pack ? enc_pack + PL.wtb[l] : ws + L.wtb[l], nullptr, dx, nullptr, N, B,
+                            (long)B * d.Cout * P, (long)d.Cout * P, st);
             dxn = dx;
         }
     }

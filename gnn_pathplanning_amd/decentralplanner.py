@@ -86,10 +86,12 @@ class _EncoderTrainFunction(torch.autograd.Function):
     reference hands to compressMLP at decentralplanner.py:287-289), with the reference's per-agent-call
     BatchNorm statistics; the running statistics receive their N momentum updates in place.  backward =
     gnnpp_encoder_train_bwd: gradients of the 20 conv / BatchNorm parameters (no gradient to obs: it is
-    data).  `tensors` = [conv_w, conv_b, bn_w, bn_b] x 5 layers; `buffers` = [running_mean, running_var] x 5."""
+    data).  `tensors` = [conv_w, conv_b, bn_w, bn_b] x 5 layers; `buffers` = [running_mean, running_var] x 5.
+    pack_b3: None (exact fp32, gnnpp_encoder_train_fwd / _bwd) or the gnnpp_train_pack_b3 buffer of the current weights
+    (config field trainPrecision='bf16x3': the convolutions on bf16x3 planes, gnnpp_encoder_train_fwd_prec / _bwd_prec)."""
 
     @staticmethod
-    def forward(ctx, obs, buffers, counters, momentum, eps, enc_pack, *tensors):
+    def forward(ctx, obs, buffers, counters, momentum, eps, enc_pack, pack_b3, *tensors):
         L = _native.lib()
         B, N = obs.shape[0], obs.shape[1]
         dev = obs.device
@@ -102,12 +104,15 @@ class _EncoderTrainFunction(torch.autograd.Function):
         wgs = L.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS)
         ws = torch.empty(L.gnnpp_encoder_train_workspace_floats(N, B), dtype=torch.float32, device=dev)
         feat = torch.empty(B, N, 128, dtype=torch.float32, device=dev)     # sample-major: node-major rows
+        args = (ctypes.byref(p), _ptr(obs), _ptr(ws), _ptr(feat), B, N, ctypes.c_float(momentum), int(buffers is not None),
+                (ctypes.c_void_p * 5)(*[c.data_ptr() for c in counters]) if counters is not None else None, 1,
+                _ptr(enc_pack), _native.stream_ptr(dev))
         with _native.device_guard(dev):
-            _native.check(L.gnnpp_encoder_train_fwd(ctypes.byref(p), _ptr(obs), _ptr(ws), _ptr(feat), B, N,
-                                                    ctypes.c_float(momentum), int(buffers is not None),
-                                                    (ctypes.c_void_p * 5)(*[c.data_ptr() for c in counters])
-                                                    if counters is not None else None, 1, _ptr(enc_pack),
-                                                    _native.stream_ptr(dev)), 'gnnpp_encoder_train_fwd')
+            if pack_b3 is None:
+                _native.check(L.gnnpp_encoder_train_fwd(*args), 'gnnpp_encoder_train_fwd')
+            else:
+                _native.check(L.gnnpp_encoder_train_fwd_prec(*args, _native.PREC_FP32, _ptr(pack_b3)),
+                              'gnnpp_encoder_train_fwd_prec')
         now = L.gnnpp_get_tuning(_native.TUNE_TRAIN_WGRAD_WGS)
         if now != wgs:
             raise _native.GnnppError('GNNPP_TUNE_TRAIN_WGRAD_WGS changed from %d to %d during the train-mode encoder '
@@ -116,6 +121,7 @@ class _EncoderTrainFunction(torch.autograd.Function):
         ctx.wgrad_wgs = wgs
         ctx.eps = float(eps)
         ctx.enc_pack = enc_pack                    # (the pack of THESE weights: the backward call reads its other half)
+        ctx.pack_b3 = pack_b3                      # (... and the precision the forward ran in)
         return feat
 
     @staticmethod
@@ -138,11 +144,15 @@ class _EncoderTrainFunction(torch.autograd.Function):
             g.conv_w[i], g.conv_b[i] = grads[4 * i].data_ptr(), grads[4 * i + 1].data_ptr()
             g.bn_w[i], g.bn_b[i] = grads[4 * i + 2].data_ptr(), grads[4 * i + 3].data_ptr()
         d = dfeat.contiguous().float()
+        args = (ctypes.byref(p), _ptr(obs), _ptr(ws), _ptr(d), ctypes.byref(g), B, N, 1, _ptr(ctx.enc_pack),
+                _native.stream_ptr(dev))
         with _native.device_guard(dev):
-            _native.check(L.gnnpp_encoder_train_bwd(ctypes.byref(p), _ptr(obs), _ptr(ws), _ptr(d), ctypes.byref(g),
-                                                    B, N, 1, _ptr(ctx.enc_pack), _native.stream_ptr(dev)),
-                          'gnnpp_encoder_train_bwd')
-        return (None, None, None, None, None, None) + tuple(grads)
+            if ctx.pack_b3 is None:
+                _native.check(L.gnnpp_encoder_train_bwd(*args), 'gnnpp_encoder_train_bwd')
+            else:
+                _native.check(L.gnnpp_encoder_train_bwd_prec(*args, _native.PREC_FP32, _ptr(ctx.pack_b3)),
+                              'gnnpp_encoder_train_bwd_prec')
+        return (None, None, None, None, None, None, None) + tuple(grads)
 
 
 class _LinearFunction(torch.autograd.Function):
@@ -294,6 +304,16 @@ class _OutputSlot:
         return stacked
 
 
+def train_precision(name):
+    """The config field `trainPrecision` checked: None (the field is absent) -> 'fp32'; a name outside
+    _native.TRAIN_PRECISIONS is refused by name."""
+    if name is None:
+        return 'fp32'
+    if not isinstance(name, str) or name not in _native.TRAIN_PRECISIONS:
+        raise _native.GnnppError('unknown trainPrecision %r (one of %s)' % (name, sorted(_native.TRAIN_PRECISIONS)))
+    return name
+
+
 def planner_route(training, N, Ns, L, E, widths, precision='fp32', largeGraphFilter='dense',
                   largeGraphTraining='dense'):
     """The route a forward of a planner takes, by name -- the ONE place that decides it; pure (no device, no module):
@@ -399,6 +419,7 @@ class DecentralPlannerNet(nn.Module):
         self._enc_cache = _native.PackCache()
         self._head_cache = _native.PackCache()
         self._train_pack_cache = _native.PackCache()
+        self._train_pack_b3_cache = _native.PackCache()
         self._ws = None
         self._ws_key = None
         self._ws_all = {}                          # feature workspaces by (rows, stream)
@@ -414,6 +435,11 @@ class DecentralPlannerNet(nn.Module):
         self.precision = getattr(self.config, 'precision', None) or DEFAULT_PRECISION
         self.range_policy = getattr(self.config, 'range_policy', 'strict')
         self._range_flag = None
+        # Optional config field `trainPrecision`: the arithmetic of the TRAIN-mode encoder's convolutions (forward and
+        # input gradient; include/gnnpp_train_b3.h) -- 'fp32' (default, also when the field is absent: exact fp32 MFMA,
+        # gnnpp_encoder_train_fwd / _bwd) or 'bf16x3' (both operands as three exact bf16 planes on the bf16 MFMA:
+        # fp32-equivalent, no input domain).  Eval mode never reads it.
+        self.trainPrecision = train_precision(getattr(self.config, 'trainPrecision', None))
 
     # ------------------------------------------------------------------------------------
     def addGSO(self, S):
@@ -855,8 +881,9 @@ class DecentralPlannerNet(nn.Module):
             buffers += [bn.running_mean, bn.running_var]
         counters = [self.ConvLayers[bi].num_batches_tracked for bi in _BN_IDX] if track else None   # += N each
         packs = self._train_packs(tensors)                                              # one launch per weight version
+        pack_b3 = self._train_pack_b3(tensors) if train_precision(self.trainPrecision) == 'bf16x3' else None
         feat = _EncoderTrainFunction.apply(obs, buffers if track else None, counters, float(momentum or 0.0),
-                                           float(eps), packs[0] if packs else None, *tensors)   # [B,N,128]
+                                           float(eps), packs[0] if packs else None, pack_b3, *tensors)   # [B,N,128]
         return (feat, packs) if with_packs else feat
 
     def _forward_train(self, inputTensor):
@@ -972,6 +999,26 @@ class DecentralPlannerNet(nn.Module):
                                                  gf.G, gf.F, gf.K, gf.E, _native.stream_ptr(dev)), 'gnnpp_train_pack')
             return enc, fwd, tr
         return self._train_pack_cache.get(ws + [h], build)
+
+    def _train_pack_b3(self, conv_tensors):
+        """The convolution weights as bf16x3 fragments (gnnpp_train_pack_b3) of the CURRENT weights: one launch per weight
+        version, invalidated where the step's other packs are (an optimizer step, load_state_dict, invalidate_packs)."""
+        ws = [conv_tensors[4 * i] for i in range(5)]
+        if any(t.dtype is not torch.float32 or not t.is_contiguous() or not t.is_cuda for t in ws):
+            raise _native.GnnppError("trainPrecision='bf16x3' needs contiguous fp32 convolution weights on the device")
+
+        def build():
+            L = _native.lib()
+            dev = ws[0].device
+            p = _native.EncoderParams()
+            for i in range(5):
+                p.conv_w[i] = ws[i].data_ptr()
+            pack = torch.empty(L.gnnpp_train_pack_b3_bytes(), dtype=torch.uint8, device=dev)
+            with _native.device_guard(dev):
+                _native.check(L.gnnpp_train_pack_b3(ctypes.byref(p), _ptr(pack), _native.stream_ptr(dev)),
+                              'gnnpp_train_pack_b3')
+            return pack
+        return self._train_pack_b3_cache.get(ws, build)
 
     def _forward_train_aten(self, inputTensor):
         """The same train-mode forward on stock aten / MIOpen ops (agents as convolution groups).  NOT
