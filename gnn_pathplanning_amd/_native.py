@@ -36,6 +36,7 @@ ROLLOUT_STREAM_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_r
 ROLLOUT_STREAM_TRACE_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_stream_trace.h')
 ROLLOUT_TEAM_STREAM_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_team_stream.h')
 TRAIN_B3_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_train_b3.h')
+ROLLOUT_SUMMARY_HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'gnnpp_rollout_summary.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-shared', '-fPIC',
                '-Wno-unused-result']
 
@@ -83,6 +84,13 @@ TUNE_POLICY_CP_TEAM = 21
 # pairs on the MFMA columns, 0 = with agents on the columns as every other form (same logits to the bit); key 21 = 0
 # selects the whole run-time form whatever this key says
 TUNE_POLICY_CP_TEAM_L0 = 22
+# include/gnnpp_rollout_summary.h (GNNPP_SUMMARY_*): the limits, then the words of out_i64 and of out_f64
+SUMMARY_MAX_GROUPS, SUMMARY_I64, SUMMARY_F64 = 64, 16, 8
+(SUMMARY_N, SUMMARY_N_REACH_ALL, SUMMARY_N_OPTIMAL, SUMMARY_AGENTS_REACHED, SUMMARY_N_DEGENERATE, SUMMARY_N_BAD_GROUP,
+ SUMMARY_SUM_MP_PRED, SUMMARY_SUM_MP_TARGET, SUMMARY_SUM_FT_PRED, SUMMARY_SUM_FT_TARGET, SUMMARY_MIN_REACHED,
+ SUMMARY_MAX_REACHED, SUMMARY_N_FAIL_SHIELDED, SUMMARY_N_COLLISION_FREE, SUMMARY_N_SHIELDED) = range(15)
+(SUMMARY_RATE_REACH, SUMMARY_AVG_DMP, SUMMARY_STD_DMP, SUMMARY_AVG_DFT, SUMMARY_STD_DFT, SUMMARY_MEAN_REACHED,
+ SUMMARY_M2_DMP, SUMMARY_M2_DFT) = range(8)
 PRECISIONS = {'fp32': PREC_FP32, 'fp32_mfma': PREC_FP32_MFMA, 'split_f16': PREC_SPLIT_F16}
 
 
@@ -109,7 +117,8 @@ def _sources():
                                                                           MAPF_AUDIT_HEADER, ROLLOUT_TRACE_HEADER,
                                                                           SCHEDULE_DRAW_HEADER, ROLLOUT_STREAM_HEADER,
                                                                           CASEGEN_MAZE_HEADER, ROLLOUT_STREAM_TRACE_HEADER,
-                                                                          ROLLOUT_TEAM_STREAM_HEADER, TRAIN_B3_HEADER]
+                                                                          ROLLOUT_TEAM_STREAM_HEADER, TRAIN_B3_HEADER,
+                                                                          ROLLOUT_SUMMARY_HEADER]
 
 
 def build(force=False, verbose=False, measure=False):
@@ -293,6 +302,14 @@ class RolloutStreamTraceStruct(ctypes.Structure):
                 ('T_cap', ctypes.c_int)]
 
 
+class RolloutSummaryIn(ctypes.Structure):
+    """struct gnnpp_rollout_summary_in (include/gnnpp_rollout_summary.h)."""
+    _fields_ = [('reached', ctypes.c_void_p), ('stats', ctypes.c_void_p), ('target_makespan', ctypes.c_void_p),
+                ('target_flowtime', ctypes.c_void_p), ('valid', ctypes.c_void_p), ('group', ctypes.c_void_p),
+                ('shielded', ctypes.c_void_p), ('audit_ok', ctypes.c_void_p), ('C', ctypes.c_int), ('N', ctypes.c_int),
+                ('G', ctypes.c_int), ('target_stride', ctypes.c_int)]
+
+
 _vp, _ci, _cs, _ll, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_float
 _enc, _rollout = ctypes.POINTER(EncoderParams), ctypes.POINTER(RolloutStruct)
 _sched, _mapf, _gemm = ctypes.POINTER(ScheduleStruct), ctypes.POINTER(MapfStruct), ctypes.POINTER(GemmDesc)
@@ -427,6 +444,12 @@ TRAIN_B3_SIGNATURES = {
     'gnnpp_encoder_train_fwd_prec': (_ci, SIGNATURES['gnnpp_encoder_train_fwd'][1] + [_ci, _vp]),
     'gnnpp_encoder_train_bwd_prec': (_ci, SIGNATURES['gnnpp_encoder_train_bwd'][1] + [_ci, _vp]),
 }
+# include/gnnpp_rollout_summary.h, the companion header of a rollout's summary: a table of its own for the same reason
+# (tests/test_rollout_summary_abi.py)
+ROLLOUT_SUMMARY_SIGNATURES = {
+    'gnnpp_rollout_summary_out_bytes': (_cs, [_ci, _ci]),
+    'gnnpp_rollout_summary': (_ci, [ctypes.POINTER(RolloutSummaryIn), _vp, _vp]),
+}
 # config field `trainPrecision` of DecentralPlannerNet -> the `precision` of the _prec calls (exact fp32 is the default)
 TRAIN_PRECISIONS = {'fp32': PREC_FP32_MFMA, 'bf16x3': PREC_FP32}
 # csrc/gnnpp_api.hip, -DGNNPP_MEASURE builds only (int gnnpp_measure_read_stamps(unsigned long long* host, int n))
@@ -437,14 +460,15 @@ def bind(library):
     """Give every exported call of an opened build of csrc/gnnpp_api.hip (the product, the measure build, the tests' host
     build) its prototype from SIGNATURES, MAPF_DISTANCE_SIGNATURES, CASEGEN_SIGNATURES, MAPF_AUDIT_SIGNATURES,
     ROLLOUT_TRACE_SIGNATURES, SCHEDULE_DRAW_SIGNATURES, ROLLOUT_STREAM_SIGNATURES, CASEGEN_MAZE_SIGNATURES,
-    ROLLOUT_STREAM_TRACE_SIGNATURES, ROLLOUT_TEAM_STREAM_SIGNATURES and TRAIN_B3_SIGNATURES; returns the library."""
+    ROLLOUT_STREAM_TRACE_SIGNATURES, ROLLOUT_TEAM_STREAM_SIGNATURES, TRAIN_B3_SIGNATURES and ROLLOUT_SUMMARY_SIGNATURES;
+    returns the library."""
     optional = [item for item in MEASURE_SIGNATURES.items() if hasattr(library, item[0])]
     for name, (restype, argtypes) in list(SIGNATURES.items()) + list(MAPF_DISTANCE_SIGNATURES.items()) + \
             list(CASEGEN_SIGNATURES.items()) + list(MAPF_AUDIT_SIGNATURES.items()) + \
             list(ROLLOUT_TRACE_SIGNATURES.items()) + list(SCHEDULE_DRAW_SIGNATURES.items()) + \
             list(ROLLOUT_STREAM_SIGNATURES.items()) + list(CASEGEN_MAZE_SIGNATURES.items()) + \
             list(ROLLOUT_STREAM_TRACE_SIGNATURES.items()) + list(ROLLOUT_TEAM_STREAM_SIGNATURES.items()) + \
-            list(TRAIN_B3_SIGNATURES.items()) + optional:
+            list(TRAIN_B3_SIGNATURES.items()) + list(ROLLOUT_SUMMARY_SIGNATURES.items()) + optional:
         f = getattr(library, name)                           # (a missing export raises here, at load time)
         f.restype, f.argtypes = restype, argtypes
     return library

@@ -37,6 +37,7 @@
 #include "rollout_stream_kernels.hip"      // streamed rollouts: finished episode slots refilled from a case queue
 #include "rollout_stream_trace_kernels.hip"   // ... their trace: per-case tables, rows relative to the seat
 #include "rollout_team_stream_kernels.hip"    // ... for teams of up to GNNPP_ROLLOUT_MAX_TEAM agents, dense graph or lists
+#include "rollout_summary_kernels.hip"        // the reference's metrics of a rollout's per-case tables, one launch
 
 using namespace gnnpp;
 
@@ -1242,6 +1243,21 @@ int gnnpp_rollout_stream_policy_steps_traced(const gnnpp_rollout* r, const float
         if (rc != GNNPP_OK) return rc;
     }
     return GNNPP_OK;
+}
+
+// include/gnnpp_rollout_summary.h: every check before any HIP call, nothing enqueued on an error
+size_t gnnpp_rollout_summary_out_bytes(int N, int G) {
+    if (N < 1 || G < 1 || G > GNNPP_SUMMARY_MAX_GROUPS) return 0;
+    return summary_out_bytes(N, G);
+}
+
+int gnnpp_rollout_summary(const gnnpp_rollout_summary_in* in, void* out, void* stream) {
+    if (!in || !out || !in->reached || !in->stats || !in->target_makespan || !in->target_flowtime) return GNNPP_ERR_ARG;
+    if (in->C <= 0 || in->N < 1 || in->G < 1 || in->G > GNNPP_SUMMARY_MAX_GROUPS || in->target_stride < 1)
+        return GNNPP_ERR_ARG;
+    if ((!in->group && in->G != 1) || (long long)in->C * in->N > 0x7fffffffLL) return GNNPP_ERR_ARG;
+    if (reinterpret_cast<size_t>(out) & 7) return GNNPP_ERR_ARG;
+    return rollout_summary_launch(*in, out, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
